@@ -11,8 +11,11 @@ framebuffer over RCCL; total work is fixed ("strong").
 WORLD_SIZE in the environment) it is one rank; started plainly with N > 1 it starts that launcher
 itself as a CHILD process, before anything touches the GPU, and relays its exit code.
 
-Prints ONE JSON line on rank 0 (contract in the task statement); see DESIGN.md "Measurement"
-for how roofline.achieved, roofline.traffic, verify and cpu_baseline are defined.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+--steps renders and prints the headline figures; `--full` adds the untimed extras (the single-pipeline
+and counting renders behind verify, roofline*, work, and the cpu_baseline leg with its oracle checks);
+see DESIGN.md "Measurement" for how they are defined.  `--dump-outputs DIR` writes the image of the
+last timed step to DIR/image.npy.
 """
 import argparse
 import hashlib
@@ -36,6 +39,19 @@ VALU_PEAK_LANE_OPS = 256 * 4 * 2.4e9 / 4 * 64
 LANE_OPS_PER_BOX = 20.0      # 6 fma + 6 min/max + 2 min3/max3 + scale, compare, select of one slab test (pt_kernels.hip, node step)
 LANE_OPS_PER_TRI = 45.0      # Moeller-Trumbore with precomputed edges: 2 cross, 4 dot, reciprocal, 5 compares (pt_device_math.h)
 WINDOW = (480, 320, 608, 384)   # 128 x 64 pixels over the sphere's silhouette: the cpu_baseline sample and the oracle check
+DUMP_MAX_BYTES = 60 << 20       # --dump-outputs stays below 64 MB: larger images are written as an every-k-th-pixel sample
+
+
+def dump_outputs(d, image):
+    """--dump-outputs: the (H, W, 3) float32 image a caller of the timed path receives, as DIR/image.npy; an image over
+    DUMP_MAX_BYTES goes out as DIR/image_sample.npy, every k-th pixel of it in row-major order, shape (n, 3)."""
+    os.makedirs(d, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    k = img.nbytes // DUMP_MAX_BYTES + 1
+    if k == 1:
+        np.save(os.path.join(d, "image.npy"), img)
+    else:
+        np.save(os.path.join(d, "image_sample.npy"), img.reshape(-1, 3)[::k].copy())
 
 
 def kernel_source_sha():
@@ -133,6 +149,8 @@ def fanout_main(args):
             t = ms.timing()
             per_rank.append(t["render_ms_per_device"]); gathers.append(t["gather_ms"]); totals.append(t["total_ms"])
         dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, img)
     pr = np.array(per_rank)
     out = {"metric": "Msamples/s (paths/s) at 1024^2 x 256spp", "value": W * H * args.spp * args.steps / dt / 1e6, "unit": "Msamples/s",
            "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -163,10 +181,14 @@ def main():
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--tris", type=int, default=100_000)
     ap.add_argument("--depth", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed extras: the single-pipeline and work-counting renders behind "
+                         "`verify`, `roofline*` and `work`, and the CPU baseline with its oracle checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the image of the last timed step to DIR/image.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its oracle checks")
     ap.add_argument("--single-pipeline", action="store_true", help="one pass in flight at a time (HPT_FLAG_SINGLE_PIPELINE) in every step")
-    ap.add_argument("--no-exclusive-step", action="store_true", help="skip the extra untimed single-pipeline step that measures the kernels' exclusive durations")
-    ap.add_argument("--no-count-step", action="store_true", help="skip the untimed work-counting render (profiling runs: the timed kernels only)")
+    ap.add_argument("--no-exclusive-step", action="store_true", help="--full without the extra untimed single-pipeline step that measures the kernels' exclusive durations")
+    ap.add_argument("--no-count-step", action="store_true", help="--full without the untimed work-counting render (profiling runs: the timed kernels only)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the multi-rank path on a one-GPU box)")
     ap.add_argument("--pmc-file", default=os.path.join(ROOT, "profiles", "r03_pmc_traffic.json"))
     ap.add_argument("--fanout", action="store_true",
@@ -259,7 +281,7 @@ def main():
     first_image = None
     for i in range(args.warmup):
         step(base_flags)
-        if i == 0 and rank == 0:
+        if i == 0 and rank == 0 and args.full:
             first_image = image.clone()
     fence()
     t0 = time.perf_counter()
@@ -286,12 +308,14 @@ def main():
         everyone = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(everyone, mine)
         rank_ms = np.array([t.cpu().numpy() for t in everyone])          # [rank][step]
-    timed_image = image.clone() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, image.cpu().numpy())
+    timed_image = image.clone() if rank == 0 and args.full else None
 
-    # ---- untimed: checks of what was just timed + the kernels' exclusive durations + the work counts ----
+    # ---- --full, untimed: checks of what was just timed + the kernels' exclusive durations + the work counts ----
     verify = {}
     excl = None
-    if not args.single_pipeline and not args.no_exclusive_step:
+    if args.full and not args.single_pipeline and not args.no_exclusive_step:
         # same render with one pass in flight at a time: the kernels' durations when they have the device to
         # themselves, and the image the two-pipeline render must reproduce bit for bit
         step(hpt.FLAG_SINGLE_PIPELINE | hpt.FLAG_TIME_KERNELS)
@@ -302,14 +326,14 @@ def main():
     if rank == 0 and first_image is not None:
         verify["timed_image_equals_first_warmup_image"] = bool(torch.equal(timed_image, first_image))
     wc = None
-    if not args.no_count_step:
+    if args.full and not args.no_count_step:
         # the same render again, counting boxes / triangles / rays per kernel (plain single-launch traversal)
         step(hpt.FLAG_COUNT_WORK)
         fence()
         wc = scene.stats()
         if rank == 0:
             verify["timed_image_equals_counting_render"] = bool(torch.equal(timed_image, image))
-    if rank == 0:
+    if rank == 0 and args.full:
         verify["timed_image_finite_and_lit"] = bool(torch.isfinite(timed_image).all().item() and timed_image.mean().item() > 0)
 
     if rank == 0:
@@ -437,7 +461,7 @@ def main():
                            "device_ms_per_step_rank0": tot_ms / args.steps,
                            "kernel_ms_last_step_rank0": {"trace": st["ms_extend"] + st["ms_connect"] + st["ms_resume"], "shade": shade_ms, "other": other_ms},
                            "bvh_nodes": wc["bvh_nodes"], "bvh_depth": wc["bvh_depth"], "ms_bvh_build": wc["ms_bvh_build"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], ref_win, ref_spp = cpu_baseline(lights, spheres, tris, W, H, args.depth)
             # the oracle's window against the GPU render of the same samples (same seed, same spp)
             step(base_flags, spp=ref_spp)
@@ -461,7 +485,8 @@ def main():
                                                      "device": {k: int(dev_counts[k]) for k in keys}, "host_walk": {k: int(host_counts[k]) for k in keys},
                                                      "equal": all(int(dev_counts[k]) == int(host_counts[k]) for k in keys),
                                                      "images_bit_identical": bool(np.array_equal(small, ref_small))}
-        out["verify"] = verify
+        if args.full:
+            out["verify"] = verify
         real_stdout.write(json.dumps(out) + "\n")
         real_stdout.flush()
     scene.close()

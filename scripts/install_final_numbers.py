@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Copies what scripts/gpu_final_numbers.sh wrote under gpurun_out/r03_final/ into profiles/r03_* and prints the headline figures."""
-import json, sys
-tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-src = "gpurun_out/%s_final/" % tag
+"""Copies what scripts/gpu_final_numbers.sh wrote into its output directory to profiles/<tag>_* and prints the headline figures.
+usage: python scripts/install_final_numbers.py <tag> <output directory of gpu_final_numbers.sh>"""
+import json, os, sys
+tag = sys.argv[1]
+src = os.path.join(sys.argv[2], "")
 m = {"bench_line": "bench_line", "bench_configs": "bench_configs", "first_call": "first_call", "host_boundary": "host_boundary",
      "bench_fanout_1": "bench_fanout_1gpu", "bench_2ranks_gloo_one_gpu": "bench_2ranks_gloo_one_gpu"}
 for a, b in m.items():

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Round profile of the bench workload.  Usage on the GPU box:  bash scripts/profile_round.sh <tag>
-#   trace / trace_single   rocprofv3 --kernel-trace --stats of `bench.py --steps 2 --warmup 1` (two pipelines / one)
+#   trace / trace_single   rocprofv3 --kernel-trace --stats of `bench.py --steps 2 --warmup 1` (two pipelines with the
+#                          counting render of --full, whose `work` line profile_summarize.py reads / one pipeline)
 #   pass_*                 one 128-spp pass (`--steps 1 --warmup 0 --spp 128 --single-pipeline`, nothing else rendered:
 #                          no counting render, no exclusive step), one PMC counter set per run -- counters are never
 #                          combined with anything but --kernel-trace
@@ -11,7 +12,7 @@ TAG="${1:-r02}"
 OUT="$ROOT/gpurun_out/$TAG"
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-exclusive-step > "$OUT/trace.log" 2> "$OUT/trace.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --no-exclusive-step > "$OUT/trace.log" 2> "$OUT/trace.err"
 echo "trace exit $?"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_single" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --single-pipeline --no-count-step > "$OUT/trace_single.log" 2> "$OUT/trace_single.err"
 echo "trace (single pipeline) exit $?"

@@ -210,7 +210,7 @@ def test_bench_self_spawned_ranks_share_the_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "256",
-                          "--spp", "16", "--tris", "5000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+                          "--spp", "16", "--tris", "5000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [l for l in run.stdout.splitlines() if l.strip()]
@@ -223,6 +223,30 @@ def test_bench_self_spawned_ranks_share_the_gpu():
     assert len(r["render_ms_per_rank_mean_over_steps"]) == 2 and len(r["render_ms_every_step"]) == 2 and len(r["render_ms_every_step"][0]) == 1
     assert r["render_ms_max_rank"] >= r["render_ms_mean_rank"] > 0 and r["load_balance_max_over_mean"] >= 1.0
     assert len(out["exchange"]["gather_ms_every_step_rank0"]) == 1
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_timed_image(tmp_path, hpt, sio):
+    """`python bench.py --gpus 1` without --full: the headline line only (no untimed extras), --steps timed steps, and
+    --dump-outputs writes the image of the last timed step -- the same image a direct render of the scene gives."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", "256", "--spp", "16", "--tris", "5000",
+                          "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = [l for l in run.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, run.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["unit"] == "Msamples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert not {"verify", "roofline", "roofline_valu", "roofline_shade", "work", "cpu_baseline"} & set(out)
+    img = np.load(str(tmp_path / "image.npy"))
+    assert img.dtype == np.float32 and img.shape == (256, 256, 3)
+    L, sp, tr, cam = _cornell(sio, 5000, 256, 256)
+    with hpt.Scene(L, sp, tr) as scene:
+        ref = scene.render_pt(cam, 256, 256, 4, 16, hpt.make_params(seed=1))
+    assert np.array_equal(img, ref)
 
 
 def test_bench_fanout_mode_times_the_one_process_fan_out():

@@ -111,6 +111,22 @@ def test_bench_starts_its_own_ranks_as_a_child_process(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_stays_under_its_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the whole image as float32 while it fits, else every k-th pixel below DUMP_MAX_BYTES."""
+    import importlib
+    bench = importlib.import_module("bench")
+    img = np.random.default_rng(5).random((40, 30, 3)).astype(np.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    got = np.load(str(tmp_path / "whole" / "image.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    bench.dump_outputs(str(tmp_path / "sample"), img)
+    got = np.load(str(tmp_path / "sample" / "image_sample.npy"))
+    assert not os.path.exists(str(tmp_path / "sample" / "image.npy"))
+    assert got.dtype == np.float32 and got.nbytes <= 4000
+    assert np.array_equal(got, img.astype(np.float32).reshape(-1, 3)[::4])       # 14400 B // 4000 + 1 = every 4th pixel
+
+
 @pytest.mark.parametrize("G", [2, 4, 8])
 def test_gather_bytes_cover_the_tiled_image(hpt, G):
     """What N ranks send to the root in one step: `exchange.gather_bytes_per_rank` (12 B per packed local framebuffer
