@@ -60,8 +60,10 @@ typedef struct hpt_params {
     int32_t world;            /* number of devices sharing the image; 0 or 1 -> whole image */
     int32_t tile;             /* tile edge in pixels, multiple of 8; 0 -> 32 */
     int32_t samples_per_pass; /* samples of every local pixel in flight at once; 0 -> auto */
-    int32_t flags;            /* HPT_FLAG_* */
-    int32_t reserved;
+    int32_t flags;            /* HPT_FLAG_*; any other bit: HPT_ERR_INVALID */
+    int32_t reserved;         /* bits 1-6 (testing and tuning): node steps a PT ray gets in the first trace launch
+                               * before it is set aside for the resume launch; 0 = default, 63 = no split.  Every
+                               * other bit must be zero (HPT_ERR_INVALID) */
 } hpt_params;
 
 #define HPT_FLAG_BRUTE_FORCE 1   /* scan every primitive instead of the BVH (tests) */

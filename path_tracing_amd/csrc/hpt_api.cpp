@@ -58,16 +58,19 @@ struct DevBuf {              // device allocation released on every return path
 };
 
 struct TimedLaunch { hipEvent_t a, b; int cls; };
-// Frames a scene whose rays are nearly all long used to render without the split (round 2: the binary resume launch cost
-// more than the single-launch walk there).  With the four-wide resume launch the split wins on that scene too (100 k random
-// triangles, 16 spp: 29.9 ms split, 33.1 unsplit binary, 30.6 unsplit four-wide), so the hold-off is switched off; the
-// asynchronous read-back of the set-aside share stays (hpt_stats.long_rays_last_pass).
-constexpr int kSplitHold = 0;
-constexpr int kMaxPipes = 4;             // passes of a render in flight at a time, at most (default 2; development: flags bits 29-30)
+// A scene whose rays are nearly all long keeps the split of the trace step frame after frame: with the four-wide resume
+// launch the split wins there too (100 k random triangles, 16 spp: 29.9 ms split, 33.1 unsplit binary, 30.6 unsplit
+// four-wide).  Round 2 rendered such scenes unsplit for a while ("split hold-off removed").
+constexpr int kMaxPipes = 2;             // passes of a render in flight at a time, at most
 // device memory per path slot of one pipeline (ensure_pass): path state 80 B, pending shadow ray 48 B, five queues of 4 B
 constexpr double kBytesPerPathSlot = 148.0;
 
 static_assert(sizeof(hpt_stats) == 312 && sizeof(hpt_params) == 40, "ABI records: keep path_tracing_amd/__init__.py and tests/test_boundary.py in step");
+
+// the documented bits of hpt_params (include/hpt.h): flags HPT_FLAG_*, reserved bits 1-6 (the trace budget)
+constexpr int32_t kKnownFlags = HPT_FLAG_BRUTE_FORCE | HPT_FLAG_COUNT_WORK | HPT_FLAG_OUTPUT_SUM | HPT_FLAG_TIME_KERNELS |
+                                HPT_FLAG_RUSSIAN_ROULETTE | HPT_FLAG_SINGLE_PIPELINE | HPT_FLAG_NO_HOST_WAIT;
+constexpr int32_t kReservedBudgetBits = 0x3F << 1;
 
 } // namespace
 
@@ -78,16 +81,12 @@ struct hpt_scene {
     float4 *d_tri_frames = nullptr;
     int device = 0;
     int stack_levels = kStackDepth;       // traversal stack entries per lane
-    int last_counter_stride = 0, last_budget = 0;   // layout of `counters` after the last PT render (0: not a PT render)
-    // default budget only: the share of rays the last split render set aside is read back asynchronously; a
-    // scene whose rays are nearly all long (every ray restarts: the split only costs) renders the next
-    // kSplitHold frames without the split, then is probed again
-    uint32_t *h_split = nullptr; int h_split_words = 0; hipEvent_t ev_split = nullptr;
-    bool split_probe_pending = false; int split_probe_stride = 0, split_hold = 0;
+    int last_counter_stride = 0;          // layout of `counters` after the last PT render (0: not a PT render)
+    int last_budget = 0;                  // node-step budget of the last PT render's first trace launch (0: unsplit)
     int num_cus = 256;
 
     // workspace, grown on demand.  Two passes of a PT render are in flight at a time (render_local), each with its own
-    // path state, queues and counters (pass[0] on the caller's stream, pass[1] on p2_stream) -- the kernels of one
+    // path state, queues and counters (pass[0] on the caller's stream, pass[1] on px_stream[1]) -- the kernels of one
     // fill the issue slots the other leaves idle; everything else (BDPT, probes) uses pass[0]
     struct PassBuffers {
         size_t cap_paths = 0;
@@ -168,14 +167,14 @@ int ensure_pass(PassBuffers &w, size_t paths, int n_counters){
     return HPT_OK;
 }
 
-// streams and events of the pipelines past the first (which runs on the caller's stream)
+// stream and events of the second pipeline (the first runs on the caller's stream)
 int ensure_pipes(hpt_scene *s, hipStream_t caller, int npipes){
     // The pipelines only overlap if their streams sit on different hardware queues.  The runtime maps streams
     // of one priority onto a small pool of queues (GPU_MAX_HW_QUEUES, 4 by default) by reference count, so once a
     // process holds a few more streams -- RCCL's, after a communicator exists -- a second stream of the caller's
     // priority can land on the caller's queue and the passes serialise (measured: 169 ms per config-3 render
     // instead of 161).  Streams of another priority come from another pool: the second pipeline takes the highest
-    // priority unless the caller's stream already has it, then the default one; further pipelines take the remaining levels in turn.
+    // priority unless the caller's stream already has it, then the default one.
     int pr_least = 0, pr_greatest = 0, pr_caller = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
     if(hipStreamGetPriority(caller, &pr_caller) != hipSuccess){ (void) hipGetLastError(); pr_caller = 0; }
@@ -250,6 +249,20 @@ int on_scene_device(const hpt_scene *s){
     return HPT_OK;
 }
 
+// hpt_params may only hold the documented bits: a stray bit is an error, not a silently different render
+int check_params(const hpt_params &P){
+    char msg[160];
+    if(P.flags & ~kKnownFlags){
+        snprintf(msg, sizeof msg, "hpt_params.flags: unknown bits 0x%x (HPT_FLAG_* are 0x%x)", (unsigned) (P.flags & ~kKnownFlags), (unsigned) kKnownFlags);
+        return fail(HPT_ERR_INVALID, msg);
+    }
+    if(P.reserved & ~kReservedBudgetBits){
+        snprintf(msg, sizeof msg, "hpt_params.reserved: bits 0x%x set; only bits 1-6 (the trace budget) may be", (unsigned) (P.reserved & ~kReservedBudgetBits));
+        return fail(HPT_ERR_INVALID, msg);
+    }
+    return HPT_OK;
+}
+
 // the wavefront render loop; everything is enqueued on `stream`
 int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int spp,
                  const hpt_params *params, float *d_local, hipStream_t stream){
@@ -259,6 +272,7 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
     if(int rcd = on_scene_device(s)) return rcd;
     hpt_params P; memset(&P, 0, sizeof P);
     if(params) P = *params;
+    if(int rcp = check_params(P)) return rcp;
     if(P.max_delta <= 0) P.max_delta = 64;
     if(P.max_delta > 250) P.max_delta = 250;
     Tiling tl;
@@ -272,9 +286,8 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
     const int flags = P.flags;
     const bool count = (flags & HPT_FLAG_COUNT_WORK) != 0;
     const bool timek = (flags & HPT_FLAG_TIME_KERNELS) != 0;
-    const bool brute = (flags & HPT_FLAG_BRUTE_FORCE) != 0;
-    const bool legacy = brute || (P.reserved & 1);          // separate extend/connect kernels (the scan variants)
-    const int kflags = (brute ? 1 : 0) | (count ? 2 : 0) | ((flags >> 16) & 1 ? 4 : 0);      // flags bits 16-31: development switches
+    const bool brute = (flags & HPT_FLAG_BRUTE_FORCE) != 0;      // separate extend/connect kernels (the scan variants)
+    const int kflags = (brute ? 1 : 0) | (count ? 2 : 0);
 
     // Samples in flight per pass: about 128 Mi path slots (19 GiB of path state, queues and shadow records per pipeline:
     // little on a 288 GB device).  Fewer, larger passes amortise the low-occupancy tail iterations of every pass
@@ -285,8 +298,7 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
     // is such a render (rank 0 of 4 at config 3, 64 Mi slots: one pass 37.2-37.4 ms, two half passes 35.3-36.5; of 2:
     // 72.1 -> 68.2; of 8: 19.5 -> 18.7; on another box 35.4 against 35.6: never a loss beyond the noise) -- unless it is
     // so small (< 1 Mi slots) that launch latencies are what it costs.
-    int npipes = (!(flags & HPT_FLAG_SINGLE_PIPELINE) && !count && !legacy) ? 2 + ((flags >> 29) & 3) : 1;     // flags bits 29-30 (development): 3 or 4 pipelines
-    if(npipes > kMaxPipes) npipes = kMaxPipes;
+    int npipes = (!(flags & HPT_FLAG_SINGLE_PIPELINE) && !count && !brute) ? kMaxPipes : 1;
     int spass = P.samples_per_pass;
     if(spass <= 0){
         long long target = 128ll << 20;
@@ -332,32 +344,12 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
     s->stats.ms_total = s->stats.ms_extend = s->stats.ms_shade = s->stats.ms_connect = s->stats.ms_other = 0.0;
     s->stats.n_extend = s->stats.n_shade = s->stats.n_connect = s->stats.n_other = 0;
 
-    // split of the trace step: decided from the previous render of this scene (see hpt_scene::h_split)
-    const bool auto_budget = ((P.reserved >> 1) & 0x3F) == 0;
-    bool split_off = false;
-    if(auto_budget){
-        if(s->split_probe_pending && hipEventQuery(s->ev_split) == hipSuccess){
-            s->split_probe_pending = false;
-            uint64_t traced = 0, set_aside = 0;
-            for(int i = 0; i < s->split_probe_stride; ++i){
-                traced += (uint64_t) s->h_split[i] + s->h_split[(size_t) s->split_probe_stride + i];
-                set_aside += (uint64_t) s->h_split[(size_t) 2 * s->split_probe_stride + i] + s->h_split[(size_t) 3 * s->split_probe_stride + i];
-            }
-            if(traced > 0 && set_aside * 2 > traced) s->split_hold = kSplitHold;
-        }
-        if(s->split_hold > 0){ split_off = true; --s->split_hold; }
-    }
-    // node-step budget of the first trace launch (tuning bits 1..6: 0 = default, 0x3F = no split)
+    // node-step budget of the first trace launch (reserved bits 1-6: 0 = default, 63 = no split).  Unsplit: counting
+    // renders (their work counts are those of the plain single-launch traversal), the scan variants, and scenes whose
+    // four-wide tree is too deep for the resume launch's stack
     int budget = (P.reserved >> 1) & 0x3F;
     budget = budget == 0 ? kTraceBudget : (budget == 0x3F ? 0 : budget);
-    if(count || legacy) budget = 0;                     // work counts are those of the plain single-launch traversal
-    int tuning = P.reserved;
-    if(auto_budget && split_off){
-        budget = 0;                                     // all rays long: single launches with the long-ray tuning
-        if(((tuning >> 16) & 0xFF) == 0) tuning |= (int) (kLongChunk / 256u) << 16;
-        if(((tuning >> 8) & 0xFF) == 0) tuning |= kLongRefillMin << 8;
-        if(((tuning >> 24) & 0x7F) == 0) tuning |= kLongNodeMin << 24;
-    }
+    if(count || brute || !resume_walk_fits(s->sd)) budget = 0;
     s->last_budget = budget;
     const int roulette = (flags & HPT_FLAG_RUSSIAN_ROULETTE) ? 1 : 0;
 
@@ -377,7 +369,7 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
         Pass &q = pipe[k];
         q.pb = w.pb; q.sb = w.sb; q.queue[0] = w.queue[0]; q.queue[1] = w.queue[1]; q.squeue = w.squeue;
         q.lqueue[0] = w.lqueue[0]; q.lqueue[1] = w.lqueue[1];
-        q.deep_stack = ((flags >> 18) & 1) ? nullptr : w.deep_stack;      // flags bits 16-31: development switches (bit 18: whole stack in LDS; bit 19: two levels in LDS; bit 20: binary resume launch; bits 21-28: its tuning)
+        q.deep_stack = w.deep_stack;
         q.counters = w.counters; q.h_count = w.h_count; q.st = k == 0 ? stream : s->px_stream[k];
     }
     for(Pass &q : pipe){
@@ -391,7 +383,7 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
     // Iteration 0 needs no generate launch: its trace and shade kernels recompute the camera ray of a slot from the slot
     // number (PRIMARY variants; -3 % per render: the launch and the 72 B per path it writes and iteration 0 reads back).
     // The counting and the scan variants keep the stored form.
-    const bool in_flight_primaries = !count && !legacy && !((flags >> 17) & 1);      // flags bits 16-31: development switches
+    const bool in_flight_primaries = !count && !brute;
     auto begin_pass = [&](Pass &q, int done) -> int {
         q.sthis = std::min(spass, spp - done);
         q.slots = (uint32_t) tl.n_local * (uint32_t) q.sthis;
@@ -414,7 +406,7 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
         const uint32_t *eq = it == 0 ? nullptr : q.queue[q.cur];
         const PrimaryGen *primary = (it == 0 && in_flight_primaries) ? &q.primary : nullptr;
         const uint32_t cap = it >= eye_depth ? blind_groups : 0u;
-        if(legacy){
+        if(brute){
             LaunchTimer t(s, q.st, timek, 0);
             launch_extend(q.st, s->sd, q.pb, eq, &q.qcnt[it], q.slots, kflags, wc);
         } else {
@@ -422,17 +414,17 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
             TraceSplit split{ q.lqueue[0], &q.lecnt[it], q.lqueue[1], &q.lscnt[it], budget };
             { LaunchTimer t(s, q.st, timek, 0);
               launch_trace(q.st, s->sd, q.pb, q.sb, eq, &q.qcnt[it], q.slots, q.squeue,
-                           q.pending_shadow >= 0 ? &q.scnt[q.pending_shadow] : nullptr, q.slots, s->stack_levels, kflags, tuning, wc, &split, primary, cap); }
+                           q.pending_shadow >= 0 ? &q.scnt[q.pending_shadow] : nullptr, q.slots, s->stack_levels, count, wc, &split, primary, cap); }
             if(split.budget > 0){
                 LaunchTimer t(s, q.st, timek, 4);
-                launch_trace_resume(q.st, s->sd, q.pb, q.sb, true, q.pending_shadow >= 0, q.slots, s->stack_levels, wc, split, primary, cap, q.deep_stack, ((flags >> 19) & 1) != 0, ((flags >> 20) & 1) == 0, (flags >> 21) & 0xFF);
+                launch_trace_resume(q.st, s->sd, q.pb, q.sb, true, q.pending_shadow >= 0, q.slots, wc, split, primary, cap, q.deep_stack);
             }
             q.pending_shadow = -1;
         }
         { LaunchTimer t(s, q.st, timek, 1);
           launch_shade(q.st, s->sd, q.pb, eq, &q.qcnt[it], q.slots, q.queue[q.cur ^ 1],
                        &q.qcnt[it + 1], q.sb, q.squeue, &q.scnt[it], eye_depth, P.max_delta, roulette, wc, primary, cap); }
-        if(legacy){
+        if(brute){
             LaunchTimer t(s, q.st, timek, 2);
             launch_connect(q.st, s->sd, q.pb, q.sb, q.squeue, &q.scnt[it], q.slots, kflags, wc);
         } else q.pending_shadow = it;
@@ -467,10 +459,10 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
             TraceSplit split{ q.lqueue[0], &q.lecnt[max_iters], q.lqueue[1], &q.lscnt[max_iters], budget };
             { LaunchTimer t(s, q.st, timek, 2);
               launch_trace(q.st, s->sd, q.pb, q.sb, nullptr, nullptr, 0, q.squeue, &q.scnt[q.pending_shadow], q.slots,
-                           s->stack_levels, kflags, tuning, wc, &split, nullptr, blind_groups); }
+                           s->stack_levels, count, wc, &split, nullptr, blind_groups); }
             if(split.budget > 0){
                 LaunchTimer t(s, q.st, timek, 4);
-                launch_trace_resume(q.st, s->sd, q.pb, q.sb, false, true, q.slots, s->stack_levels, wc, split, nullptr, blind_groups, q.deep_stack, ((flags >> 19) & 1) != 0, ((flags >> 20) & 1) == 0, (flags >> 21) & 0xFF);
+                launch_trace_resume(q.st, s->sd, q.pb, q.sb, false, true, q.slots, wc, split, nullptr, blind_groups, q.deep_stack);
             }
         }
         return HPT_OK;
@@ -504,19 +496,6 @@ int render_local(hpt_scene *s, const void *camera, int W, int H, int eye_depth, 
     { LaunchTimer t(s, stream, timek, 3);
       launch_finalize(stream, tl, s->accum, d_local, divisor); }
     HIP_TRY(hipEventRecord(s->ev_stop, stream));
-    if(auto_budget && s->last_budget > 0 && !s->split_probe_pending){
-        int words = 4 * (max_iters + 2);
-        if(words > s->h_split_words){
-            if(s->h_split) hipHostFree(s->h_split);
-            s->h_split = nullptr; s->h_split_words = 0;
-            HIP_TRY(hipHostMalloc((void **) &s->h_split, (size_t) words * sizeof(uint32_t)));
-            s->h_split_words = words;
-        }
-        if(!s->ev_split) HIP_TRY(hipEventCreateWithFlags(&s->ev_split, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(s->h_split, s->last_counters, (size_t) words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(s->ev_split, stream));
-        s->split_probe_pending = true; s->split_probe_stride = max_iters + 2;
-    }
     HIP_TRY(hipGetLastError());
     s->ev_valid = true;
     s->stats_pending = true;
@@ -625,6 +604,7 @@ int render_bdpt_local(hpt_scene *s, const void *camera, int W, int H, int eye_de
     if(int rcd = on_scene_device(s)) return rcd;
     hpt_params P; memset(&P, 0, sizeof P);
     if(params) P = *params;
+    if(int rcp = check_params(P)) return rcp;
     if(P.max_delta <= 0) P.max_delta = 64;            // the CPU renderer has no cap (cpu_bdpt.cpp:458)
     if(P.max_delta > 250) P.max_delta = 250;
     Tiling tl;
@@ -910,8 +890,6 @@ void hpt_scene_destroy(hpt_scene *s){
         if(s->px_done[k]) hipEventDestroy(s->px_done[k]);
         if(s->px_stream[k]) hipStreamDestroy(s->px_stream[k]);
     }
-    if(s->h_split) hipHostFree(s->h_split);
-    if(s->ev_split) hipEventDestroy(s->ev_split);
     hipFree(s->d_local_own); hipFree(s->d_image_own);
     hipFree(s->d_nodes); hipFree(s->d_qnodes); hipFree(s->d_wnodes); hipFree(s->d_tris); hipFree(s->d_rounds); hipFree(s->d_mats); hipFree(s->d_lights);
     hipFree(s->d_tri_frames);

@@ -9,7 +9,7 @@ namespace hpt {
 struct SceneDev {
     const float4 *nodes;        // BvhNode as 4 x float4
     const uint4 *qnodes;        // QBvhNode as 2 x uint4 (k_trace)
-    const uint4 *wnodes;        // WideNode as 4 x uint4 (development: four-wide resume launch)
+    const uint4 *wnodes;        // WideNode as 4 x uint4 (the resume launch's tree)
     int wide_depth;
     float qorigin[3], qscale[3];
     const float4 *tris;         // DevTriangle as 3 x float4, leaf order
@@ -64,17 +64,14 @@ constexpr uint32_t kHitMiss = 0xFFFFFFFFu;
 constexpr uint32_t kHitRoundFlag = 0x80000000u;   // | index into rounds; else triangle slot
 
 constexpr int kBlock = 256;
-// k_trace tuning for launches whose rays are all long (the resume launch of a split step; every launch of a
-// scene whose split is held off): rays per workgroup, idle lanes that trigger a refill, early-leaf-break threshold
+// rays per workgroup of the resume launch of a split step (every ray in it is a long one)
 constexpr uint32_t kLongChunk = 4096;       // with two passes in flight: 2048 -> 4096 = -3.0 % / -2.1 % on 100 k / 20 k random triangles, -0.5 % on the sphere scenes
                                             // (one pass in flight: +2 % on random triangles: a launch's tail is then nobody's to fill)
-constexpr int kLongRefillMin = 16;
-constexpr int kLongNodeMin = 8;
-constexpr int kResumeLdsLevels = 12; // stack levels of the resume launch kept in LDS when a deep-stack buffer is given (deeper: global memory)
+constexpr int kResumeLdsLevels = 12; // stack levels of a resume-launch lane kept in LDS (deeper: the deep-stack buffer in global memory)
 constexpr uint32_t kResumeMaxGroups = 8192;   // grid cap of the resume launch
 constexpr int kDeepLevels = 48;      // global-memory stack levels per lane of the resume launch (the four-wide walk stacks up to three children per step)
-constexpr int kWideRefillMin = 24;   // the same two thresholds for the four-wide resume launch (A/B grid 16/24/32 x 12/16/24 on configs 3 and 5)
-constexpr int kWideNodeMin = 16;
+constexpr int kWideRefillMin = 24;   // idle lanes that trigger a refill in the resume launch, and its early-leaf-break threshold
+constexpr int kWideNodeMin = 16;     // (A/B grid 16/24/32 x 12/16/24 on configs 3 and 5)
 #ifndef HPT_TRACE_BUDGET             // development A/B: `make variant EXTRA="-DHPT_TRACE_BUDGET=7 -DHPT_TOP_LEVELS=7"`
 #define HPT_TRACE_BUDGET 6
 #endif
@@ -102,12 +99,14 @@ void launch_connect(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb,
 struct TraceSplit { uint32_t *equeue, *ecount, *squeue, *scount; int budget; };
 void launch_trace(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uint32_t *equeue,
                   const uint32_t *ecount, uint32_t max_extend, const uint32_t *squeue, const uint32_t *scount,
-                  uint32_t max_shadow, int stack_levels, int flags, int tuning, WorkCounters *wc,
+                  uint32_t max_shadow, int stack_levels, bool count, WorkCounters *wc,
                   const TraceSplit *split = nullptr, const PrimaryGen *primary = nullptr, uint32_t max_groups = 0);
+// the resume launch walks the four-wide tree with kResumeLdsLevels stack levels in LDS and up to kDeepLevels more in
+// deep_stack: a scene may only be split if resume_walk_fits() it
 void launch_trace_resume(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, bool extend, bool shadow,
-                         uint32_t max_items, int stack_levels, WorkCounters *wc, const TraceSplit &split,
-                         const PrimaryGen *primary = nullptr, uint32_t max_groups = 0, uint32_t *deep_stack = nullptr,
-                         bool tiny_lds_share = false, bool wide = false, int dev_tuning = 0);
+                         uint32_t max_items, WorkCounters *wc, const TraceSplit &split, const PrimaryGen *primary,
+                         uint32_t max_groups, uint32_t *deep_stack);
+inline bool resume_walk_fits(const SceneDev &sc){ return 3 * sc.wide_depth + 2 <= kResumeLdsLevels + kDeepLevels; }
 // words of the buffer launch_trace_resume's deep_stack needs (one column per lane of its largest grid)
 size_t resume_deep_stack_words();
 // fills frames[4 * num_tris] from tris (once per scene)

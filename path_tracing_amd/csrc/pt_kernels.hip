@@ -849,11 +849,11 @@ constexpr int kNodeMin = 4;           // fewer lanes than this still walking nod
                                       // (A/B: off 42.1 ms, 2: 39.9, 4: 39.4, 8: 40.2, 16: 41.3, 32: 43.2)
 constexpr uint32_t kTraceShortQueue = 1u << 20;   // below this many rays a workgroup takes 256 instead of kTraceChunk
 
-// LDSK > 0: only the first LDSK stack levels of a lane live in LDS, deeper ones in its column of `deep` (global memory,
-// one column per lane of the grid, `deep_stride` words apart): the resume launch walks the long rays with the whole tree
-// depth as its stack bound (22 KB of LDS per workgroup at depth 21, 27 KB at 26: five or six workgroups per CU), while a
-// ray rarely holds more than a dozen pending subtrees
-template <bool ANY, bool COUNT, bool RESUME, bool TOP, bool PRIMARY, int LDSK, bool WIDE>
+// The first launch (!RESUME) walks the binary tree with the whole stack in LDS.  The resume launch (RESUME) walks the
+// four-wide tree; only the first kResumeLdsLevels stack levels of a lane live in LDS, deeper ones in its column of `deep`
+// (global memory, one column per lane of the grid, `deep_stride` words apart): the whole stack in LDS would take 22 KB per
+// workgroup at depth 21, 27 KB at 26 (five or six workgroups per CU), while a ray rarely holds more than a dozen pending subtrees
+template <bool ANY, bool COUNT, bool RESUME, bool TOP, bool PRIMARY>
 HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uint32_t *queue,
                          uint32_t end, uint32_t *stk, uint32_t *s_next, int refill_min, int node_min, WorkCounters *wc,
                          uint32_t budget, uint32_t *s_long, uint32_t *s_nlong, const uint4 *top, const PrimaryGen &pg,
@@ -989,8 +989,8 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                 if((int) lane == __ffsll((long long) __ballot(true)) - 1) n_wave_steps += 64;   // one wave trip
             }
             if(!RESUME) steps += 1u;
-            if(WIDE){
-                // four-wide step (development A/B): four child boxes from one 64-B node; the nearest hit child is entered, the
+            if(RESUME){
+                // four-wide step: four child boxes from one 64-B node; the nearest hit child is entered, the
                 // other hit children are stacked in slot order (ordering them too buys 0.3 % fewer steps on the benchmark
                 // meshes: scripts/micro/bvh4_steps.cpp).  t = q * i + o is monotone in q, so the near plane of an axis is the
                 // lower one when i >= 0 and the upper one otherwise: one bit-select per word picks it for two children.
@@ -1023,15 +1023,15 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                 const int e0 = (k0 + c1 < c2) ? 1 : 0, e1 = (k1 + c1 < c2) ? 1 : 0, e2 = (k2 + c1 < c2) ? 1 : 0, e3 = (k3 + c1 < c2) ? 1 : 0;
                 uint32_t top;
                 int p = sp;
-                if(sp + 3 < LDSK){
+                if(sp + 3 < kResumeLdsLevels){
                     // every level this step can touch is in LDS; a child that is not stacked is written to the spare level
                     top = stk[(sp > 0 ? sp - 1 : 0) * kBlock];
-                    stk[(e0 ? p : LDSK) * kBlock] = qc.x; p += e0;
-                    stk[(e1 ? p : LDSK) * kBlock] = qc.y; p += e1;
-                    stk[(e2 ? p : LDSK) * kBlock] = qc.z; p += e2;
-                    stk[(e3 ? p : LDSK) * kBlock] = qc.w; p += e3;
+                    stk[(e0 ? p : kResumeLdsLevels) * kBlock] = qc.x; p += e0;
+                    stk[(e1 ? p : kResumeLdsLevels) * kBlock] = qc.y; p += e1;
+                    stk[(e2 ? p : kResumeLdsLevels) * kBlock] = qc.z; p += e2;
+                    stk[(e3 ? p : kResumeLdsLevels) * kBlock] = qc.w; p += e3;
                 } else {
-                    auto level = [&](int l) -> uint32_t * { return l < LDSK ? stk + l * kBlock : deep + (size_t) (l - LDSK) * deep_stride; };
+                    auto level = [&](int l) -> uint32_t * { return l < kResumeLdsLevels ? stk + l * kBlock : deep + (size_t) (l - kResumeLdsLevels) * deep_stride; };
                     top = *level(sp > 0 ? sp - 1 : 0);
                     if(e0){ *level(p) = qc.x; ++p; }
                     if(e1){ *level(p) = qc.y; ++p; }
@@ -1064,14 +1064,8 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
             // it, then pick by selects.  The stack has one spare level for the unconditional store.
             bool any = hl || hr, both = hl && hr;
             bool left_first = hl && (!hr || ln <= rn);
-            uint32_t top;
-            if(LDSK > 0 && sp >= LDSK){                  // rare: this lane's stack has grown past its LDS share
-                top = sp > LDSK ? deep[(size_t) (sp - 1 - LDSK) * deep_stride] : stk[(LDSK - 1) * kBlock];
-                deep[(size_t) (sp - LDSK) * deep_stride] = left_first ? rc : lc;
-            } else {
-                top = stk[(sp > 0 ? sp - 1 : 0) * kBlock];
-                stk[sp * kBlock] = left_first ? rc : lc;
-            }
+            uint32_t top = stk[(sp > 0 ? sp - 1 : 0) * kBlock];
+            stk[sp * kBlock] = left_first ? rc : lc;
             uint32_t near = left_first ? lc : rc;
             cur = any ? near : (sp > 0 ? top : kDoneCode);
             sp = any ? sp + (both ? 1 : 0) : (sp > 0 ? sp - 1 : 0);
@@ -1106,7 +1100,7 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                 if(ANY && blocked) finished = true;                   // occluded: no contribution
                 else if(sp > 0){
                     --sp;
-                    cur = (LDSK > 0 && sp >= LDSK) ? deep[(size_t) (sp - LDSK) * deep_stride] : stk[sp * kBlock];
+                    cur = (RESUME && sp >= kResumeLdsLevels) ? deep[(size_t) (sp - kResumeLdsLevels) * deep_stride] : stk[sp * kBlock];
                 }
                 else finished = true;
             }
@@ -1149,7 +1143,7 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
 // is the same (closest hit with the ordinal tie-break, or the occlusion boolean, of the same ray).
 struct LongQueues { uint32_t *equeue, *ecount, *squeue, *scount; uint32_t budget; };
 
-template <bool COUNT, bool RESUME, bool TOP, bool PRIMARY, int LDSK, bool WIDE>
+template <bool COUNT, bool RESUME, bool TOP, bool PRIMARY>
 __global__ __launch_bounds__(kBlock) HPT_TRACE_ATTR
 void k_trace(SceneDev sc, PathBuf pb, ShadowBuf sb, const uint32_t *equeue, const uint32_t *ecount_ptr,
              const uint32_t *squeue, const uint32_t *scount_ptr, uint32_t chunk_rays, int refill_min, int node_min,
@@ -1177,12 +1171,12 @@ void k_trace(SceneDev sc, PathBuf pb, ShadowBuf sb, const uint32_t *equeue, cons
         uint32_t end = begin + csize < total ? begin + csize : total;
         if(threadIdx.x == 0){ s_next = begin; s_nlong = 0u; }
         __syncthreads();
-        uint32_t *deep_lane = LDSK > 0 ? deep + (size_t) blockIdx.x * kBlock + threadIdx.x : nullptr;
+        uint32_t *deep_lane = RESUME ? deep + (size_t) blockIdx.x * kBlock + threadIdx.x : nullptr;
         const uint32_t deep_stride = gridDim.x * kBlock;
-        if(shadow) trace_chunk<true, COUNT, RESUME, TOP, false, LDSK, WIDE>(sc, pb, sb, squeue, end, s_dyn_stack + threadIdx.x, &s_next, refill_min, node_min, wc,
-                                                                      lq.budget, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
-        else trace_chunk<false, COUNT, RESUME, TOP, PRIMARY, LDSK, WIDE>(sc, pb, sb, equeue, end, s_dyn_stack + threadIdx.x, &s_next, refill_min, node_min, wc,
-                                                                   lq.budget, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
+        if(shadow) trace_chunk<true, COUNT, RESUME, TOP, false>(sc, pb, sb, squeue, end, s_dyn_stack + threadIdx.x, &s_next, refill_min, node_min, wc,
+                                                                lq.budget, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
+        else trace_chunk<false, COUNT, RESUME, TOP, PRIMARY>(sc, pb, sb, equeue, end, s_dyn_stack + threadIdx.x, &s_next, refill_min, node_min, wc,
+                                                             lq.budget, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
         __syncthreads();
         if(!RESUME && lq.budget != 0u){
             uint32_t n = s_nlong;
@@ -1335,12 +1329,9 @@ void launch_connect(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb,
 
 void launch_trace(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uint32_t *equeue,
                   const uint32_t *ecount, uint32_t max_extend, const uint32_t *squeue, const uint32_t *scount,
-                  uint32_t max_shadow, int stack_levels, int flags, int tuning, WorkCounters *wc, const TraceSplit *split,
+                  uint32_t max_shadow, int stack_levels, bool count, WorkCounters *wc, const TraceSplit *split,
                   const PrimaryGen *primary, uint32_t max_groups){
-    uint32_t chunk = ((tuning >> 16) & 0xFF) ? (uint32_t) ((tuning >> 16) & 0xFF) * 256u : (uint32_t) kTraceChunk;
-    int refill_min = ((tuning >> 8) & 0xFF) ? ((tuning >> 8) & 0xFF) : kRefillMin;
-    int node_min = ((tuning >> 24) & 0x7F) ? ((tuning >> 24) & 0x7F) : kNodeMin;
-    if(node_min == 0x7F) node_min = 0;                 // tuning: switch the early leaf break off
+    const uint32_t chunk = (uint32_t) kTraceChunk;
     // worst-case grid for either chunking regime of k_trace (long queues: `chunk` rays per workgroup,
     // queues shorter than kTraceShortQueue: kBlock rays per workgroup)
     auto groups = [&](uint32_t items){
@@ -1355,20 +1346,19 @@ void launch_trace(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, c
     if(stack_levels < 1) stack_levels = 1;
     if(stack_levels > kStackDepth) stack_levels = kStackDepth;
     int stack_words = (stack_levels + 1) * kBlock;                            // + the spare level of the branch-free step
-    const bool count = (flags & 2) != 0;
     LongQueues lq{};
     if(split && split->budget > 0 && !count){
         lq.equeue = split->equeue; lq.ecount = split->ecount; lq.squeue = split->squeue; lq.scount = split->scount;
         lq.budget = (uint32_t) split->budget;
         // a ray of this launch is set aside after `budget` node steps, so its stack never grows past that many entries
-        if(stack_levels > split->budget && !(flags & 4)) stack_words = (split->budget + 1) * kBlock;      // flags bit 2: development A/B
+        if(stack_levels > split->budget) stack_words = (split->budget + 1) * kBlock;
     }
     size_t lds = (size_t) stack_words * sizeof(uint32_t) + (lq.budget ? (size_t) chunk * sizeof(uint32_t) : 0);
-    const bool top = lq.budget != 0u && lq.budget <= (uint32_t) kTopLevels && !(tuning & 0x80);       // tuning bit 7: node fetches from global memory (A/B)
+    const bool top = lq.budget != 0u && lq.budget <= (uint32_t) kTopLevels;
     PrimaryGen none{};
     const PrimaryGen &pg = primary ? *primary : none;
-#define HPT_LAUNCH_TRACE(C, T, P) hipLaunchKernelGGL((k_trace<C, false, T, P, 0, false>), dim3(g), dim3(kBlock), lds, s, sc, pb, sb, equeue, ecount, squeue, \
-                                                     scount, chunk, refill_min, node_min, stack_words, lq, wc, pg, (uint32_t *) nullptr)
+#define HPT_LAUNCH_TRACE(C, T, P) hipLaunchKernelGGL((k_trace<C, false, T, P>), dim3(g), dim3(kBlock), lds, s, sc, pb, sb, equeue, ecount, squeue, \
+                                                     scount, chunk, kRefillMin, kNodeMin, stack_words, lq, wc, pg, (uint32_t *) nullptr)
     if(count) HPT_LAUNCH_TRACE(true, false, false);
     else if(top && primary) HPT_LAUNCH_TRACE(false, true, true);
     else if(top) HPT_LAUNCH_TRACE(false, true, false);
@@ -1378,60 +1368,29 @@ void launch_trace(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, c
 }
 
 // second launch of a split trace step: the rays launch_trace set aside.  Their number is only known on
-// the device, so a fixed grid walks the chunks.
+// the device, so a fixed grid walks the chunks.  The long rays walk the four-wide twin of the tree (up to
+// three children stacked per step), kResumeLdsLevels stack levels per lane in LDS and the deeper ones in
+// deep_stack (resume_deep_stack_words()); render_local only splits scenes whose tree fits (resume_walk_fits).
 void launch_trace_resume(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, bool extend, bool shadow,
-                         uint32_t max_items, int stack_levels, WorkCounters *wc, const TraceSplit &split, const PrimaryGen *primary,
-                         uint32_t max_groups, uint32_t *deep_stack, bool tiny_lds_share, bool wide, int dev_tuning){
+                         uint32_t max_items, WorkCounters *wc, const TraceSplit &split, const PrimaryGen *primary,
+                         uint32_t max_groups, uint32_t *deep_stack){
     if(!extend && !shadow) return;
-    if(stack_levels < 1) stack_levels = 1;
-    if(stack_levels > kStackDepth) stack_levels = kStackDepth;
-    // deep_stack: the lanes' stack levels past kResumeLdsLevels live in global memory (resume_deep_stack_words()); a tree
-    // that is no deeper keeps the plain LDS stack
-    // (tiny_lds_share: two levels in LDS, so that the tests walk the global-memory levels on every ray)
-    const int lds_levels = tiny_lds_share ? 2 : kResumeLdsLevels;
-    const bool spill = deep_stack != nullptr && stack_levels > lds_levels;
-    int stack_words = ((spill ? lds_levels : stack_levels) + 1) * kBlock;
-    // every ray of this launch is a long one: lanes refill sooner, a workgroup takes more rays (a lane
-    // gets ~8 rays, which evens out their lengths) and the leaf phase waits for fewer stragglers
-    uint32_t chunk2 = kLongChunk; int refill2 = kLongRefillMin, node_min2 = kLongNodeMin;
-    {   // development sweeps (hpt_params.flags bits 21-28): refill threshold, early-leaf-break threshold, chunk
-        static const int refill_tab[8] = { 0, 8, 16, 24, 32, 40, 48, 56 }, node_tab[8] = { 0, 1, 2, 4, 12, 16, 24, 32 };
-        static const uint32_t chunk_tab[4] = { 0u, 1024u, 2048u, 512u };
-        if(dev_tuning & 7) refill2 = refill_tab[dev_tuning & 7];
-        if((dev_tuning >> 3) & 7) node_min2 = node_tab[(dev_tuning >> 3) & 7];
-        if((dev_tuning >> 6) & 3) chunk2 = chunk_tab[(dev_tuning >> 6) & 3];
-    }
+    const int stack_words = (kResumeLdsLevels + 1) * kBlock;
+    const size_t lds = (size_t) stack_words * sizeof(uint32_t);
     uint32_t per = (max_items + kBlock - 1) / kBlock;
     uint64_t g = (uint64_t) per * ((extend ? 1u : 0u) + (shadow ? 1u : 0u));
     uint32_t g2 = g < kResumeMaxGroups ? (uint32_t) (g < 1u ? 1u : g) : kResumeMaxGroups;
     if(max_groups != 0u && g2 > max_groups) g2 = max_groups;          // blind tail iterations (HPT_FLAG_NO_HOST_WAIT)
     LongQueues none{};
     PrimaryGen no_primary{};
-    const size_t lds = (size_t) stack_words * sizeof(uint32_t);
     const uint32_t *eq = extend ? split.equeue : nullptr, *ec = extend ? split.ecount : nullptr;
     const uint32_t *sq = shadow ? split.squeue : nullptr, *scn = shadow ? split.scount : nullptr;
-#define HPT_LAUNCH_RESUME(P, K, W, PG) hipLaunchKernelGGL((k_trace<false, true, false, P, K, W>), dim3(g2), dim3(kBlock), lds, s, sc, pb, sb, eq, ec, sq, scn, \
-                                                          chunk2, refill2, node_min2, stack_words, none, wc, PG, deep_stack)
-    // the long rays walk the four-wide twin of the tree (up to three children stacked per step: needs the deep-stack buffer);
-    // `wide` false = the binary walk (development A/B, and scenes whose wide tree would outgrow the stack)
-    if(wide && deep_stack && sc.wnodes && 3 * sc.wide_depth + 2 <= lds_levels + kDeepLevels){
-        stack_words = (lds_levels + 1) * kBlock;
-        const size_t lds = (size_t) stack_words * sizeof(uint32_t);
-        if(!(dev_tuning & 7)) refill2 = kWideRefillMin;
-        if(!((dev_tuning >> 3) & 7)) node_min2 = kWideNodeMin;
-        if(primary && extend){ if(tiny_lds_share) HPT_LAUNCH_RESUME(true, 2, true, *primary); else HPT_LAUNCH_RESUME(true, kResumeLdsLevels, true, *primary); }
-        else { if(tiny_lds_share) HPT_LAUNCH_RESUME(false, 2, true, no_primary); else HPT_LAUNCH_RESUME(false, kResumeLdsLevels, true, no_primary); }
-        return;
-    }
-    if(primary && extend){
-        if(spill && tiny_lds_share) HPT_LAUNCH_RESUME(true, 2, false, *primary);
-        else if(spill) HPT_LAUNCH_RESUME(true, kResumeLdsLevels, false, *primary);
-        else HPT_LAUNCH_RESUME(true, 0, false, *primary);
-    } else {
-        if(spill && tiny_lds_share) HPT_LAUNCH_RESUME(false, 2, false, no_primary);
-        else if(spill) HPT_LAUNCH_RESUME(false, kResumeLdsLevels, false, no_primary);
-        else HPT_LAUNCH_RESUME(false, 0, false, no_primary);
-    }
+    // every ray of this launch is a long one: a workgroup takes more rays (a lane gets ~8 rays, which evens
+    // out their lengths), lanes refill sooner and the leaf phase waits for fewer stragglers
+#define HPT_LAUNCH_RESUME(P, PG) hipLaunchKernelGGL((k_trace<false, true, false, P>), dim3(g2), dim3(kBlock), lds, s, sc, pb, sb, eq, ec, sq, scn, \
+                                                    kLongChunk, kWideRefillMin, kWideNodeMin, stack_words, none, wc, PG, deep_stack)
+    if(primary && extend) HPT_LAUNCH_RESUME(true, *primary);
+    else HPT_LAUNCH_RESUME(false, no_primary);
 #undef HPT_LAUNCH_RESUME
 }
 

@@ -1,4 +1,4 @@
-"""A/B of several builds of libhpt.so and/or tuning variants on one box: every (library, scene) cell is measured by
+"""A/B of several builds of libhpt.so and/or trace budgets (AB_VARIANTS) on one box: every (library, scene) cell is measured by
 scripts/ab_tuning.py in its own process, AB_ROUNDS rounds, the order of the libraries rotated from round to round (the
 later process of a group runs a little faster whatever it loads).  Prints the median of each cell's medians.
 usage: python scripts/ab_matrix.py <lib name or 'default'> [...]     env: AB_* of ab_tuning.py, ABM_ROUNDS (default 3)

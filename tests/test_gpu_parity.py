@@ -394,32 +394,49 @@ def hpt_default_budget():
     return 6          # kTraceBudget, csrc/pt_kernels.h
 
 
-def test_resume_launch_layouts(hpt, sio, oracle_mod):
+def test_resume_launch_walks_deep_trees_bit_exact(hpt, sio, oracle_mod):
     """The resume launch walks the four-wide twin of the tree, 12 stack levels per lane in LDS and deeper ones in global
-    memory.  Development switches force the other forms -- two levels in LDS (flags bit 19: every long ray then uses
-    the global-memory levels), the binary walk (bit 20) with 12 levels, the whole stack (bit 18) or two levels in LDS --
-    on a mesh of 30 000 triangles and on the incoherent random-triangle cloud, with the default budget and with a
-    budget of 1 (practically every ray resumes); every form is the oracle's image bit for bit."""
-    W18, W19, W20 = 1 << 18, 1 << 19, 1 << 20
+    memory.  On a mesh of 30 000 triangles and on the incoherent random-triangle cloud (binary trees deeper than the 12
+    LDS levels), with the default budget and with a budget of 1 (practically every ray resumes), the image is the
+    oracle's bit for bit."""
     for L, sp, tr in (sio.cornell_with_sphere(30000), sio.cornell_random_triangles(20000)):
         cam = sio.make_camera(sio.CORNELL_EYE, sio.CORNELL_LOOK, sio.CORNELL_UP, 50.0, 80, 64)
         bvh = hpt.export_bvh_host(L, sp, tr)
         assert bvh["bvh_depth"] > 12
         ref, _ = oracle_mod.pt_render(L, sp, tr, cam, 80, 64, 4, 3, seed=9, bvh=bvh)
         with hpt.Scene(L, sp, tr) as scene:
-            for dev in (0, W19, W20, W20 | W18, W20 | W19):
-                for budget in (6, 1):
-                    p = hpt.make_params(seed=9, flags=dev | hpt.FLAG_TIME_KERNELS)
-                    p.reserved = budget << 1
-                    img = scene.render_pt(cam, 80, 64, 4, 3, p)
-                    assert scene.stats()["n_resume"] > 0
-                    assert_parity(img, ref)
+            for budget in (6, 1):
+                p = hpt.make_params(seed=9, flags=hpt.FLAG_TIME_KERNELS)
+                p.reserved = budget << 1
+                img = scene.render_pt(cam, 80, 64, 4, 3, p)
+                assert scene.stats()["n_resume"] > 0
+                assert_parity(img, ref)
+
+
+def test_undocumented_param_bits_are_rejected(hpt, sio):
+    """hpt_params.flags may only hold HPT_FLAG_* bits and hpt_params.reserved only bits 1-6 (the trace budget).  Any
+    other bit is HPT_ERR_INVALID from both render entries (the wrapper raises), and the scene renders on unchanged."""
+    L, sp, tr = sio.cornell_with_sphere(2000)
+    cam = sio.make_camera(sio.CORNELL_EYE, sio.CORNELL_LOOK, sio.CORNELL_UP, 50.0, 32, 32)
+    with hpt.Scene(L, sp, tr) as scene:
+        pt = scene.render_pt(cam, 32, 32, 4, 2, hpt.make_params(seed=2))
+        bd = scene.render_bdpt(cam, 32, 32, 2, 2, 2, 2, hpt.make_params(seed=2))
+        for flags, reserved in ((1 << 7, 0), (1 << 16, 0), (1 << 17, 0), (1 << 20, 0), (1 << 29, 0),
+                                (0, 1), (0, 1 << 7), (0, 1 << 16), (0, 1 << 24)):
+            p = hpt.make_params(seed=2, flags=flags)
+            p.reserved = reserved
+            with pytest.raises(hpt.HptError, match="hpt error 1:"):
+                scene.render_pt(cam, 32, 32, 4, 2, p)
+            with pytest.raises(hpt.HptError, match="hpt error 1:"):
+                scene.render_bdpt(cam, 32, 32, 2, 2, 2, 2, p)
+        assert np.array_equal(scene.render_pt(cam, 32, 32, 4, 2, hpt.make_params(seed=2)), pt)
+        assert np.array_equal(scene.render_bdpt(cam, 32, 32, 2, 2, 2, 2, hpt.make_params(seed=2)), bd)
 
 
 def test_split_is_kept_for_scenes_whose_rays_are_all_long(hpt, sio, oracle_mod):
-    """The renderer reads back (asynchronously) how many rays the split set aside.  Round 2 dropped the split for the
-    next frames of a scene where that is most of them; with the four-wide resume launch the split is the faster form
-    there too, so it stays on -- frame after frame, same image, and the share is reported."""
+    """Round 2 dropped the split for the next frames of a scene where most rays are set aside; with the four-wide resume
+    launch the split is the faster form there too, so it stays on -- frame after frame, same image, and the share of
+    long rays is reported."""
     L, sp, tr = sio.cornell_random_triangles(4000)
     cam = sio.make_camera(sio.CORNELL_EYE, sio.CORNELL_LOOK, sio.CORNELL_UP, 50.0, 64, 64)
     ref, _ = oracle_mod.pt_render(L, sp, tr, cam, 64, 64, 4, 2, seed=5)
@@ -430,7 +447,7 @@ def test_split_is_kept_for_scenes_whose_rays_are_all_long(hpt, sio, oracle_mod):
         assert st["long_rays_last_pass"] * 2 > st["traced_rays_last_pass"]
         b = scene.render_pt(cam, 64, 64, 4, 2, hpt.make_params(seed=5))
         assert scene.stats()["split_budget"] == hpt_default_budget()
-        p = hpt.make_params(seed=5); p.reserved = 63 << 1               # 63 = no split (development)
+        p = hpt.make_params(seed=5); p.reserved = 63 << 1               # 63 = no split
         c = scene.render_pt(cam, 64, 64, 4, 2, p)
         assert scene.stats()["split_budget"] == 0
     assert_parity(a, ref); assert_parity(b, ref); assert_parity(c, ref)
