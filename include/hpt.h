@@ -205,6 +205,49 @@ int hpt_bdpt_render_wrapper(const void *lights, int num_lights, const void *sphe
 
 int hpt_get_stats(const hpt_scene *scene, hpt_stats *out);
 
+/* ---- photon mapping (the reference's PPM integrator) ----------------------------------------------
+ * Replaces ppm_render_wrapper (reference include/ppm_cu.cuh:8-15, src/ppm_cu.cu:328-400) and run_cuda_ppm
+ * (include/ppm_cu_helper.h).  One pass = an eye pass (a hit point at the first non-delta surface of every pixel,
+ * the direct term where a light ball is reached through delta bounces), nl * spl photons of light_depth
+ * non-delta bounces each, and for every hit point the sum of flux * f(wo, wi) * throughput over the photon
+ * deposits within `radius` (normals agreeing), divided by pi r^2 and clamped to 15.  The reference's float-atomic
+ * scatter is replaced by a gather in a fixed order ("PPM"), so an image is a function of the seed.
+ * `spp` passes are independent and averaged (HPT_FLAG_OUTPUT_SUM: summed).  eye_depth only has to be >= 1: the
+ * eye path ends at its first non-delta hit, delta bounces are free (capped at hpt_params.max_delta) as in the
+ * reference.  radius <= 0 -> 0.05 (the reference's PPM_RADIUS; the grid cell is the radius).  scene_min /
+ * scene_max NULL -> the scene's bounds as the reference's helper computes them (spheres +- r, triangle vertices,
+ * no light balls).  PPM renders on ONE device: params->world must be 0 or 1, and the multi-device fan-out
+ * (hpt_multi_*, hpt_wrapper_set_devices) stays PT/BDPT only.  Accepted flags: OUTPUT_SUM, TIME_KERNELS,
+ * COUNT_WORK; any other flag, spl < 0, or depths outside [1, 255] return HPT_ERR_INVALID; nl * spl *
+ * light_depth deposits that do not fit the device return HPT_ERR_NOMEM (nothing is batched). */
+int hpt_render_ppm(hpt_scene *scene, const void *camera, int W, int H, int eye_depth, int light_depth,
+                   int spp, int spl, float radius, const float *scene_min, const float *scene_max,
+                   const hpt_params *params, float *host_image);
+
+typedef struct hpt_ppm_stats {
+    uint64_t photons;         /* photons emitted (all passes of the last render) */
+    uint64_t photon_rays;     /* closest-hit rays of the photon paths */
+    uint64_t deposits;        /* live photon deposits */
+    uint64_t hit_points;      /* eye hit points */
+    uint64_t direct_pixels;   /* pixels whose eye path reached a light ball (direct term written) */
+    uint64_t candidates;      /* COUNT_WORK: (hit point, deposit) pairs in the 27 cells, exact cell match */
+    uint64_t accepted;        /* COUNT_WORK: of those, normals agree and distance < radius */
+    uint64_t cand_median, cand_max, acc_median, acc_max;   /* COUNT_WORK: per hit point, last pass */
+    uint64_t grid_buckets;    /* bucket table size (power of two) */
+    double ms_eye, ms_photon, ms_grid, ms_gather;          /* TIME_KERNELS: device time per phase, all passes */
+    double ms_total;          /* device time of the last render */
+} hpt_ppm_stats;
+int hpt_ppm_get_stats(const hpt_scene *scene, hpt_ppm_stats *out);
+
+/* One-shot, the reference's ppm_render_wrapper argument list plus seed (< 0: clock).  ONE pass whatever spp is
+ * (the reference never reads it); scene_min / scene_max are used as given; the scene is kept between calls like
+ * the other wrappers' (hpt_wrapper_cache_clear).  Always one device. */
+int hpt_ppm_render_wrapper(const void *lights, int num_lights, const void *spheres, int num_spheres,
+                           const void *triangles, int num_triangles,
+                           const float scene_min[3], const float scene_max[3],
+                           const void *camera, float *host_image, int W, int H,
+                           int light_depth, int light_sample, int eye_depth, int spp, int64_t seed);
+
 /* ---- multi-device fan-out inside the blocking call -----------------------------------------------
  * The reference's launch API is one blocking call per frame (run_cuda_pt -> pt_render_wrapper, reference
  * src/pt_cu_helper.cpp:66-77, src/pt_cu.cu:255-297, one device).  hpt_multi_* is the same call over the
@@ -220,7 +263,8 @@ int hpt_get_stats(const hpt_scene *scene, hpt_stats *out);
  *                    several ranks on one device, which an RCCL communicator refuses)
  * hpt_wrapper_set_devices(n) (or HPT_DEVICES=n in the environment, read once) makes the two one-shot
  * wrappers -- hence the reference's unmodified run_cuda_pt / run_cuda_bdpt -- render on n devices this way;
- * 0 returns to the environment's value, 1 to a single device. */
+ * 0 returns to the environment's value, 1 to a single device.  Photon mapping (hpt_render_ppm,
+ * hpt_ppm_render_wrapper) always renders on one device. */
 typedef struct hpt_multi hpt_multi;
 int hpt_multi_create(const void *lights, int num_lights, const void *spheres, int num_spheres,
                      const void *triangles, int num_triangles,

@@ -52,4 +52,17 @@ void bdpt_render_wrapper(
     const CudaCamera cuda_camera, float3 *cuda_image, int W, int H,
     int light_depth, int light_sample, int eye_depth, int spp, int spl /*sample per light*/);
 
+
+// Replaces:  void ppm_render_wrapper(...)   reference include/ppm_cu.cuh:8-15, defined src/ppm_cu.cu:328-400
+// One call renders ONE pass whatever spp is (the reference never reads it), with the scene_min / scene_max given
+// (grid origin, parallel-light emission) and radius 0.05; light directions are used as given (the reference's helper
+// normalises them).  Random streams as pt_render_wrapper's: the clock unless HPT_SEED is set.  One device.
+void ppm_render_wrapper(
+    const CudaLight *cuda_lights, int num_lights,
+    const CudaSphere *cuda_spheres, int num_spheres,
+    const CudaTriangle *cuda_triangles, int num_triangles,
+    float3 scene_min, float3 scene_max,
+    const CudaCamera cuda_camera, float3 *cuda_image, int W, int H,
+    int light_depth, int light_sample, int eye_depth, int spp);
+
 #endif

@@ -63,6 +63,16 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PpmStats(C.Structure):
+    """hpt_ppm_stats (include/hpt.h): counts and phase times of the last photon-mapping render."""
+    _fields_ = [(n, C.c_uint64) for n in ("photons", "photon_rays", "deposits", "hit_points", "direct_pixels", "candidates", "accepted",
+                                          "cand_median", "cand_max", "acc_median", "acc_max", "grid_buckets")] + \
+               [(n, C.c_double) for n in ("ms_eye", "ms_photon", "ms_grid", "ms_gather", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("num_nodes", C.c_int32), ("num_tris", C.c_int32), ("bvh_depth", C.c_int32), ("num_rounds", C.c_int32),
                 ("qorigin", C.c_float * 3), ("qscale", C.c_float * 3)]
@@ -113,7 +123,8 @@ def load_library() -> C.CDLL:
                      "hpt_pt_render_wrapper", "hpt_get_stats", "hpt_trace_closest", "hpt_trace_visibility",
                      "hpt_device_count", "hpt_multi_create", "hpt_multi_num_devices", "hpt_multi_set_groups",
                      "hpt_multi_render_pt", "hpt_multi_render_bdpt", "hpt_multi_get_timing", "hpt_wrapper_set_devices",
-                     "hpt_probe_functions", "hpt_tonemap", "hpt_tonemap_host", "hpt_bvh_export_host", "hpt_scene_export_bvh"):
+                     "hpt_probe_functions", "hpt_tonemap", "hpt_tonemap_host", "hpt_bvh_export_host", "hpt_scene_export_bvh",
+                     "hpt_render_ppm", "hpt_ppm_get_stats", "hpt_ppm_render_wrapper"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         lib.hpt_scene_destroy.restype = None
@@ -218,6 +229,25 @@ class Scene:
         cam = np.ascontiguousarray(camera, CAMERA)
         _check(self._lib.hpt_render_bdpt_device(self._h, _vp(cam.reshape(1)), W, H, eye_depth, light_depth, spp, spl, C.byref(params),
                                                 C.c_void_p(d_local_ptr), C.c_void_p(stream)))
+
+    # -- photon mapping (run_cuda_ppm / ppm_render_wrapper, reference src/ppm_cu.cu) ----------------------------------
+    def render_ppm(self, camera, W, H, eye_depth=4, light_depth=4, spp=1, spl=8, radius=0.05, params: Params | None = None,
+                   scene_min=None, scene_max=None) -> np.ndarray:
+        """spp independent passes of the reference's photon-mapping estimator, averaged (FLAG_OUTPUT_SUM: summed);
+        nl * spl photons per pass.  scene_min / scene_max None: the scene's own bounds.  float32 [H, W, 3]."""
+        params = params or make_params()
+        cam = np.ascontiguousarray(camera, CAMERA)
+        img = np.empty((H, W, 3), np.float32)
+        mn = (C.c_float * 3)(*scene_min) if scene_min is not None else None
+        mx = (C.c_float * 3)(*scene_max) if scene_max is not None else None
+        _check(self._lib.hpt_render_ppm(self._h, _vp(cam.reshape(1)), W, H, eye_depth, light_depth, spp, spl, C.c_float(radius),
+                                        mn, mx, C.byref(params), _vp(img)))
+        return img
+
+    def ppm_stats(self) -> dict:
+        st = PpmStats()
+        _check(self._lib.hpt_ppm_get_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def stats(self) -> dict:
         st = Stats()
@@ -377,4 +407,21 @@ def pt_render_wrapper(lights, spheres, triangles, camera, W, H, eye_depth, spp, 
     _check(lib.hpt_pt_render_wrapper(_vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), len(triangles),
                                      mn, mx, _vp(cam), _vp(img), W, H, light_depth, light_sample, eye_depth, spp,
                                      C.c_int64(seed)))
+    return img
+
+
+def ppm_render_wrapper(lights, spheres, triangles, camera, W, H, scene_min, scene_max, light_depth=4, light_sample=8,
+                       eye_depth=4, spp=1, seed=-1) -> np.ndarray:
+    """One-shot photon-mapping pass with the reference's ppm_render_wrapper argument list (include/ppm_cu.cuh:8-15):
+    one pass whatever spp is, the bounds as given, lights as given."""
+    lib = load_library()
+    lights = np.ascontiguousarray(lights, LIGHT)
+    spheres = np.ascontiguousarray(spheres, SPHERE)
+    triangles = np.ascontiguousarray(triangles, TRIANGLE)
+    cam = np.ascontiguousarray(camera, CAMERA).reshape(1)
+    img = np.empty((H, W, 3), np.float32)
+    mn = (C.c_float * 3)(*scene_min)
+    mx = (C.c_float * 3)(*scene_max)
+    _check(lib.hpt_ppm_render_wrapper(_vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), len(triangles),
+                                      mn, mx, _vp(cam), _vp(img), W, H, light_depth, light_sample, eye_depth, spp, C.c_int64(seed)))
     return img

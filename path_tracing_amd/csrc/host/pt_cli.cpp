@@ -6,8 +6,10 @@
 //   --max-depth N     eye depth (reference: EYE_DEPTH 4)  --obj FILE append an OBJ's faces (current material: 0.7 grey diffuse)
 //   --rr              optional unbiased Russian roulette (pt)
 //   --gpus N          render on N devices of this node inside the blocking call (image tiles, RCCL gather)
-// --mode pt and --mode bdpt are built (ppm is outside this library); bdpt renders the reference's CPU
-// estimator (run_cpu_bdpt) on the GPU.
+//   --radius R        photon search radius of --mode ppm (reference: PPM_RADIUS 0.05)
+// --mode pt, bdpt and ppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
+// reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
+// averaged, on one device.
 #include "scene_model.hpp"
 #include "../../../include/hpt.h"
 
@@ -21,7 +23,7 @@
 #define LIGHT_DEPTH 4
 #define EYE_DEPTH 4
 
-namespace hpt_host { extern hpt_params g_run_params; extern bool g_seed_from_clock; extern int g_devices; }
+namespace hpt_host { extern hpt_params g_run_params; extern bool g_seed_from_clock; extern int g_devices; extern float g_ppm_radius; }
 
 int main(int argc, char **argv){
     int spp = 8, spl = 8;
@@ -43,12 +45,13 @@ int main(int argc, char **argv){
         else if(arg == "--obj" && i + 1 < argc) obj_file = argv[++i];
         else if(arg == "--rr") hpt_host::g_run_params.flags |= HPT_FLAG_RUSSIAN_ROULETTE;
         else if(arg == "--gpus" && i + 1 < argc) hpt_host::g_devices = std::max(1, std::stoi(argv[++i]));
+        else if(arg == "--radius" && i + 1 < argc) hpt_host::g_ppm_radius = std::stof(argv[++i]);
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
                       << "  --spp <int>       Samples per pixel (default: 8)\n"
                       << "  --spl <int>       Samples per light (default: 8)\n"
-                      << "  --mode <string>   Render mode: pt, bdpt (default: pt)\n"
+                      << "  --mode <string>   Render mode: pt, bdpt, ppm (default: pt)\n"
                       << "  --device <string> Compute device: gpu (default: gpu)\n"
                       << "  --output <string> Output image path (.png or .pfm)\n"
                       << "  --input <string>  Input scene file\n"
@@ -57,7 +60,8 @@ int main(int argc, char **argv){
                       << "  --max-depth <int> eye depth (default: 4)\n"
                       << "  --obj <file>      append the faces of a Wavefront OBJ\n"
                       << "  --rr              unbiased Russian roulette (pt mode; not in the reference, off by default)\n"
-                      << "  --gpus <int>      devices of this node to render on (image tiles, RCCL gather; default: 1)\n";
+                      << "  --gpus <int>      devices of this node to render on (image tiles, RCCL gather; default: 1; pt and bdpt)\n"
+                      << "  --radius <float>  photon search radius of ppm mode (default: 0.05)\n";
             return 0;
         }
     }
@@ -69,7 +73,7 @@ int main(int argc, char **argv){
     std::cout << " Input  : " << input_file << "\n";
     std::cout << " Output : " << output_file << "\n";
     std::cout << "====================================\n";
-    if(mode != "pt" && mode != "bdpt"){ std::cerr << "[Error] this build provides --mode pt and --mode bdpt (ppm is outside this library).\n"; return -1; }
+    if(mode != "pt" && mode != "bdpt" && mode != "ppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm).\n"; return -1; }
 
     hpt_host::SceneFile scene;
     if(!hpt_host::parse_scene_file(input_file, scene)){
@@ -96,12 +100,14 @@ int main(int argc, char **argv){
 
     std::cout << "[Init] Transferring Data to the GPU...\n";
     if(mode == "bdpt") move_data_to_cuda_bdpt(scene.groups(), scene.lights, spl);
+    else if(mode == "ppm") move_data_to_cuda_ppm(scene.groups(), scene.lights, spl);
     else move_data_to_cuda_pt(scene.groups(), scene.lights, spl);
     if(seed >= 0){ hpt_host::g_seed_from_clock = false; hpt_host::g_run_params.seed = (uint64_t) seed; }
 
     std::cout << "[Render] Starting Render...\n";
     auto start_time = std::chrono::steady_clock::now();
     if(mode == "bdpt") run_cuda_bdpt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp, spl);
+    else if(mode == "ppm") run_cuda_ppm(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
     else run_cuda_pt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
     std::cout << "\n";
     auto diff = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - start_time);

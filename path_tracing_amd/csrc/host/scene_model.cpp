@@ -357,6 +357,7 @@ bool write_image(const std::string &path, const float3 *img, int W, int H, std::
 hpt_params g_run_params = { 1, 0, 0, 0, 0, 0, 0, 0, 0 };
 bool g_seed_from_clock = true;
 int g_devices = 1;            // devices the helper API renders on (pt_cli --gpus): > 1 = fan-out inside the blocking call
+float g_ppm_radius = 0.05f;   // search radius of run_cuda_ppm (pt_cli --radius; the reference's PPM_RADIUS)
 
 } // namespace hpt_host
 
@@ -395,7 +396,7 @@ struct MovedScene {
     }
 };
 
-MovedScene g_pt, g_bdpt;
+MovedScene g_pt, g_bdpt, g_ppm;
 
 hpt_params run_params(){
     hpt_params p = hpt_host::g_run_params;
@@ -434,6 +435,25 @@ void run_cuda_bdpt(CudaCamera cam, float3 *image_buffer, int light_depth, int ey
     int rc = g_bdpt.fan_out ? hpt_multi_render_bdpt(g_bdpt.fan_out, &cam, W, H, eye_depth, light_depth, spp, spl, &p, &image_buffer->x)
                             : hpt_render_bdpt(g_bdpt.device, &cam, W, H, eye_depth, light_depth, spp, spl, &p, &image_buffer->x);
     if(rc != HPT_OK) std::cerr << "run_cuda_bdpt: " << hpt_last_error() << std::endl;
+}
+
+void move_data_to_cuda_ppm(std::map<int, hpt_host::AABB> groups, std::vector<CudaLight> &lights, int light_sample){
+    hpt_host::flatten_groups(groups, lights, g_ppm.flat);
+    g_ppm.light_sample = light_sample;
+    const int devices = hpt_host::g_devices;            // photon mapping renders on one device
+    hpt_host::g_devices = 1;
+    g_ppm.upload("move_data_to_cuda_ppm", false);
+    hpt_host::g_devices = devices;
+}
+
+void run_cuda_ppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int spp){
+    if(!g_ppm.device){ std::cerr << "run_cuda_ppm: no scene moved to the device" << std::endl; return; }
+    hpt_params p = run_params();
+    p.flags &= HPT_FLAG_OUTPUT_SUM | HPT_FLAG_TIME_KERNELS | HPT_FLAG_COUNT_WORK;
+    // bounds of the moved scene: NULL = the scene's own (spheres +- r, triangle vertices), src/ppm_cu_helper.cpp:21-52
+    int rc = hpt_render_ppm(g_ppm.device, &cam, W, H, eye_depth, light_depth, spp, g_ppm.light_sample, hpt_host::g_ppm_radius, nullptr, nullptr,
+                            &p, &image_buffer->x);
+    if(rc != HPT_OK) std::cerr << "run_cuda_ppm: " << hpt_last_error() << std::endl;
 }
 
 // ---- C entry points (tests, Python: scene_io.load_scene_fast / load_obj) ---------------------------------------

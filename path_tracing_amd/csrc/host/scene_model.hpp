@@ -121,3 +121,9 @@ void run_cuda_pt(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_
 // run_cpu_bdpt's estimator on the same groups.
 void move_data_to_cuda_bdpt(std::map<int, hpt_host::AABB> groups, std::vector<CudaLight> &cuda_lights, int light_sample);
 void run_cuda_bdpt(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int spp, int spl = 1);
+// PPM twins (include/ppm_cu_helper.h): light directions normalised, illum NOT divided (the kernel divides by spl,
+// src/ppm_cu_helper.cpp:54-59); the bounds are computed afresh on every move (the reference's accumulate across moves
+// and are never reset, like its vectors in SURVEY Q17).  run_cuda_ppm renders spp passes with `light_sample` photons
+// per light (the reference renders one pass per call and ignores spp); one device.
+void move_data_to_cuda_ppm(std::map<int, hpt_host::AABB> groups, std::vector<CudaLight> &cuda_lights, int light_sample);
+void run_cuda_ppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int spp);

@@ -12,8 +12,10 @@
 #include "hpt_scene.h"
 #include "pt_kernels.h"
 #include "bdpt_kernels.h"
+#include "ppm_kernels.h"
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -118,6 +120,15 @@ struct hpt_scene {
     LightVertexDev *d_lv = nullptr; size_t bd_cap_lv = 0;
     LightVertexCtx *d_lctx = nullptr; size_t bd_cap_lctx = 0;
     uint32_t *cqueue = nullptr; size_t bd_cap_cqueue = 0;
+
+    // photon-mapping path (render_ppm): hit points, deposits and grid, grown on demand
+    bool ppm_bounds_ready = false; float ppm_min[3] = {0, 0, 0}, ppm_max[3] = {0, 0, 0};   // the scene's own bounds
+    PpmHitBuf hb{}; size_t ppm_cap_hp = 0;
+    PpmGrid grid{}; size_t ppm_cap_dep = 0, ppm_cap_buckets = 0, ppm_cap_tmp = 0;
+    uint32_t *ppm_cand = nullptr, *ppm_acc = nullptr; size_t ppm_cap_count = 0;
+    PpmCounters *d_pc = nullptr;
+    std::vector<hipEvent_t> ppm_marks;              // TIME_KERNELS: five events per pass (eye, photon, grid, gather, end)
+    hpt_ppm_stats ppm_stats{}; bool ppm_pending = false; int ppm_flags = 0; uint32_t ppm_hp_last = 0;
 
     hipEvent_t ev_start = nullptr, ev_stop = nullptr; bool ev_valid = false;
     std::vector<TimedLaunch> timed; std::vector<hipEvent_t> event_pool; size_t event_next = 0;
@@ -724,6 +735,226 @@ int render_bdpt_local(hpt_scene *s, const void *camera, int W, int H, int eye_de
     return HPT_OK;
 }
 
+
+void free_ppm(hpt_scene *s){
+    hipFree(s->hb.pos_mat); hipFree(s->hb.nrm); hipFree(s->hb.wo); hipFree(s->hb.thr); hipFree(s->hb.list);
+    hipFree(s->grid.dep); hipFree(s->grid.key); hipFree(s->grid.slot_in); hipFree(s->grid.key_sorted); hipFree(s->grid.slot_sorted);
+    hipFree(s->grid.packed); hipFree(s->grid.range); hipFree(s->grid.sort_tmp);
+    hipFree(s->ppm_cand); hipFree(s->ppm_acc); hipFree(s->d_pc);
+    for(hipEvent_t e : s->ppm_marks) hipEventDestroy(e);
+    s->ppm_marks.clear();
+    s->hb = PpmHitBuf{}; s->grid = PpmGrid{}; s->ppm_cand = s->ppm_acc = nullptr; s->d_pc = nullptr;
+    s->ppm_cap_hp = s->ppm_cap_dep = s->ppm_cap_buckets = s->ppm_cap_tmp = s->ppm_cap_count = 0;
+}
+
+// the scene's bounds as the reference's helper computes them (src/ppm_cu_helper.cpp:21-52): spheres +- r and triangle
+// vertices, light balls left out, starting from +-1e9
+void ppm_scene_bounds(hpt_scene *s){
+    if(s->ppm_bounds_ready) return;
+    float mn[3] = { 1e9f, 1e9f, 1e9f }, mx[3] = { -1e9f, -1e9f, -1e9f };
+    for(int i = 0; i < s->ns; ++i){
+        float c[4]; memcpy(c, s->h_spheres.data() + (size_t) i * HPT_SPHERE_BYTES, 16);
+        for(int a = 0; a < 3; ++a){ mx[a] = std::max(mx[a], c[a] + c[3]); mn[a] = std::min(mn[a], c[a] - c[3]); }
+    }
+    for(int i = 0; i < s->nt; ++i){
+        float v[9]; memcpy(v, s->h_tris.data() + (size_t) i * HPT_TRIANGLE_BYTES, 36);
+        for(int a = 0; a < 3; ++a){
+            mx[a] = std::max({ mx[a], v[a], v[3 + a], v[6 + a] });
+            mn[a] = std::min({ mn[a], v[a], v[3 + a], v[6 + a] });
+        }
+    }
+    for(int a = 0; a < 3; ++a){ s->ppm_min[a] = mn[a]; s->ppm_max[a] = mx[a]; }
+    s->ppm_bounds_ready = true;
+}
+
+constexpr int32_t kPpmFlags = HPT_FLAG_OUTPUT_SUM | HPT_FLAG_TIME_KERNELS | HPT_FLAG_COUNT_WORK;
+
+// the photon-mapping render (reference src/ppm_cu.cu:328-400, `spp` passes), blocking, whole image into host_image
+int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl, float radius,
+               const float *scene_min, const float *scene_max, const hpt_params *params, float *host_image){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(!camera || !host_image) return fail(HPT_ERR_INVALID, "null camera or image");
+    if(spp <= 0 || spl < 0 || eye_depth <= 0 || eye_depth > 255 || light_depth <= 0 || light_depth > 255)
+        return fail(HPT_ERR_INVALID, "spp must be > 0, spl >= 0 and depths in [1, 255]");
+    if(int rcd = on_scene_device(s)) return rcd;
+    hpt_params P; memset(&P, 0, sizeof P);
+    if(params) P = *params;
+    if(P.world > 1) return fail(HPT_ERR_INVALID, "hpt_render_ppm renders the whole image on one device: world must be 0 or 1");
+    if(P.flags & ~kPpmFlags) return fail(HPT_ERR_INVALID, "hpt_render_ppm accepts HPT_FLAG_OUTPUT_SUM, TIME_KERNELS and COUNT_WORK only");
+    if(P.reserved) return fail(HPT_ERR_INVALID, "hpt_params.reserved must be zero for hpt_render_ppm");
+    if(P.max_delta <= 0) P.max_delta = 64;
+    if(P.max_delta > 250) P.max_delta = 250;
+    Tiling tl;
+    int rc = make_tiling(W, H, &P, tl);
+    if(rc) return rc;
+    if(!(radius > 0.0f)) radius = 0.05f;                                    // PPM_RADIUS, include/ppm_cu.cuh:4
+    PpmFrame fr;
+    ppm_scene_bounds(s);
+    for(int a = 0; a < 3; ++a){ fr.smin[a] = scene_min ? scene_min[a] : s->ppm_min[a]; fr.smax[a] = scene_max ? scene_max[a] : s->ppm_max[a]; }
+    fr.cell = radius; fr.r2 = radius * radius;
+
+    const uint64_t n_ph64 = s->nl > 0 ? (uint64_t) s->nl * (uint64_t) spl : 0u;
+    const uint64_t n_dep64 = n_ph64 * (uint64_t) light_depth;
+    if(n_dep64 > (1ull << 30))
+        return fail(HPT_ERR_NOMEM, "num_lights * spl * light_depth photon deposits do not fit (at most 2^30 per pass)");
+    const uint32_t n_ph = (uint32_t) n_ph64, n_dep = (uint32_t) n_dep64;
+    uint32_t buckets = 1024u;
+    while(buckets < 2u * n_dep) buckets <<= 1;
+    fr.buckets = buckets;
+    const uint32_t n_local = (uint32_t) tl.n_local;
+    const size_t paths = std::max<size_t>(n_local, n_ph);
+    const int eye_iters = 1 + P.max_delta, ph_iters = light_depth + P.max_delta;
+    const int M = std::max(eye_iters, ph_iters) + 2;
+    const int n_counters = 4 * M + 2;
+    rc = ensure_workspace(s, paths, tl.n_local, n_counters);
+    if(rc) return rc;
+    const bool count = (P.flags & HPT_FLAG_COUNT_WORK) != 0, timek = (P.flags & HPT_FLAG_TIME_KERNELS) != 0;
+    if(n_local > s->ppm_cap_hp){
+        size_t c;
+        c = s->ppm_cap_hp; rc = grow(&s->hb.pos_mat, c, n_local); if(rc) return rc;
+        c = s->ppm_cap_hp; rc = grow(&s->hb.nrm, c, n_local); if(rc) return rc;
+        c = s->ppm_cap_hp; rc = grow(&s->hb.wo, c, n_local); if(rc) return rc;
+        c = s->ppm_cap_hp; rc = grow(&s->hb.thr, c, n_local); if(rc) return rc;
+        c = s->ppm_cap_hp; rc = grow(&s->hb.list, c, n_local); if(rc) return rc;
+        s->ppm_cap_hp = n_local;
+    }
+    if(count && n_local > s->ppm_cap_count){
+        size_t c = s->ppm_cap_count; rc = grow(&s->ppm_cand, c, n_local); if(rc) return rc;
+        c = s->ppm_cap_count; rc = grow(&s->ppm_acc, c, n_local); if(rc) return rc;
+        s->ppm_cap_count = n_local;
+    }
+    const size_t dep_cap = std::max<size_t>(n_dep, 1);
+    if(dep_cap > s->ppm_cap_dep){
+        size_t c;
+        c = s->ppm_cap_dep * 4; rc = grow(&s->grid.dep, c, dep_cap * 4); if(rc) return rc;
+        c = s->ppm_cap_dep * 4; rc = grow(&s->grid.packed, c, dep_cap * 4); if(rc) return rc;
+        c = s->ppm_cap_dep; rc = grow(&s->grid.key, c, dep_cap); if(rc) return rc;
+        c = s->ppm_cap_dep; rc = grow(&s->grid.slot_in, c, dep_cap); if(rc) return rc;
+        c = s->ppm_cap_dep; rc = grow(&s->grid.key_sorted, c, dep_cap); if(rc) return rc;
+        c = s->ppm_cap_dep; rc = grow(&s->grid.slot_sorted, c, dep_cap); if(rc) return rc;
+        s->ppm_cap_dep = dep_cap;
+    }
+    rc = grow(&s->grid.range, s->ppm_cap_buckets, buckets); if(rc) return rc;
+    const size_t tmp = std::max<size_t>(ppm_sort_tmp_bytes(n_dep, buckets), 1);
+    { size_t c = s->ppm_cap_tmp; rc = grow((unsigned char **) &s->grid.sort_tmp, c, tmp); if(rc) return rc; s->ppm_cap_tmp = c; }
+    s->grid.sort_tmp_bytes = tmp; s->grid.buckets = buckets;
+    if(!s->d_pc) HIP_TRY(hipMalloc((void **) &s->d_pc, sizeof(PpmCounters)));
+    { size_t c = s->cap_local_own; rc = grow(&s->d_local_own, c, (size_t) tl.n_local * 3); if(rc) return rc; s->cap_local_own = c; }
+    { size_t c = s->cap_image_own; rc = grow(&s->d_image_own, c, (size_t) W * H * 3); if(rc) return rc; s->cap_image_own = c; }
+
+    const float *cf = (const float *) camera;
+    CameraDev cam;
+    memcpy(cam.eye, cf + 0, 12); memcpy(cam.UL, cf + 12, 12); memcpy(cam.dx, cf + 15, 12); memcpy(cam.dy, cf + 18, 12);
+    hipStream_t st = nullptr;
+    PassBuffers &w = s->pass[0];
+    uint32_t *eq = w.counters, *elc = w.counters + M, *pq = w.counters + 2 * M, *plc = w.counters + 3 * M;
+    uint32_t *hp_count = w.counters + 4 * M, *no_shadow = w.counters + 4 * M + 1;
+    const int budget = resume_walk_fits(s->sd) ? kTraceBudget : 0;
+    // closest-hit rays of the queue in cnt[it] (it = 0: the identity queue), the PT path's split trace step
+    auto trace = [&](int it, const uint32_t *queue, uint32_t *cnt, uint32_t *lcnt, uint32_t max_items){
+        TraceSplit split{ w.lqueue[0], &lcnt[it], w.lqueue[1], no_shadow, budget };
+        launch_trace(st, s->sd, w.pb, w.sb, queue, &cnt[it], max_items, nullptr, nullptr, 0, s->stack_levels, false, nullptr, &split, nullptr, 0u);
+        if(budget > 0) launch_trace_resume(st, s->sd, w.pb, w.sb, true, false, max_items, nullptr, split, nullptr, 0u, w.deep_stack);
+    };
+    // the host looks at a queue's length before an iteration that only delta bounces can fill
+    auto queue_empty = [&](const uint32_t *cnt, bool &empty) -> int {
+        HIP_TRY(hipMemcpyAsync(w.h_count, cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        empty = *w.h_count == 0u;
+        return HPT_OK;
+    };
+    const size_t n_marks = timek ? (size_t) spp * 5 : 0;
+    while(s->ppm_marks.size() < n_marks){ hipEvent_t e; HIP_TRY(hipEventCreate(&e)); s->ppm_marks.push_back(e); }
+    auto mark = [&](int pass, int k){ if(timek) hipEventRecord(s->ppm_marks[(size_t) pass * 5 + k], st); };
+
+    HIP_TRY(hipMemsetAsync(s->d_pc, 0, sizeof(PpmCounters), st));
+    HIP_TRY(hipMemsetAsync(s->accum, 0, (size_t) tl.n_local * sizeof(float4), st));
+    if(n_dep) launch_ppm_iota(st, s->grid.slot_in, n_dep);
+    HIP_TRY(hipEventRecord(s->ev_start, st));
+    for(int pass = 0; pass < spp; ++pass){
+        const uint32_t pidx = (uint32_t) (P.sample_offset + pass);
+        HIP_TRY(hipMemsetAsync(w.counters, 0, (size_t) n_counters * sizeof(uint32_t), st));
+        mark(pass, 0);
+        // eye pass: slot = local pixel, stream (seed ^ kPpmEyeKey, pixel, pass), jitter first
+        launch_generate(st, tl, cam, w.pb, &eq[0], 1, pidx, P.seed ^ kPpmEyeKey, nullptr);
+        int cur = 0;
+        for(int it = 0; it < eye_iters; ++it){
+            if(it >= 1){ bool empty; if(int r = queue_empty(&eq[it], empty)) return r; if(empty) break; }
+            const uint32_t *q = it == 0 ? nullptr : w.queue[cur];
+            trace(it, q, eq, elc, n_local);
+            launch_ppm_eye_shade(st, s->sd, w.pb, s->hb, q, &eq[it], n_local, w.queue[cur ^ 1], &eq[it + 1], hp_count, P.max_delta, s->d_pc);
+            cur ^= 1;
+        }
+        mark(pass, 1);
+        if(n_ph){
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) s->grid.key, (int) buckets, n_dep, st));
+            launch_ppm_emit(st, s->sd, w.pb, &pq[0], n_ph, spl, P.seed, pidx, fr);
+            cur = 0;
+            for(int it = 0; it < ph_iters; ++it){
+                if(it >= light_depth){ bool empty; if(int r = queue_empty(&pq[it], empty)) return r; if(empty) break; }
+                const uint32_t *q = it == 0 ? nullptr : w.queue[cur];
+                trace(it, q, pq, plc, n_ph);
+                launch_ppm_photon_shade(st, s->sd, w.pb, s->grid, q, &pq[it], n_ph, w.queue[cur ^ 1], &pq[it + 1], light_depth,
+                                        P.max_delta, fr, s->d_pc);
+                cur ^= 1;
+            }
+        }
+        mark(pass, 2);
+        HIP_TRY(hipMemsetAsync(s->grid.range, 0, (size_t) buckets * sizeof(uint2), st));
+        if(n_dep && launch_ppm_grid(st, s->grid, n_dep)) return fail(HPT_ERR_DEVICE, "photon grid: radix sort launch failed");
+        mark(pass, 3);
+        launch_ppm_gather(st, s->sd, w.pb, s->hb, s->grid, hp_count, n_local, fr, count ? s->ppm_cand : nullptr,
+                          count ? s->ppm_acc : nullptr, s->d_pc);
+        launch_resolve(st, tl, w.pb, s->accum, 1);
+        mark(pass, 4);
+    }
+    launch_finalize(st, tl, s->accum, s->d_local_own, (P.flags & HPT_FLAG_OUTPUT_SUM) ? 1.0f : (float) spp);
+    launch_untile(st, tl, s->d_local_own, s->d_image_own);
+    HIP_TRY(hipEventRecord(s->ev_stop, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(host_image, s->d_image_own, (size_t) W * H * 3 * sizeof(float), hipMemcpyDeviceToHost));
+
+    // statistics of this render (the call is blocking anyway)
+    hpt_ppm_stats &ps = s->ppm_stats;
+    memset(&ps, 0, sizeof ps);
+    PpmCounters pc;
+    HIP_TRY(hipMemcpy(&pc, s->d_pc, sizeof pc, hipMemcpyDeviceToHost));
+    ps.photons = n_ph64 * (uint64_t) spp; ps.photon_rays = pc.photon_rays; ps.deposits = pc.deposits;
+    ps.hit_points = pc.hit_points; ps.direct_pixels = pc.direct; ps.candidates = pc.candidates; ps.accepted = pc.accepted;
+    ps.grid_buckets = buckets;
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
+    ps.ms_total = ms;
+    if(timek){
+        double *phase[4] = { &ps.ms_eye, &ps.ms_photon, &ps.ms_grid, &ps.ms_gather };
+        for(int pass = 0; pass < spp; ++pass) for(int k = 0; k < 4; ++k){
+            float e = 0.0f;
+            if(hipEventElapsedTime(&e, s->ppm_marks[(size_t) pass * 5 + k], s->ppm_marks[(size_t) pass * 5 + k + 1]) == hipSuccess) *phase[k] += e;
+        }
+    }
+    if(count){
+        uint32_t nhp = 0;
+        HIP_TRY(hipMemcpy(&nhp, hp_count, sizeof nhp, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> list(nhp), cand(n_local), acc(n_local);
+        if(nhp){
+            HIP_TRY(hipMemcpy(list.data(), s->hb.list, (size_t) nhp * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cand.data(), s->ppm_cand, (size_t) n_local * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(acc.data(), s->ppm_acc, (size_t) n_local * 4, hipMemcpyDeviceToHost));
+            std::vector<uint32_t> c(nhp), a(nhp);
+            for(uint32_t k = 0; k < nhp; ++k){ c[k] = cand[list[k]]; a[k] = acc[list[k]]; }
+            std::nth_element(c.begin(), c.begin() + nhp / 2, c.end()); ps.cand_median = c[nhp / 2];
+            std::nth_element(a.begin(), a.begin() + nhp / 2, a.end()); ps.acc_median = a[nhp / 2];
+            ps.cand_max = *std::max_element(c.begin(), c.end()); ps.acc_max = *std::max_element(a.begin(), a.end());
+        }
+    }
+    // hpt_get_stats after this render reports its total time only
+    s->timed.clear(); s->event_next = 0; s->last_counter_stride = 0; s->last_budget = 0; s->last_flags = P.flags;
+    s->stats.ms_extend = s->stats.ms_shade = s->stats.ms_connect = s->stats.ms_other = 0.0;
+    s->stats.n_extend = s->stats.n_shade = s->stats.n_connect = s->stats.n_other = 0;
+    s->ev_valid = true; s->stats_pending = true;
+    return HPT_OK;
+}
+
 } // namespace
 
 namespace {
@@ -894,6 +1125,7 @@ void hpt_scene_destroy(hpt_scene *s){
     hipFree(s->d_nodes); hipFree(s->d_qnodes); hipFree(s->d_wnodes); hipFree(s->d_tris); hipFree(s->d_rounds); hipFree(s->d_mats); hipFree(s->d_lights);
     hipFree(s->d_tri_frames);
     free_bdpt(s);
+    free_ppm(s);
     if(s->ev_start) hipEventDestroy(s->ev_start);
     if(s->ev_stop) hipEventDestroy(s->ev_stop);
     for(hipEvent_t e : s->event_pool) hipEventDestroy(e);
@@ -1181,6 +1413,32 @@ int hpt_bdpt_render_wrapper(const void *lights, int nl, const void *spheres, int
     hpt_params p; memset(&p, 0, sizeof p);
     p.seed = seed >= 0 ? (uint64_t) seed : (uint64_t) time(nullptr);
     rc = hpt_render_bdpt(s, camera, W, H, eye_depth, light_depth, spp, spl, &p, host_image);
+    wrapper_release(s);
+    return rc;
+}
+
+int hpt_render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl, float radius,
+                   const float *scene_min, const float *scene_max, const hpt_params *params, float *host_image){
+    return render_ppm(s, camera, W, H, eye_depth, light_depth, spp, spl, radius, scene_min, scene_max, params, host_image);
+}
+
+int hpt_ppm_get_stats(const hpt_scene *s, hpt_ppm_stats *out){
+    if(!s || !out) return fail(HPT_ERR_INVALID, "null argument");
+    *out = s->ppm_stats;
+    return HPT_OK;
+}
+
+int hpt_ppm_render_wrapper(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt,
+                           const float scene_min[3], const float scene_max[3], const void *camera, float *host_image,
+                           int W, int H, int light_depth, int light_sample, int eye_depth, int spp, int64_t seed){
+    (void) spp;                  // one call is one pass: the reference never reads spp (src/ppm_cu.cu:328-400)
+    std::lock_guard<std::mutex> lock(g_wrap.mu);
+    hpt_scene *s = nullptr;      // one device whatever hpt_wrapper_set_devices says (include/hpt.h)
+    int rc = wrapper_scene(lights, nl, spheres, ns, tris, nt, &s);
+    if(rc) return rc;
+    hpt_params p; memset(&p, 0, sizeof p);
+    p.seed = seed >= 0 ? (uint64_t) seed : (uint64_t) time(nullptr);      // reference: time(NULL) + 1234, ppm_cu.cu:358
+    rc = hpt_render_ppm(s, camera, W, H, eye_depth, light_depth, 1, light_sample, 0.05f, scene_min, scene_max, &p, host_image);
     wrapper_release(s);
     return rc;
 }

@@ -1,0 +1,226 @@
+// TEST INFRASTRUCTURE ONLY -- CPU restatement of the photon-mapping path (reference src/ppm_cu.cu) with the order of
+// every sum defined as DESIGN.md "PPM" defines it.  Built by tests/ppm_oracle.py with the flags of oracle/Makefile;
+// the shared math (BSDF, intersections, PCG) is oracle/ref_math.hpp, which the HIP kernels match bit for bit.
+//
+// Closest hit: the reference's brute-force scan (include/geometric.cuh:327-388).  Gather: a std::map from cell to
+// the ascending list of deposit slots; brute != 0 instead scans every deposit slot for every one of the 27 cells
+// (the double loop the map must agree with).
+#include "../oracle/ref_math.hpp"
+
+#include <cstdint>
+#include <map>
+#include <tuple>
+#include <vector>
+
+using namespace orc;
+
+namespace {
+
+constexpr uint64_t kEyeKey = 0x5050454945ull;        // path_tracing_amd/csrc/ppm_kernels.h
+constexpr uint64_t kPhotonKey = 0x50504850484Full;
+
+struct Sc { const RLight *lights; int nl; const RSphere *spheres; int ns; const RTriangle *tris; int nt; };
+
+Hit closest(const Sc &sc, V3 ro, V3 rd){
+    Hit best; best.hit = false; best.t = 1e20f; best.is_light = false; best.prim = -1;
+    best.mtl.base_color = v3(0, 0, 0); best.mtl.roughness = 0; best.mtl.metallic = 0; best.mtl.eta = 0; best.mtl.type = 0;
+    best.pos = v3(0, 0, 0); best.normal = v3(0, 0, 0);
+    float t; const float max_dist = 1e20f;
+    for(int i = 0; i < sc.ns; ++i){
+        const RSphere &s = sc.spheres[i];
+        if(intersect_sphere(ro, rd, s.center, s.r, t, max_dist) && t < best.t){
+            best.hit = true; best.t = t; best.mtl = s.mtl; best.pos = ro + rd * t;
+            best.normal = normalize(best.pos - s.center); best.is_light = false; best.prim = i;
+            if(dot(best.normal, rd) > 0.0f) best.normal = best.normal * -1.0f;
+        }
+    }
+    for(int i = 0; i < sc.nl; ++i){
+        const RSphere &s = sc.lights[i].light_ball;
+        if(intersect_sphere(ro, rd, s.center, s.r, t, max_dist) && t < best.t){
+            best.hit = true; best.t = t; best.mtl.base_color = sc.lights[i].illum; best.pos = ro + rd * t;
+            best.normal = normalize(best.pos - s.center); best.is_light = true; best.prim = sc.ns + i;
+            if(dot(best.normal, rd) > 0.0f) best.normal = best.normal * -1.0f;
+        }
+    }
+    for(int i = 0; i < sc.nt; ++i){
+        const RTriangle &tr = sc.tris[i];
+        if(intersect_triangle(ro, rd, tr.v0, tr.v1, tr.v2, t, max_dist) && t < best.t){
+            best.hit = true; best.t = t; best.mtl = tr.mtl; best.pos = ro + rd * t;
+            best.normal = normalize(cross(tr.v1 - tr.v0, tr.v2 - tr.v0)); best.is_light = false; best.prim = sc.ns + sc.nl + i;
+            if(dot(best.normal, rd) > 0.0f) best.normal = best.normal * -1.0f;
+        }
+    }
+    return best;
+}
+
+struct HitPoint { bool valid; V3 pos, normal, wo, thr; RMat mtl; };
+struct Deposit { bool valid; V3 pos, normal, wi, flux; int cx, cy, cz; };
+
+void cell_of(V3 p, V3 mn, float cell, int &gx, int &gy, int &gz){
+    gx = (int) floorf((p.x - mn.x) / cell);
+    gy = (int) floorf((p.y - mn.y) / cell);
+    gz = (int) floorf((p.z - mn.z) / cell);
+}
+
+} // namespace
+
+// stats_out: photons, photon_rays, deposits, hit_points, direct_pixels (summed over passes).
+// flux_out (optional, W*H*3): the accumulated flux of every pixel's hit point in the LAST pass.
+extern "C" int ppm_oracle_render(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt,
+                                 const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl,
+                                 float radius, const float *smin, const float *smax, uint64_t seed, int sample_offset,
+                                 int max_delta, int output_sum, int brute, float *image, uint64_t *stats_out, float *flux_out){
+    Sc sc{ (const RLight *) lights, nl, (const RSphere *) spheres, ns, (const RTriangle *) tris, nt };
+    const RCamera &cam = *(const RCamera *) camera;
+    if(max_delta <= 0) max_delta = 64;
+    if(max_delta > 250) max_delta = 250;
+    if(!(radius > 0.0f)) radius = 0.05f;
+    const float cell = radius, r2 = radius * radius;
+    const V3 mn = v3(smin[0], smin[1], smin[2]), mx = v3(smax[0], smax[1], smax[2]);
+    const int n_ph = nl > 0 ? nl * spl : 0;
+    const size_t npx = (size_t) W * H;
+    std::vector<V3> sum(npx, v3(0, 0, 0)), img(npx);
+    std::vector<HitPoint> hps(npx);
+    std::vector<Deposit> deps((size_t) n_ph * light_depth);
+    uint64_t st[5] = { 0, 0, 0, 0, 0 };
+    for(int pass = 0; pass < spp; ++pass){
+        const uint32_t pidx = (uint32_t) (sample_offset + pass);
+        uint64_t direct = 0, nhp = 0, ndep = 0, rays = 0;
+        // eye pass, ppm_cu.cu:64-150
+#pragma omp parallel for schedule(dynamic, 16) reduction(+:direct, nhp)
+        for(int py = 0; py < H; ++py) for(int px = 0; px < W; ++px){
+            const size_t idx = (size_t) py * W + px;
+            HitPoint &hp = hps[idx]; hp.valid = false;
+            img[idx] = v3(0, 0, 0);
+            Pcg rng; rng.seed(seed ^ kEyeKey, (uint32_t) idx, pidx);
+            float pixel_x = (float) px + rng.next();
+            float pixel_y = (float) py + rng.next();
+            V3 o = cam.eye;
+            V3 pixel_pos = cam.UL + cam.dx * pixel_x + cam.dy * pixel_y;
+            V3 d = normalize(pixel_pos - o);
+            float eta = 1.0f;
+            V3 thr = v3(1, 1, 1);
+            int deltas = 0;
+            for(int depth = 0; depth < eye_depth; depth++){
+                Hit h = closest(sc, o, d);
+                if(!h.hit) break;
+                V3 wo = d * -1.0f;
+                if(h.is_light){
+                    V3 c = thr * h.mtl.base_color;
+                    if(is_valid_color(c)){ img[idx] = clamp_radiance(c, 15.0f); ++direct; }
+                    break;
+                }
+                float u_rr = rng.next(), u1 = rng.next(), u2 = rng.next();
+                V3 wi, f; float pdf, new_eta; bool is_delta;
+                bsdf_sample(0, h.mtl, wo, h.normal, u_rr, u1, u2, eta, wi, f, pdf, is_delta, new_eta);
+                if(is_delta){
+                    if(pdf <= 0.0f) break;
+                    thr = thr * f;
+                    d = wi; eta = new_eta;
+                    o = h.pos + h.normal * (dot(wi, h.normal) < 0.0f ? -kEps : kEps);
+                    if(!is_valid_color(thr)) break;
+                    if(++deltas > max_delta) break;
+                    depth--;
+                    continue;
+                }
+                hp.valid = true; hp.pos = h.pos; hp.normal = h.normal; hp.wo = wo; hp.mtl = h.mtl; hp.thr = thr;
+                ++nhp;
+                break;
+            }
+        }
+        // photon pass, ppm_cu.cu:156-295 (deposit slot = photon * light_depth + depth)
+        for(Deposit &dp : deps) dp.valid = false;
+#pragma omp parallel for schedule(dynamic, 64) reduction(+:ndep, rays)
+        for(int i = 0; i < n_ph; ++i){
+            Pcg rng; rng.seed(seed ^ kPhotonKey, (uint32_t) i, pidx);
+            const RLight &L = sc.lights[i % nl];
+            V3 w = normalize(L.dir);
+            V3 u_vec = (fabsf(w.x) > 0.9f) ? v3(0, 1, 0) : v3(1, 0, 0);
+            V3 v_vec = normalize(cross(w, u_vec));
+            u_vec = normalize(cross(v_vec, w));
+            V3 o, d;
+            if(L.is_parallel){
+                d = w;
+                V3 center = (mn + mx) * 0.5f;
+                float scene_radius = length(mx - mn) * 0.5f;
+                float r1 = rng.next(), rr2 = rng.next();
+                float plane = scene_radius * 2.0f;
+                float offset_u = (r1 - 0.5f) * plane, offset_v = (rr2 - 0.5f) * plane;
+                o = center - d * (scene_radius * 2.0f) + u_vec * offset_u + v_vec * offset_v;
+            } else {
+                float u1 = rng.next(), u2 = rng.next();
+                float cos_t = 1.0f - u1 * (1.0f - cosf(L.cutoff));
+                float sin_t = sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t));
+                float sp, cp; sincos_2pi_poly(u2, sp, cp);
+                V3 ld = v3(sin_t * cp, sin_t * sp, cos_t);
+                d = normalize(u_vec * ld.x + v_vec * ld.y + w * ld.z);
+                o = L.pos + d * L.light_ball.r;
+            }
+            V3 flux = L.illum * (float) nl / fmaxf((float) spl, 1.0f);
+            float eta = 1.0f;
+            int deltas = 0;
+            for(int depth = 0; depth < light_depth; depth++){
+                Hit h = closest(sc, o, d);
+                ++rays;
+                if(!h.hit || h.is_light) break;
+                V3 wi_light = d * -1.0f;
+                if(h.mtl.eta <= 0.0f && (h.mtl.metallic < 0.99f || h.mtl.roughness > 0.01f)){
+                    Deposit &dp = deps[(size_t) i * light_depth + depth];
+                    dp.valid = true; dp.pos = h.pos; dp.normal = h.normal; dp.wi = wi_light; dp.flux = flux;
+                    cell_of(h.pos, mn, cell, dp.cx, dp.cy, dp.cz);
+                    ++ndep;
+                }
+                float u_rr = rng.next(), u1 = rng.next(), u2 = rng.next();
+                V3 wi, f; float pdf, new_eta; bool is_delta;
+                bsdf_sample(0, h.mtl, wi_light, h.normal, u_rr, u1, u2, eta, wi, f, pdf, is_delta, new_eta);
+                if(pdf <= 0.0f) break;
+                float cos_wi = fabsf(dot(h.normal, wi));
+                if(is_delta){ flux = flux * f; depth--; }
+                else flux = flux * f * cos_wi / pdf;
+                if(!is_valid_color(flux)) break;
+                if(is_delta && ++deltas > max_delta) break;
+                d = wi; eta = new_eta;
+                o = h.pos + h.normal * (dot(wi, h.normal) < 0.0f ? -kEps : kEps);
+            }
+        }
+        // gather in the defined order: 27 cells (z, y, x from -1 to +1), ascending slot inside a cell
+        std::map<std::tuple<int, int, int>, std::vector<uint32_t>> grid;
+        if(!brute) for(size_t k = 0; k < deps.size(); ++k) if(deps[k].valid) grid[std::make_tuple(deps[k].cx, deps[k].cy, deps[k].cz)].push_back((uint32_t) k);
+#pragma omp parallel for schedule(dynamic, 16)
+        for(int64_t idx = 0; idx < (int64_t) npx; ++idx){
+            const HitPoint &hp = hps[idx];
+            if(!hp.valid){ if(flux_out){ flux_out[idx * 3] = flux_out[idx * 3 + 1] = flux_out[idx * 3 + 2] = 0.0f; } continue; }
+            int cx, cy, cz;
+            cell_of(hp.pos, mn, cell, cx, cy, cz);
+            V3 acc = v3(0, 0, 0);
+            auto visit = [&](const Deposit &dp){
+                if(!(dot(hp.normal, dp.normal) > 0.01f)) return;
+                V3 dd = hp.pos - dp.pos;
+                if(!(dot(dd, dd) < r2)) return;
+                V3 brdf = bsdf_evaluate(hp.mtl, hp.wo, dp.wi, hp.normal);
+                if(is_valid_color(brdf)) acc = acc + dp.flux * brdf * hp.thr;
+            };
+            for(int z = -1; z <= 1; z++) for(int y = -1; y <= 1; y++) for(int x = -1; x <= 1; x++){
+                const int gx = cx + x, gy = cy + y, gz = cz + z;
+                if(brute){
+                    for(const Deposit &dp : deps) if(dp.valid && dp.cx == gx && dp.cy == gy && dp.cz == gz) visit(dp);
+                } else {
+                    auto it = grid.find(std::make_tuple(gx, gy, gz));
+                    if(it != grid.end()) for(uint32_t k : it->second) visit(deps[k]);
+                }
+            }
+            if(flux_out){ flux_out[idx * 3] = acc.x; flux_out[idx * 3 + 1] = acc.y; flux_out[idx * 3 + 2] = acc.z; }
+            V3 radiance = acc / fmaxf(kPi * r2, 1e-6f);
+            if(is_valid_color(radiance)) img[idx] = img[idx] + clamp_radiance(radiance, 15.0f);
+        }
+        for(size_t k = 0; k < npx; ++k){ V3 c = img[k]; if(!is_valid_color(c)) c = v3(0, 0, 0); sum[k] = sum[k] + c; }
+        st[0] += (uint64_t) n_ph; st[1] += rays; st[2] += ndep; st[3] += nhp; st[4] += direct;
+    }
+    for(size_t k = 0; k < npx; ++k){
+        V3 v = sum[k];
+        if(!output_sum && spp != 1) v = v / (float) spp;
+        image[k * 3] = v.x; image[k * 3 + 1] = v.y; image[k * 3 + 2] = v.z;
+    }
+    if(stats_out) for(int k = 0; k < 5; ++k) stats_out[k] = st[k];
+    return 0;
+}
