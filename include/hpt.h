@@ -248,6 +248,40 @@ int hpt_ppm_render_wrapper(const void *lights, int num_lights, const void *spher
                            const void *camera, float *host_image, int W, int H,
                            int light_depth, int light_sample, int eye_depth, int spp, int64_t seed);
 
+/* ---- progressive photon mapping (per-pixel shrinking radius) ----------------------------------------
+ * The progressive step of Hachisuka & Jensen's photon mapping, whose statistics the reference's hit-point record
+ * carries (radius2, photon_count, accum_flux in src/ppm_cu.cu) but never uses.  A state holds, per pixel i:
+ * R2_i (starts at radius^2), N_i (0), tau_i (0, flux) and D_i (0, the sum of direct terms); K counts the passes.
+ * Pass K has the global index sample_offset + K; its eye pass, photons, deposits and grid are those of
+ * hpt_render_ppm's pass of that index, with the grid cell = the initial radius for the whole life of the state.
+ *   gather   at pixel i's hit point, PPM's cells in PPM's order, a deposit accepted when its cell matches, the
+ *            normals agree (> 0.01) and |h - p|^2 < R2_i; for each accepted deposit whose BSDF value f is a valid
+ *            colour: Phi += flux * f * throughput, M += 1.  Cells no deposit within R_i can lie in are skipped
+ *            ("Progressive photon mapping"): the result is the same bits.
+ *   update   pixels with a hit point and M > 0: n = N + alpha M, ratio = n / (N + M), R2 *= ratio,
+ *            tau = (tau + Phi) * ratio, N = n.  alpha = 1 keeps the radius (ratio is exactly 1).
+ *   direct   D += the direct term of the eye pass (k_resolve's guard).
+ *   estimate d = D, p = tau / max(pi R2, 1e-6), both divided by K unless K = 1;
+ *            pixel = p a valid colour ? d + clamp(p, 15) : d.
+ * One pass with alpha = 1 gives the bytes of hpt_render_ppm with spp = 1 (same seed, offset and radius).
+ *
+ * hpt_sppm_create takes seed, sample_offset, max_delta and tile from params (flags must be 0, reserved 0, world
+ * 0 or 1); radius <= 0 -> 0.05; scene_min / scene_max NULL -> the scene's bounds as for hpt_render_ppm.  alpha
+ * outside (0, 1], spl < 0 or depths outside [1, 255] return HPT_ERR_INVALID.  The state lives on the scene's device
+ * and the scene must outlive it; renders of any kind on the scene in between do not touch it.
+ * hpt_sppm_render advances the state by `passes` (> 0) passes and writes the estimate (W*H*3 floats, row-major)
+ * into host_image; flags may hold HPT_FLAG_TIME_KERNELS and HPT_FLAG_COUNT_WORK only, and the scene's
+ * hpt_ppm_stats then describe this call (candidates: the pairs examined in the cells visited).  hpt_sppm_reset
+ * returns to K = 0.  hpt_sppm_read_state copies R2 and N (W*H floats each, row-major; either may be NULL) and K. */
+typedef struct hpt_sppm hpt_sppm;
+int hpt_sppm_create(hpt_scene *scene, const void *camera, int W, int H, int eye_depth, int light_depth, int spl,
+                    float radius, float alpha, const float *scene_min, const float *scene_max,
+                    const hpt_params *params, hpt_sppm **out);
+int hpt_sppm_render(hpt_sppm *state, int passes, int32_t flags, float *host_image);
+int hpt_sppm_reset(hpt_sppm *state);
+int hpt_sppm_read_state(const hpt_sppm *state, float *radius2, float *photons, int64_t *passes);
+void hpt_sppm_destroy(hpt_sppm *state);
+
 /* ---- multi-device fan-out inside the blocking call -----------------------------------------------
  * The reference's launch API is one blocking call per frame (run_cuda_pt -> pt_render_wrapper, reference
  * src/pt_cu_helper.cpp:66-77, src/pt_cu.cu:255-297, one device).  hpt_multi_* is the same call over the

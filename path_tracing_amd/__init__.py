@@ -124,9 +124,13 @@ def load_library() -> C.CDLL:
                      "hpt_device_count", "hpt_multi_create", "hpt_multi_num_devices", "hpt_multi_set_groups",
                      "hpt_multi_render_pt", "hpt_multi_render_bdpt", "hpt_multi_get_timing", "hpt_wrapper_set_devices",
                      "hpt_probe_functions", "hpt_tonemap", "hpt_tonemap_host", "hpt_bvh_export_host", "hpt_scene_export_bvh",
-                     "hpt_render_ppm", "hpt_ppm_get_stats", "hpt_ppm_render_wrapper"):
+                     "hpt_render_ppm", "hpt_ppm_get_stats", "hpt_ppm_render_wrapper",
+                     "hpt_sppm_create", "hpt_sppm_render", "hpt_sppm_reset", "hpt_sppm_read_state"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
+        if hasattr(lib, "hpt_sppm_destroy"):
+            lib.hpt_sppm_destroy.restype = None
+            lib.hpt_sppm_destroy.argtypes = [C.c_void_p]
         lib.hpt_scene_destroy.restype = None
         lib.hpt_wrapper_cache_clear.restype = None
         lib.hpt_wrapper_cache_clear.argtypes = []
@@ -249,6 +253,13 @@ class Scene:
         _check(self._lib.hpt_ppm_get_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def sppm(self, camera, W, H, eye_depth=4, light_depth=4, spl=8, radius=0.05, alpha=0.7, params: Params | None = None,
+             scene_min=None, scene_max=None) -> "Sppm":
+        """A progressive photon-mapping state on this scene (include/hpt.h, hpt_sppm_*): per-pixel radius, photon
+        count and flux that last across passes and calls.  params: seed, sample_offset, max_delta, tile (flags 0).
+        The scene must stay open while the state lives."""
+        return Sppm(self, camera, W, H, eye_depth, light_depth, spl, radius, alpha, params, scene_min, scene_max)
+
     def stats(self) -> dict:
         st = Stats()
         _check(self._lib.hpt_get_stats(self._h, C.byref(st)))
@@ -276,6 +287,57 @@ class Scene:
         vis = np.empty(n, np.int32)
         _check(self._lib.hpt_trace_visibility(self._h, _vp(a), _vp(b), n, FLAG_BRUTE_FORCE if brute_force else 0, _vp(vis)))
         return vis
+
+
+class Sppm:
+    """Progressive photon-mapping state (Scene.sppm).  render(passes) advances it and returns the estimate."""
+
+    def __init__(self, scene, camera, W, H, eye_depth, light_depth, spl, radius, alpha, params, scene_min, scene_max):
+        self._lib = scene._lib
+        self._scene = scene                 # the scene must outlive the state
+        self._h = C.c_void_p()
+        self.W, self.H = W, H
+        params = params or make_params()
+        cam = np.ascontiguousarray(camera, CAMERA)
+        mn = (C.c_float * 3)(*scene_min) if scene_min is not None else None
+        mx = (C.c_float * 3)(*scene_max) if scene_max is not None else None
+        _check(self._lib.hpt_sppm_create(scene._h, _vp(cam.reshape(1)), W, H, eye_depth, light_depth, spl, C.c_float(radius),
+                                         C.c_float(alpha), mn, mx, C.byref(params), C.byref(self._h)))
+
+    def render(self, passes=1, flags=0) -> np.ndarray:
+        """`passes` more passes; the estimate after them, float32 [H, W, 3] (flags: FLAG_TIME_KERNELS | FLAG_COUNT_WORK,
+        reported through Scene.ppm_stats)."""
+        img = np.empty((self.H, self.W, 3), np.float32)
+        _check(self._lib.hpt_sppm_render(self._h, int(passes), int(flags), _vp(img)))
+        return img
+
+    def reset(self):
+        _check(self._lib.hpt_sppm_reset(self._h))
+
+    def state(self) -> dict:
+        """dict(radius2 [H, W] f32, photons [H, W] f32, passes int)."""
+        r2 = np.empty((self.H, self.W), np.float32)
+        n = np.empty((self.H, self.W), np.float32)
+        k = C.c_int64()
+        _check(self._lib.hpt_sppm_read_state(self._h, _vp(r2), _vp(n), C.byref(k)))
+        return dict(radius2=r2, photons=n, passes=int(k.value))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.hpt_sppm_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class MultiScene:

@@ -6,10 +6,11 @@
 //   --max-depth N     eye depth (reference: EYE_DEPTH 4)  --obj FILE append an OBJ's faces (current material: 0.7 grey diffuse)
 //   --rr              optional unbiased Russian roulette (pt)
 //   --gpus N          render on N devices of this node inside the blocking call (image tiles, RCCL gather)
-//   --radius R        photon search radius of --mode ppm (reference: PPM_RADIUS 0.05)
-// --mode pt, bdpt and ppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
+//   --radius R        photon search radius of --mode ppm, initial radius of --mode sppm (reference: PPM_RADIUS 0.05)
+//   --alpha A         radius reduction of --mode sppm (default 0.7)
+// --mode pt, bdpt, ppm and sppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
 // reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
-// averaged, on one device.
+// averaged, on one device; sppm the same passes into one progressive state whose radius shrinks per pixel.
 #include "scene_model.hpp"
 #include "../../../include/hpt.h"
 
@@ -23,7 +24,7 @@
 #define LIGHT_DEPTH 4
 #define EYE_DEPTH 4
 
-namespace hpt_host { extern hpt_params g_run_params; extern bool g_seed_from_clock; extern int g_devices; extern float g_ppm_radius; }
+namespace hpt_host { extern hpt_params g_run_params; extern bool g_seed_from_clock; extern int g_devices; extern float g_ppm_radius; extern float g_sppm_alpha; }
 
 int main(int argc, char **argv){
     int spp = 8, spl = 8;
@@ -46,12 +47,13 @@ int main(int argc, char **argv){
         else if(arg == "--rr") hpt_host::g_run_params.flags |= HPT_FLAG_RUSSIAN_ROULETTE;
         else if(arg == "--gpus" && i + 1 < argc) hpt_host::g_devices = std::max(1, std::stoi(argv[++i]));
         else if(arg == "--radius" && i + 1 < argc) hpt_host::g_ppm_radius = std::stof(argv[++i]);
+        else if(arg == "--alpha" && i + 1 < argc) hpt_host::g_sppm_alpha = std::stof(argv[++i]);
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
                       << "  --spp <int>       Samples per pixel (default: 8)\n"
                       << "  --spl <int>       Samples per light (default: 8)\n"
-                      << "  --mode <string>   Render mode: pt, bdpt, ppm (default: pt)\n"
+                      << "  --mode <string>   Render mode: pt, bdpt, ppm, sppm (default: pt)\n"
                       << "  --device <string> Compute device: gpu (default: gpu)\n"
                       << "  --output <string> Output image path (.png or .pfm)\n"
                       << "  --input <string>  Input scene file\n"
@@ -61,7 +63,8 @@ int main(int argc, char **argv){
                       << "  --obj <file>      append the faces of a Wavefront OBJ\n"
                       << "  --rr              unbiased Russian roulette (pt mode; not in the reference, off by default)\n"
                       << "  --gpus <int>      devices of this node to render on (image tiles, RCCL gather; default: 1; pt and bdpt)\n"
-                      << "  --radius <float>  photon search radius of ppm mode (default: 0.05)\n";
+                      << "  --radius <float>  photon search radius of ppm mode, initial radius of sppm mode (default: 0.05)\n"
+                      << "  --alpha <float>   radius reduction of sppm mode, in (0, 1] (default: 0.7); --spp is its number of passes\n";
             return 0;
         }
     }
@@ -73,7 +76,7 @@ int main(int argc, char **argv){
     std::cout << " Input  : " << input_file << "\n";
     std::cout << " Output : " << output_file << "\n";
     std::cout << "====================================\n";
-    if(mode != "pt" && mode != "bdpt" && mode != "ppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm).\n"; return -1; }
+    if(mode != "pt" && mode != "bdpt" && mode != "ppm" && mode != "sppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm, sppm).\n"; return -1; }
 
     hpt_host::SceneFile scene;
     if(!hpt_host::parse_scene_file(input_file, scene)){
@@ -100,7 +103,7 @@ int main(int argc, char **argv){
 
     std::cout << "[Init] Transferring Data to the GPU...\n";
     if(mode == "bdpt") move_data_to_cuda_bdpt(scene.groups(), scene.lights, spl);
-    else if(mode == "ppm") move_data_to_cuda_ppm(scene.groups(), scene.lights, spl);
+    else if(mode == "ppm" || mode == "sppm") move_data_to_cuda_ppm(scene.groups(), scene.lights, spl);
     else move_data_to_cuda_pt(scene.groups(), scene.lights, spl);
     if(seed >= 0){ hpt_host::g_seed_from_clock = false; hpt_host::g_run_params.seed = (uint64_t) seed; }
 
@@ -108,6 +111,7 @@ int main(int argc, char **argv){
     auto start_time = std::chrono::steady_clock::now();
     if(mode == "bdpt") run_cuda_bdpt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp, spl);
     else if(mode == "ppm") run_cuda_ppm(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
+    else if(mode == "sppm") run_cuda_sppm(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
     else run_cuda_pt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
     std::cout << "\n";
     auto diff = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - start_time);

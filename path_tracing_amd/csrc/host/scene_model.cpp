@@ -358,6 +358,7 @@ hpt_params g_run_params = { 1, 0, 0, 0, 0, 0, 0, 0, 0 };
 bool g_seed_from_clock = true;
 int g_devices = 1;            // devices the helper API renders on (pt_cli --gpus): > 1 = fan-out inside the blocking call
 float g_ppm_radius = 0.05f;   // search radius of run_cuda_ppm (pt_cli --radius; the reference's PPM_RADIUS)
+float g_sppm_alpha = 0.7f;    // radius reduction of run_cuda_sppm (pt_cli --alpha)
 
 } // namespace hpt_host
 
@@ -454,6 +455,19 @@ void run_cuda_ppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye
     int rc = hpt_render_ppm(g_ppm.device, &cam, W, H, eye_depth, light_depth, spp, g_ppm.light_sample, hpt_host::g_ppm_radius, nullptr, nullptr,
                             &p, &image_buffer->x);
     if(rc != HPT_OK) std::cerr << "run_cuda_ppm: " << hpt_last_error() << std::endl;
+}
+
+void run_cuda_sppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int passes){
+    if(!g_ppm.device){ std::cerr << "run_cuda_sppm: no scene moved to the device" << std::endl; return; }
+    hpt_params p = run_params();
+    const int32_t flags = p.flags & (HPT_FLAG_TIME_KERNELS | HPT_FLAG_COUNT_WORK);
+    p.flags = 0;
+    hpt_sppm *state = nullptr;
+    int rc = hpt_sppm_create(g_ppm.device, &cam, W, H, eye_depth, light_depth, g_ppm.light_sample, hpt_host::g_ppm_radius,
+                             hpt_host::g_sppm_alpha, nullptr, nullptr, &p, &state);
+    if(rc == HPT_OK) rc = hpt_sppm_render(state, passes, flags, &image_buffer->x);
+    if(rc != HPT_OK) std::cerr << "run_cuda_sppm: " << hpt_last_error() << std::endl;
+    hpt_sppm_destroy(state);
 }
 
 // ---- C entry points (tests, Python: scene_io.load_scene_fast / load_obj) ---------------------------------------

@@ -127,3 +127,6 @@ void run_cuda_bdpt(CudaCamera cam, float3 *image_buffer, int light_depth, int ey
 // per light (the reference renders one pass per call and ignores spp); one device.
 void move_data_to_cuda_ppm(std::map<int, hpt_host::AABB> groups, std::vector<CudaLight> &cuda_lights, int light_sample);
 void run_cuda_ppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int spp);
+// Progressive photon mapping on the scene moved by move_data_to_cuda_ppm: one state (hpt_sppm_*), `passes` passes of
+// `light_sample` photons per light, initial radius hpt_host::g_ppm_radius, alpha hpt_host::g_sppm_alpha; one device.
+void run_cuda_sppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int passes);

@@ -769,46 +769,43 @@ void ppm_scene_bounds(hpt_scene *s){
 
 constexpr int32_t kPpmFlags = HPT_FLAG_OUTPUT_SUM | HPT_FLAG_TIME_KERNELS | HPT_FLAG_COUNT_WORK;
 
-// the photon-mapping render (reference src/ppm_cu.cu:328-400, `spp` passes), blocking, whole image into host_image
-int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl, float radius,
-               const float *scene_min, const float *scene_max, const hpt_params *params, float *host_image){
-    if(!s) return fail(HPT_ERR_INVALID, "null scene");
-    if(!camera || !host_image) return fail(HPT_ERR_INVALID, "null camera or image");
-    if(spp <= 0 || spl < 0 || eye_depth <= 0 || eye_depth > 255 || light_depth <= 0 || light_depth > 255)
-        return fail(HPT_ERR_INVALID, "spp must be > 0, spl >= 0 and depths in [1, 255]");
-    if(int rcd = on_scene_device(s)) return rcd;
-    hpt_params P; memset(&P, 0, sizeof P);
-    if(params) P = *params;
-    if(P.world > 1) return fail(HPT_ERR_INVALID, "hpt_render_ppm renders the whole image on one device: world must be 0 or 1");
-    if(P.flags & ~kPpmFlags) return fail(HPT_ERR_INVALID, "hpt_render_ppm accepts HPT_FLAG_OUTPUT_SUM, TIME_KERNELS and COUNT_WORK only");
-    if(P.reserved) return fail(HPT_ERR_INVALID, "hpt_params.reserved must be zero for hpt_render_ppm");
-    if(P.max_delta <= 0) P.max_delta = 64;
-    if(P.max_delta > 250) P.max_delta = 250;
-    Tiling tl;
-    int rc = make_tiling(W, H, &P, tl);
-    if(rc) return rc;
-    if(!(radius > 0.0f)) radius = 0.05f;                                    // PPM_RADIUS, include/ppm_cu.cuh:4
-    PpmFrame fr;
-    ppm_scene_bounds(s);
-    for(int a = 0; a < 3; ++a){ fr.smin[a] = scene_min ? scene_min[a] : s->ppm_min[a]; fr.smax[a] = scene_max ? scene_max[a] : s->ppm_max[a]; }
-    fr.cell = radius; fr.r2 = radius * radius;
+// What the passes of one photon-mapping render share (render_ppm, sppm_render).  The caller fills P (max_delta
+// clamped), tl, cam and fr (bounds, cell, r2); ppm_prepare sizes the rest and grows the scene's PPM workspace.
+struct PpmRun {
+    hpt_params P; Tiling tl; CameraDev cam; PpmFrame fr;
+    int light_depth = 0, spl = 0, eye_iters = 0, ph_iters = 0, M = 0, n_counters = 0;
+    uint64_t n_ph64 = 0; uint32_t n_ph = 0, n_dep = 0, n_local = 0, buckets = 0;
+    bool count = false, timek = false;
+    uint32_t *hp_count(const hpt_scene *s) const { return s->pass[0].counters + 4 * M; }
+};
 
-    const uint64_t n_ph64 = s->nl > 0 ? (uint64_t) s->nl * (uint64_t) spl : 0u;
-    const uint64_t n_dep64 = n_ph64 * (uint64_t) light_depth;
+void set_camera(CameraDev &cam, const void *camera){
+    const float *cf = (const float *) camera;
+    memcpy(cam.eye, cf + 0, 12); memcpy(cam.UL, cf + 12, 12); memcpy(cam.dx, cf + 15, 12); memcpy(cam.dy, cf + 18, 12);
+}
+
+// `passes`: how many passes the call renders (TIME_KERNELS: five events each)
+int ppm_prepare(hpt_scene *s, PpmRun &r, int light_depth, int spl, int passes){
+    const hpt_params &P = r.P;
+    r.light_depth = light_depth; r.spl = spl;
+    r.n_ph64 = s->nl > 0 ? (uint64_t) s->nl * (uint64_t) spl : 0u;
+    const uint64_t n_dep64 = r.n_ph64 * (uint64_t) light_depth;
     if(n_dep64 > (1ull << 30))
         return fail(HPT_ERR_NOMEM, "num_lights * spl * light_depth photon deposits do not fit (at most 2^30 per pass)");
-    const uint32_t n_ph = (uint32_t) n_ph64, n_dep = (uint32_t) n_dep64;
+    const uint32_t n_ph = (uint32_t) r.n_ph64, n_dep = (uint32_t) n_dep64;
     uint32_t buckets = 1024u;
     while(buckets < 2u * n_dep) buckets <<= 1;
-    fr.buckets = buckets;
-    const uint32_t n_local = (uint32_t) tl.n_local;
+    r.fr.buckets = buckets;
+    r.n_ph = n_ph; r.n_dep = n_dep; r.buckets = buckets;
+    const uint32_t n_local = (uint32_t) r.tl.n_local;
+    r.n_local = n_local;
     const size_t paths = std::max<size_t>(n_local, n_ph);
-    const int eye_iters = 1 + P.max_delta, ph_iters = light_depth + P.max_delta;
-    const int M = std::max(eye_iters, ph_iters) + 2;
-    const int n_counters = 4 * M + 2;
-    rc = ensure_workspace(s, paths, tl.n_local, n_counters);
+    r.eye_iters = 1 + P.max_delta; r.ph_iters = light_depth + P.max_delta;
+    r.M = std::max(r.eye_iters, r.ph_iters) + 2;
+    r.n_counters = 4 * r.M + 2;
+    int rc = ensure_workspace(s, paths, r.tl.n_local, r.n_counters);
     if(rc) return rc;
-    const bool count = (P.flags & HPT_FLAG_COUNT_WORK) != 0, timek = (P.flags & HPT_FLAG_TIME_KERNELS) != 0;
+    r.count = (P.flags & HPT_FLAG_COUNT_WORK) != 0; r.timek = (P.flags & HPT_FLAG_TIME_KERNELS) != 0;
     if(n_local > s->ppm_cap_hp){
         size_t c;
         c = s->ppm_cap_hp; rc = grow(&s->hb.pos_mat, c, n_local); if(rc) return rc;
@@ -818,7 +815,7 @@ int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, in
         c = s->ppm_cap_hp; rc = grow(&s->hb.list, c, n_local); if(rc) return rc;
         s->ppm_cap_hp = n_local;
     }
-    if(count && n_local > s->ppm_cap_count){
+    if(r.count && n_local > s->ppm_cap_count){
         size_t c = s->ppm_cap_count; rc = grow(&s->ppm_cand, c, n_local); if(rc) return rc;
         c = s->ppm_cap_count; rc = grow(&s->ppm_acc, c, n_local); if(rc) return rc;
         s->ppm_cap_count = n_local;
@@ -839,16 +836,26 @@ int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, in
     { size_t c = s->ppm_cap_tmp; rc = grow((unsigned char **) &s->grid.sort_tmp, c, tmp); if(rc) return rc; s->ppm_cap_tmp = c; }
     s->grid.sort_tmp_bytes = tmp; s->grid.buckets = buckets;
     if(!s->d_pc) HIP_TRY(hipMalloc((void **) &s->d_pc, sizeof(PpmCounters)));
-    { size_t c = s->cap_local_own; rc = grow(&s->d_local_own, c, (size_t) tl.n_local * 3); if(rc) return rc; s->cap_local_own = c; }
-    { size_t c = s->cap_image_own; rc = grow(&s->d_image_own, c, (size_t) W * H * 3); if(rc) return rc; s->cap_image_own = c; }
+    { size_t c = s->cap_local_own; rc = grow(&s->d_local_own, c, (size_t) r.tl.n_local * 3); if(rc) return rc; s->cap_local_own = c; }
+    { size_t c = s->cap_image_own; rc = grow(&s->d_image_own, c, (size_t) r.tl.W * r.tl.H * 3); if(rc) return rc; s->cap_image_own = c; }
+    const size_t n_marks = r.timek ? (size_t) passes * 5 : 0;
+    while(s->ppm_marks.size() < n_marks){ hipEvent_t e; HIP_TRY(hipEventCreate(&e)); s->ppm_marks.push_back(e); }
+    return HPT_OK;
+}
 
-    const float *cf = (const float *) camera;
-    CameraDev cam;
-    memcpy(cam.eye, cf + 0, 12); memcpy(cam.UL, cf + 12, 12); memcpy(cam.dx, cf + 15, 12); memcpy(cam.dy, cf + 18, 12);
+void ppm_mark(hpt_scene *s, const PpmRun &r, int pass, int k){ if(r.timek) hipEventRecord(s->ppm_marks[(size_t) pass * 5 + k], nullptr); }
+
+// The eye, photon and grid phases of photon-mapping pass `pidx`, marks 0-3 of the call's pass `pass`: the hit points
+// in s->hb (their number in r.hp_count(s)), the direct terms in pass[0].pb.col, the deposits' grid in s->grid.
+int ppm_phases(hpt_scene *s, const PpmRun &r, int pass, uint32_t pidx){
+    const hpt_params &P = r.P;
+    const PpmFrame &fr = r.fr;
+    const uint32_t n_local = r.n_local, n_ph = r.n_ph, n_dep = r.n_dep;
+    const int M = r.M, light_depth = r.light_depth;
     hipStream_t st = nullptr;
     PassBuffers &w = s->pass[0];
     uint32_t *eq = w.counters, *elc = w.counters + M, *pq = w.counters + 2 * M, *plc = w.counters + 3 * M;
-    uint32_t *hp_count = w.counters + 4 * M, *no_shadow = w.counters + 4 * M + 1;
+    uint32_t *hp_count = r.hp_count(s), *no_shadow = w.counters + 4 * M + 1;
     const int budget = resume_walk_fits(s->sd) ? kTraceBudget : 0;
     // closest-hit rays of the queue in cnt[it] (it = 0: the identity queue), the PT path's split trace step
     auto trace = [&](int it, const uint32_t *queue, uint32_t *cnt, uint32_t *lcnt, uint32_t max_items){
@@ -863,78 +870,62 @@ int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, in
         empty = *w.h_count == 0u;
         return HPT_OK;
     };
-    const size_t n_marks = timek ? (size_t) spp * 5 : 0;
-    while(s->ppm_marks.size() < n_marks){ hipEvent_t e; HIP_TRY(hipEventCreate(&e)); s->ppm_marks.push_back(e); }
-    auto mark = [&](int pass, int k){ if(timek) hipEventRecord(s->ppm_marks[(size_t) pass * 5 + k], st); };
-
-    HIP_TRY(hipMemsetAsync(s->d_pc, 0, sizeof(PpmCounters), st));
-    HIP_TRY(hipMemsetAsync(s->accum, 0, (size_t) tl.n_local * sizeof(float4), st));
-    if(n_dep) launch_ppm_iota(st, s->grid.slot_in, n_dep);
-    HIP_TRY(hipEventRecord(s->ev_start, st));
-    for(int pass = 0; pass < spp; ++pass){
-        const uint32_t pidx = (uint32_t) (P.sample_offset + pass);
-        HIP_TRY(hipMemsetAsync(w.counters, 0, (size_t) n_counters * sizeof(uint32_t), st));
-        mark(pass, 0);
-        // eye pass: slot = local pixel, stream (seed ^ kPpmEyeKey, pixel, pass), jitter first
-        launch_generate(st, tl, cam, w.pb, &eq[0], 1, pidx, P.seed ^ kPpmEyeKey, nullptr);
-        int cur = 0;
-        for(int it = 0; it < eye_iters; ++it){
-            if(it >= 1){ bool empty; if(int r = queue_empty(&eq[it], empty)) return r; if(empty) break; }
+    HIP_TRY(hipMemsetAsync(w.counters, 0, (size_t) r.n_counters * sizeof(uint32_t), st));
+    ppm_mark(s, r, pass, 0);
+    // eye pass: slot = local pixel, stream (seed ^ kPpmEyeKey, pixel, pass), jitter first
+    launch_generate(st, r.tl, r.cam, w.pb, &eq[0], 1, pidx, P.seed ^ kPpmEyeKey, nullptr);
+    int cur = 0;
+    for(int it = 0; it < r.eye_iters; ++it){
+        if(it >= 1){ bool empty; if(int rc = queue_empty(&eq[it], empty)) return rc; if(empty) break; }
+        const uint32_t *q = it == 0 ? nullptr : w.queue[cur];
+        trace(it, q, eq, elc, n_local);
+        launch_ppm_eye_shade(st, s->sd, w.pb, s->hb, q, &eq[it], n_local, w.queue[cur ^ 1], &eq[it + 1], hp_count, P.max_delta, s->d_pc);
+        cur ^= 1;
+    }
+    ppm_mark(s, r, pass, 1);
+    if(n_ph){
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) s->grid.key, (int) r.buckets, n_dep, st));
+        launch_ppm_emit(st, s->sd, w.pb, &pq[0], n_ph, r.spl, P.seed, pidx, fr);
+        cur = 0;
+        for(int it = 0; it < r.ph_iters; ++it){
+            if(it >= light_depth){ bool empty; if(int rc = queue_empty(&pq[it], empty)) return rc; if(empty) break; }
             const uint32_t *q = it == 0 ? nullptr : w.queue[cur];
-            trace(it, q, eq, elc, n_local);
-            launch_ppm_eye_shade(st, s->sd, w.pb, s->hb, q, &eq[it], n_local, w.queue[cur ^ 1], &eq[it + 1], hp_count, P.max_delta, s->d_pc);
+            trace(it, q, pq, plc, n_ph);
+            launch_ppm_photon_shade(st, s->sd, w.pb, s->grid, q, &pq[it], n_ph, w.queue[cur ^ 1], &pq[it + 1], light_depth,
+                                    P.max_delta, fr, s->d_pc);
             cur ^= 1;
         }
-        mark(pass, 1);
-        if(n_ph){
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) s->grid.key, (int) buckets, n_dep, st));
-            launch_ppm_emit(st, s->sd, w.pb, &pq[0], n_ph, spl, P.seed, pidx, fr);
-            cur = 0;
-            for(int it = 0; it < ph_iters; ++it){
-                if(it >= light_depth){ bool empty; if(int r = queue_empty(&pq[it], empty)) return r; if(empty) break; }
-                const uint32_t *q = it == 0 ? nullptr : w.queue[cur];
-                trace(it, q, pq, plc, n_ph);
-                launch_ppm_photon_shade(st, s->sd, w.pb, s->grid, q, &pq[it], n_ph, w.queue[cur ^ 1], &pq[it + 1], light_depth,
-                                        P.max_delta, fr, s->d_pc);
-                cur ^= 1;
-            }
-        }
-        mark(pass, 2);
-        HIP_TRY(hipMemsetAsync(s->grid.range, 0, (size_t) buckets * sizeof(uint2), st));
-        if(n_dep && launch_ppm_grid(st, s->grid, n_dep)) return fail(HPT_ERR_DEVICE, "photon grid: radix sort launch failed");
-        mark(pass, 3);
-        launch_ppm_gather(st, s->sd, w.pb, s->hb, s->grid, hp_count, n_local, fr, count ? s->ppm_cand : nullptr,
-                          count ? s->ppm_acc : nullptr, s->d_pc);
-        launch_resolve(st, tl, w.pb, s->accum, 1);
-        mark(pass, 4);
     }
-    launch_finalize(st, tl, s->accum, s->d_local_own, (P.flags & HPT_FLAG_OUTPUT_SUM) ? 1.0f : (float) spp);
-    launch_untile(st, tl, s->d_local_own, s->d_image_own);
-    HIP_TRY(hipEventRecord(s->ev_stop, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(host_image, s->d_image_own, (size_t) W * H * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    ppm_mark(s, r, pass, 2);
+    HIP_TRY(hipMemsetAsync(s->grid.range, 0, (size_t) r.buckets * sizeof(uint2), st));
+    if(n_dep && launch_ppm_grid(st, s->grid, n_dep)) return fail(HPT_ERR_DEVICE, "photon grid: radix sort launch failed");
+    ppm_mark(s, r, pass, 3);
+    return HPT_OK;
+}
 
-    // statistics of this render (the call is blocking anyway)
+// statistics of a finished render of `passes` passes (blocking) into s->ppm_stats
+int ppm_collect_stats(hpt_scene *s, const PpmRun &r, int passes){
     hpt_ppm_stats &ps = s->ppm_stats;
     memset(&ps, 0, sizeof ps);
     PpmCounters pc;
     HIP_TRY(hipMemcpy(&pc, s->d_pc, sizeof pc, hipMemcpyDeviceToHost));
-    ps.photons = n_ph64 * (uint64_t) spp; ps.photon_rays = pc.photon_rays; ps.deposits = pc.deposits;
+    ps.photons = r.n_ph64 * (uint64_t) passes; ps.photon_rays = pc.photon_rays; ps.deposits = pc.deposits;
     ps.hit_points = pc.hit_points; ps.direct_pixels = pc.direct; ps.candidates = pc.candidates; ps.accepted = pc.accepted;
-    ps.grid_buckets = buckets;
+    ps.grid_buckets = r.buckets;
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
     ps.ms_total = ms;
-    if(timek){
+    if(r.timek){
         double *phase[4] = { &ps.ms_eye, &ps.ms_photon, &ps.ms_grid, &ps.ms_gather };
-        for(int pass = 0; pass < spp; ++pass) for(int k = 0; k < 4; ++k){
+        for(int pass = 0; pass < passes; ++pass) for(int k = 0; k < 4; ++k){
             float e = 0.0f;
             if(hipEventElapsedTime(&e, s->ppm_marks[(size_t) pass * 5 + k], s->ppm_marks[(size_t) pass * 5 + k + 1]) == hipSuccess) *phase[k] += e;
         }
     }
-    if(count){
+    if(r.count){
+        const uint32_t n_local = r.n_local;
         uint32_t nhp = 0;
-        HIP_TRY(hipMemcpy(&nhp, hp_count, sizeof nhp, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&nhp, r.hp_count(s), sizeof nhp, hipMemcpyDeviceToHost));
         std::vector<uint32_t> list(nhp), cand(n_local), acc(n_local);
         if(nhp){
             HIP_TRY(hipMemcpy(list.data(), s->hb.list, (size_t) nhp * 4, hipMemcpyDeviceToHost));
@@ -948,10 +939,196 @@ int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, in
         }
     }
     // hpt_get_stats after this render reports its total time only
-    s->timed.clear(); s->event_next = 0; s->last_counter_stride = 0; s->last_budget = 0; s->last_flags = P.flags;
+    s->timed.clear(); s->event_next = 0; s->last_counter_stride = 0; s->last_budget = 0; s->last_flags = r.P.flags;
     s->stats.ms_extend = s->stats.ms_shade = s->stats.ms_connect = s->stats.ms_other = 0.0;
     s->stats.n_extend = s->stats.n_shade = s->stats.n_connect = s->stats.n_other = 0;
     s->ev_valid = true; s->stats_pending = true;
+    return HPT_OK;
+}
+
+// the photon-mapping render (reference src/ppm_cu.cu:328-400, `spp` passes), blocking, whole image into host_image
+int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl, float radius,
+               const float *scene_min, const float *scene_max, const hpt_params *params, float *host_image){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(!camera || !host_image) return fail(HPT_ERR_INVALID, "null camera or image");
+    if(spp <= 0 || spl < 0 || eye_depth <= 0 || eye_depth > 255 || light_depth <= 0 || light_depth > 255)
+        return fail(HPT_ERR_INVALID, "spp must be > 0, spl >= 0 and depths in [1, 255]");
+    if(int rcd = on_scene_device(s)) return rcd;
+    PpmRun r;
+    hpt_params &P = r.P;
+    memset(&P, 0, sizeof P);
+    if(params) P = *params;
+    if(P.world > 1) return fail(HPT_ERR_INVALID, "hpt_render_ppm renders the whole image on one device: world must be 0 or 1");
+    if(P.flags & ~kPpmFlags) return fail(HPT_ERR_INVALID, "hpt_render_ppm accepts HPT_FLAG_OUTPUT_SUM, TIME_KERNELS and COUNT_WORK only");
+    if(P.reserved) return fail(HPT_ERR_INVALID, "hpt_params.reserved must be zero for hpt_render_ppm");
+    if(P.max_delta <= 0) P.max_delta = 64;
+    if(P.max_delta > 250) P.max_delta = 250;
+    int rc = make_tiling(W, H, &P, r.tl);
+    if(rc) return rc;
+    if(!(radius > 0.0f)) radius = 0.05f;                                    // PPM_RADIUS, include/ppm_cu.cuh:4
+    PpmFrame &fr = r.fr;
+    ppm_scene_bounds(s);
+    for(int a = 0; a < 3; ++a){ fr.smin[a] = scene_min ? scene_min[a] : s->ppm_min[a]; fr.smax[a] = scene_max ? scene_max[a] : s->ppm_max[a]; }
+    fr.cell = radius; fr.r2 = radius * radius;
+    set_camera(r.cam, camera);
+    rc = ppm_prepare(s, r, light_depth, spl, spp);
+    if(rc) return rc;
+
+    hipStream_t st = nullptr;
+    PassBuffers &w = s->pass[0];
+    const Tiling &tl = r.tl;
+    HIP_TRY(hipMemsetAsync(s->d_pc, 0, sizeof(PpmCounters), st));
+    HIP_TRY(hipMemsetAsync(s->accum, 0, (size_t) tl.n_local * sizeof(float4), st));
+    if(r.n_dep) launch_ppm_iota(st, s->grid.slot_in, r.n_dep);
+    HIP_TRY(hipEventRecord(s->ev_start, st));
+    for(int pass = 0; pass < spp; ++pass){
+        rc = ppm_phases(s, r, pass, (uint32_t) (P.sample_offset + pass));
+        if(rc) return rc;
+        launch_ppm_gather(st, s->sd, w.pb, s->hb, s->grid, r.hp_count(s), r.n_local, fr, r.count ? s->ppm_cand : nullptr,
+                          r.count ? s->ppm_acc : nullptr, s->d_pc);
+        launch_resolve(st, tl, w.pb, s->accum, 1);
+        ppm_mark(s, r, pass, 4);
+    }
+    launch_finalize(st, tl, s->accum, s->d_local_own, (P.flags & HPT_FLAG_OUTPUT_SUM) ? 1.0f : (float) spp);
+    launch_untile(st, tl, s->d_local_own, s->d_image_own);
+    HIP_TRY(hipEventRecord(s->ev_stop, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(host_image, s->d_image_own, (size_t) W * H * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return ppm_collect_stats(s, r, spp);
+}
+
+} // namespace
+
+// Progressive photon mapping (include/hpt.h, hpt_sppm_*): the per-pixel state of one (scene, camera, image) lives
+// here, not in the scene's workspace, so renders of other kinds on the same scene in between leave it alone.
+struct hpt_sppm {
+    hpt_scene *scene = nullptr;
+    unsigned char camera[HPT_CAMERA_BYTES];
+    int W = 0, H = 0, eye_depth = 0, light_depth = 0, spl = 0;
+    float radius = 0.05f, alpha = 1.0f;
+    float smin[3] = { 0, 0, 0 }, smax[3] = { 0, 0, 0 };
+    hpt_params P{};                  // seed, sample_offset, max_delta (clamped), tile
+    Tiling tl{};
+    int64_t passes = 0;              // K
+    SppmState st{};
+    float *d_local = nullptr, *d_image = nullptr;   // hpt_sppm_read_state's untile
+};
+
+namespace {
+
+int sppm_reset(hpt_sppm *z){
+    if(int rcd = on_scene_device(z->scene)) return rcd;
+    launch_sppm_init(nullptr, z->st, (uint32_t) z->tl.n_local, z->radius * z->radius);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    z->passes = 0;
+    return HPT_OK;
+}
+
+void sppm_free(hpt_sppm *z){
+    hipFree(z->st.tau_r2); hipFree(z->st.photons); hipFree(z->st.direct); hipFree(z->d_local); hipFree(z->d_image);
+    delete z;
+}
+
+int sppm_create(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int light_depth, int spl, float radius, float alpha,
+                const float *scene_min, const float *scene_max, const hpt_params *params, hpt_sppm **out){
+    if(!out) return fail(HPT_ERR_INVALID, "null out");
+    *out = nullptr;
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(!camera) return fail(HPT_ERR_INVALID, "null camera");
+    if(spl < 0 || eye_depth <= 0 || eye_depth > 255 || light_depth <= 0 || light_depth > 255)
+        return fail(HPT_ERR_INVALID, "spl must be >= 0 and depths in [1, 255]");
+    if(!(alpha > 0.0f && alpha <= 1.0f)) return fail(HPT_ERR_INVALID, "alpha must be in (0, 1]");
+    if(int rcd = on_scene_device(s)) return rcd;
+    hpt_params P; memset(&P, 0, sizeof P);
+    if(params) P = *params;
+    if(P.world > 1) return fail(HPT_ERR_INVALID, "progressive photon mapping renders the whole image on one device: world must be 0 or 1");
+    if(P.flags) return fail(HPT_ERR_INVALID, "hpt_sppm_create: hpt_params.flags must be zero (render flags go to hpt_sppm_render)");
+    if(P.reserved) return fail(HPT_ERR_INVALID, "hpt_params.reserved must be zero for progressive photon mapping");
+    if(P.max_delta <= 0) P.max_delta = 64;
+    if(P.max_delta > 250) P.max_delta = 250;
+    Tiling tl;
+    int rc = make_tiling(W, H, &P, tl);
+    if(rc) return rc;
+    if(!(radius > 0.0f)) radius = 0.05f;
+    hpt_sppm *z = new (std::nothrow) hpt_sppm;
+    if(!z) return fail(HPT_ERR_NOMEM, "out of host memory");
+    z->scene = s; memcpy(z->camera, camera, HPT_CAMERA_BYTES);
+    z->W = W; z->H = H; z->eye_depth = eye_depth; z->light_depth = light_depth; z->spl = spl;
+    z->radius = radius; z->alpha = alpha; z->P = P; z->tl = tl;
+    ppm_scene_bounds(s);
+    for(int a = 0; a < 3; ++a){ z->smin[a] = scene_min ? scene_min[a] : s->ppm_min[a]; z->smax[a] = scene_max ? scene_max[a] : s->ppm_max[a]; }
+    const size_t n = (size_t) tl.n_local;
+    hipError_t e = hipMalloc((void **) &z->st.tau_r2, n * sizeof(float4));
+    if(e == hipSuccess) e = hipMalloc((void **) &z->st.photons, n * sizeof(float));
+    if(e == hipSuccess) e = hipMalloc((void **) &z->st.direct, n * sizeof(float4));
+    if(e == hipSuccess) e = hipMalloc((void **) &z->d_local, n * 3 * sizeof(float));
+    if(e == hipSuccess) e = hipMalloc((void **) &z->d_image, (size_t) W * H * 3 * sizeof(float));
+    if(e != hipSuccess){
+        sppm_free(z);
+        return fail(e == hipErrorOutOfMemory ? HPT_ERR_NOMEM : HPT_ERR_DEVICE, std::string("progressive photon map state: ") + hipGetErrorString(e));
+    }
+    rc = sppm_reset(z);
+    if(rc){ sppm_free(z); return rc; }
+    *out = z;
+    return HPT_OK;
+}
+
+constexpr int32_t kSppmFlags = HPT_FLAG_TIME_KERNELS | HPT_FLAG_COUNT_WORK;
+
+// `passes` more passes of PPM's estimator into the state, then the estimate into host_image (blocking)
+int sppm_render(hpt_sppm *z, int passes, int32_t flags, float *host_image){
+    if(!z) return fail(HPT_ERR_INVALID, "null state");
+    if(!host_image) return fail(HPT_ERR_INVALID, "null image");
+    if(passes <= 0) return fail(HPT_ERR_INVALID, "passes must be > 0");
+    if(flags & ~kSppmFlags) return fail(HPT_ERR_INVALID, "hpt_sppm_render accepts HPT_FLAG_TIME_KERNELS and COUNT_WORK only");
+    hpt_scene *s = z->scene;
+    if(int rcd = on_scene_device(s)) return rcd;
+    PpmRun r;
+    r.P = z->P; r.P.flags = flags; r.tl = z->tl;
+    set_camera(r.cam, z->camera);
+    for(int a = 0; a < 3; ++a){ r.fr.smin[a] = z->smin[a]; r.fr.smax[a] = z->smax[a]; }
+    r.fr.cell = z->radius; r.fr.r2 = z->radius * z->radius;             // the cell stays the initial radius
+    int rc = ppm_prepare(s, r, z->light_depth, z->spl, passes);
+    if(rc) return rc;
+
+    hipStream_t st = nullptr;
+    PassBuffers &w = s->pass[0];
+    HIP_TRY(hipMemsetAsync(s->d_pc, 0, sizeof(PpmCounters), st));
+    if(r.n_dep) launch_ppm_iota(st, s->grid.slot_in, r.n_dep);
+    HIP_TRY(hipEventRecord(s->ev_start, st));
+    for(int pass = 0; pass < passes; ++pass){
+        rc = ppm_phases(s, r, pass, (uint32_t) ((int64_t) r.P.sample_offset + z->passes + pass));
+        if(rc) return rc;
+        launch_sppm_gather(st, s->sd, s->hb, s->grid, r.hp_count(s), r.n_local, r.fr, z->st, z->alpha,
+                           r.count ? s->ppm_cand : nullptr, r.count ? s->ppm_acc : nullptr, s->d_pc);
+        launch_resolve(st, r.tl, w.pb, z->st.direct, 1);                  // D += the guarded direct term
+        ppm_mark(s, r, pass, 4);
+    }
+    z->passes += passes;
+    launch_sppm_estimate(st, r.tl, z->st, (float) z->passes, s->d_local_own);
+    launch_untile(st, r.tl, s->d_local_own, s->d_image_own);
+    HIP_TRY(hipEventRecord(s->ev_stop, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(host_image, s->d_image_own, (size_t) z->W * z->H * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return ppm_collect_stats(s, r, passes);
+}
+
+int sppm_read_state(const hpt_sppm *z, float *radius2, float *photons, int64_t *passes){
+    if(!z) return fail(HPT_ERR_INVALID, "null state");
+    if(passes) *passes = z->passes;
+    if(!radius2 && !photons) return HPT_OK;
+    if(int rcd = on_scene_device(z->scene)) return rcd;
+    launch_sppm_state(nullptr, z->tl, z->st, z->d_local);
+    launch_untile(nullptr, z->tl, z->d_local, z->d_image);
+    HIP_TRY(hipGetLastError());
+    const size_t npx = (size_t) z->W * z->H;
+    std::vector<float> img(npx * 3);
+    HIP_TRY(hipMemcpy(img.data(), z->d_image, npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    for(size_t k = 0; k < npx; ++k){
+        if(radius2) radius2[k] = img[k * 3 + 0];
+        if(photons) photons[k] = img[k * 3 + 1];
+    }
     return HPT_OK;
 }
 
@@ -1426,6 +1603,28 @@ int hpt_ppm_get_stats(const hpt_scene *s, hpt_ppm_stats *out){
     if(!s || !out) return fail(HPT_ERR_INVALID, "null argument");
     *out = s->ppm_stats;
     return HPT_OK;
+}
+
+int hpt_sppm_create(hpt_scene *s, const void *camera, int W, int H, int eye_depth, int light_depth, int spl, float radius, float alpha,
+                    const float *scene_min, const float *scene_max, const hpt_params *params, hpt_sppm **out){
+    return sppm_create(s, camera, W, H, eye_depth, light_depth, spl, radius, alpha, scene_min, scene_max, params, out);
+}
+
+int hpt_sppm_render(hpt_sppm *state, int passes, int32_t flags, float *host_image){
+    return sppm_render(state, passes, flags, host_image);
+}
+
+int hpt_sppm_reset(hpt_sppm *state){
+    if(!state) return fail(HPT_ERR_INVALID, "null state");
+    return sppm_reset(state);
+}
+
+int hpt_sppm_read_state(const hpt_sppm *state, float *radius2, float *photons, int64_t *passes){
+    return sppm_read_state(state, radius2, photons, passes);
+}
+
+void hpt_sppm_destroy(hpt_sppm *state){
+    if(state) sppm_free(state);
 }
 
 int hpt_ppm_render_wrapper(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt,

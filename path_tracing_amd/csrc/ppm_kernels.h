@@ -64,4 +64,22 @@ void launch_ppm_gather(hipStream_t s, const SceneDev &sc, PathBuf pb, PpmHitBuf 
                        uint32_t max_items, PpmFrame fr, uint32_t *cand, uint32_t *acc, PpmCounters *pc);
 void launch_ppm_iota(hipStream_t s, uint32_t *p, uint32_t n);
 
+// Progressive photon mapping (hpt_sppm, DESIGN.md "Progressive photon mapping"): per local pixel state that lasts
+// across passes and calls.  The passes are PPM's (eye, photon, grid); only the gather and the image differ.
+struct SppmState {
+    float4 *tau_r2;      // accumulated flux tau xyz | squared radius R2
+    float *photons;      // N
+    float4 *direct;      // D, the sum of the guarded direct terms xyz | 0
+};
+// tau = 0, R2 = r2, N = 0, D = 0 for every local pixel
+void launch_sppm_init(hipStream_t s, SppmState st, uint32_t n_local, float r2);
+// one lane per hit point: the cells its sphere (R2 of its pixel) can reach, summed in PPM's order, and the pixel's
+// update (alpha); cand / acc as launch_ppm_gather's.  fr.cell is the grid cell; fr.r2 is not read.
+void launch_sppm_gather(hipStream_t s, const SceneDev &sc, PpmHitBuf hb, PpmGrid g, const uint32_t *hp_count, uint32_t max_items,
+                        PpmFrame fr, SppmState st, float alpha, uint32_t *cand, uint32_t *acc, PpmCounters *pc);
+// d_local[p] = the estimate after `passes` passes (divided when passes != 1)
+void launch_sppm_estimate(hipStream_t s, const Tiling &tl, SppmState st, float passes, float *d_local);
+// d_local[p] = (R2, N, 0), for launch_untile
+void launch_sppm_state(hipStream_t s, const Tiling &tl, SppmState st, float *d_local);
+
 } // namespace hpt

@@ -361,6 +361,123 @@ void k_ppm_gather(SceneDev sc, PathBuf pb, PpmHitBuf hb, PpmGrid g, const uint32
     }
 }
 
+// ---- progressive photon mapping (DESIGN.md "Progressive photon mapping") ---------------------------------------
+// Cell offsets along one axis that a sphere of radius rho (in cells) around u = (h - smin) / cell can reach: -1 only
+// if fr < rho + mg, +1 only if fr > 1 - rho - mg (fr = u - floor(u), exact); all three when |u| >= 2^20 or u is not
+// a number.  The margin mg = 2^-6 + |u| 2^-20 covers the rounding of u, of a deposit's own u and of rho.
+HPT_DEV void sppm_axis(float h, float smin, float cell, float rho, int &lo, int &hi){
+    const float u = (h - smin) / cell;
+    const float au = fabsf(u);
+    lo = -1; hi = 1;
+    if(!(au < 1048576.0f)) return;
+    const float fr = u - floorf(u);
+    const float mg = 0.015625f + au * 9.5367431640625e-07f;
+    if(!(fr < rho + mg)) lo = 0;
+    if(!(fr > 1.0f - rho - mg)) hi = 0;
+}
+
+// k_ppm_gather with the pixel's own R2 and the cull above, and the pixel's update fused in: the lane owns its pixel.
+// Skipped cells hold no accepted pair, so the sum, M and the image are those of the full 27 cells, bit for bit.
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock)
+void k_sppm_gather(SceneDev sc, PpmHitBuf hb, PpmGrid g, const uint32_t *hp_count, PpmFrame fr, SppmState st, float alpha,
+                   uint32_t *cand_out, uint32_t *acc_out, PpmCounters *pc){
+    const uint32_t count = *hp_count;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long n_cand = 0, n_acc = 0;
+    if(i < count){
+        const uint32_t slot = hb.list[i];
+        const float4 pm = hb.pos_mat[slot];
+        const f3 hp = xyz(pm), hn = xyz(hb.nrm[slot]), hwo = xyz(hb.wo[slot]), hthr = xyz(hb.thr[slot]);
+        const float r2 = st.tau_r2[slot].w;
+        const DevMaterial dm = sc.mats[f2u(pm.w)];
+        const Mat m = load_mat(dm);
+        const ShadeCtx ctx = make_shade_ctx(hn, hwo);
+        ShadePre pre; pre.diffuse = mk3(dm.diffuse[0], dm.diffuse[1], dm.diffuse[2]);
+        pre.lam_o = ggx_lambda(ctx.wo, roughness_to_alpha(m.roughness));
+        int cx, cy, cz;
+        cell_of(fr, hp, cx, cy, cz);
+        const float rho = sqrtf(r2) / fr.cell;
+        int x0, x1, y0, y1, z0, z1;
+        sppm_axis(hp.x, fr.smin[0], fr.cell, rho, x0, x1);
+        sppm_axis(hp.y, fr.smin[1], fr.cell, rho, y0, y1);
+        sppm_axis(hp.z, fr.smin[2], fr.cell, rho, z0, z1);
+        f3 acc = mk3(0, 0, 0);
+        uint32_t n_m = 0;
+        for(int z = z0; z <= z1; ++z) for(int y = y0; y <= y1; ++y) for(int x = x0; x <= x1; ++x){
+            const int gx = cx + x, gy = cy + y, gz = cz + z;
+            const uint2 r = g.range[bucket_of(gx, gy, gz, g.buckets)];
+            for(uint32_t e = r.x; e < r.y; ++e){
+                const float4 a = g.packed[(size_t) e * 4 + 0], b = g.packed[(size_t) e * 4 + 1], c = g.packed[(size_t) e * 4 + 2];
+                if((int) f2u(a.w) != gx || (int) f2u(b.w) != gy || (int) f2u(c.w) != gz) continue;   // another cell in this bucket
+                if(COUNT) ++n_cand;
+                if(!(dot3(hn, xyz(b)) > 0.01f)) continue;
+                const f3 d = hp - xyz(a);
+                if(!(dot3(d, d) < r2)) continue;
+                if(COUNT) ++n_acc;
+                f3 f; float pdf_unused;
+                bsdf_eval_pdf_local<true, false>(m, ctx.wo, to_local(xyz(c), ctx.T, ctx.B, ctx.N), f, pdf_unused, &pre);
+                if(is_valid_color(f)){
+                    const float4 fl = g.packed[(size_t) e * 4 + 3];
+                    f3 energy = xyz(fl) * f * hthr;
+                    acc = acc + energy;
+                    ++n_m;
+                }
+            }
+        }
+        if(n_m > 0u){
+            const float mf = (float) n_m;
+            const float n_old = st.photons[slot];
+            const float n_new = n_old + alpha * mf;
+            const float ratio = n_new / (n_old + mf);
+            const f3 tau = (xyz(st.tau_r2[slot]) + acc) * ratio;
+            st.tau_r2[slot] = make_float4(tau.x, tau.y, tau.z, r2 * ratio);
+            st.photons[slot] = n_new;
+        }
+        if(COUNT){ cand_out[slot] = (uint32_t) n_cand; acc_out[slot] = (uint32_t) n_acc; }
+    }
+    if(COUNT){
+        n_cand = wave_sum(n_cand); n_acc = wave_sum(n_acc);
+        if((threadIdx.x & 63u) == 0u){
+            if(n_cand) atomicAdd(&pc->candidates, n_cand);
+            if(n_acc) atomicAdd(&pc->accepted, n_acc);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock)
+void k_sppm_init(SppmState st, uint32_t n, float r2){
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if(p >= n) return;
+    st.tau_r2[p] = make_float4(0.0f, 0.0f, 0.0f, r2);
+    st.photons[p] = 0.0f;
+    st.direct[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// d = D, p = tau / max(pi R2, 1e-6), both divided by K unless K is 1; the radiance term after PPM's guard and clamp
+__global__ __launch_bounds__(kBlock)
+void k_sppm_estimate(Tiling tl, SppmState st, float passes, float *d_local){
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if(p >= (uint32_t) tl.n_local) return;
+    const float4 tr = st.tau_r2[p];
+    f3 d = xyz(st.direct[p]);
+    f3 rad = xyz(tr) / fmaxf(kPi * tr.w, 1e-6f);
+    if(passes != 1.0f){ d = d / passes; rad = rad / passes; }
+    const f3 v = is_valid_color(rad) ? d + clamp_radiance(rad, 15.0f) : d;
+    d_local[(size_t) p * 3 + 0] = v.x;
+    d_local[(size_t) p * 3 + 1] = v.y;
+    d_local[(size_t) p * 3 + 2] = v.z;
+}
+
+__global__ __launch_bounds__(kBlock)
+void k_sppm_state(Tiling tl, SppmState st, float *d_local){
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if(p >= (uint32_t) tl.n_local) return;
+    d_local[(size_t) p * 3 + 0] = st.tau_r2[p].w;
+    d_local[(size_t) p * 3 + 1] = st.photons[p];
+    d_local[(size_t) p * 3 + 2] = 0.0f;
+}
+
 uint32_t groups_for(uint32_t n){ return n == 0u ? 1u : (n + kBlock - 1) / kBlock; }
 
 } // namespace
@@ -415,6 +532,24 @@ void launch_ppm_gather(hipStream_t s, const SceneDev &sc, PathBuf pb, PpmHitBuf 
 
 void launch_ppm_iota(hipStream_t s, uint32_t *p, uint32_t n){
     hipLaunchKernelGGL(k_ppm_iota, dim3(groups_for(n)), dim3(kBlock), 0, s, p, n);
+}
+
+void launch_sppm_init(hipStream_t s, SppmState st, uint32_t n_local, float r2){
+    hipLaunchKernelGGL(k_sppm_init, dim3(groups_for(n_local)), dim3(kBlock), 0, s, st, n_local, r2);
+}
+
+void launch_sppm_gather(hipStream_t s, const SceneDev &sc, PpmHitBuf hb, PpmGrid g, const uint32_t *hp_count, uint32_t max_items,
+                        PpmFrame fr, SppmState st, float alpha, uint32_t *cand, uint32_t *acc, PpmCounters *pc){
+    if(cand) hipLaunchKernelGGL(k_sppm_gather<true>, dim3(groups_for(max_items)), dim3(kBlock), 0, s, sc, hb, g, hp_count, fr, st, alpha, cand, acc, pc);
+    else hipLaunchKernelGGL(k_sppm_gather<false>, dim3(groups_for(max_items)), dim3(kBlock), 0, s, sc, hb, g, hp_count, fr, st, alpha, cand, acc, pc);
+}
+
+void launch_sppm_estimate(hipStream_t s, const Tiling &tl, SppmState st, float passes, float *d_local){
+    hipLaunchKernelGGL(k_sppm_estimate, dim3(groups_for((uint32_t) tl.n_local)), dim3(kBlock), 0, s, tl, st, passes, d_local);
+}
+
+void launch_sppm_state(hipStream_t s, const Tiling &tl, SppmState st, float *d_local){
+    hipLaunchKernelGGL(k_sppm_state, dim3(groups_for((uint32_t) tl.n_local)), dim3(kBlock), 0, s, tl, st, d_local);
 }
 
 } // namespace hpt
