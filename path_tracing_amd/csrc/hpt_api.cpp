@@ -982,7 +982,7 @@ int render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth, in
     if(r.n_dep) launch_ppm_iota(st, s->grid.slot_in, r.n_dep);
     HIP_TRY(hipEventRecord(s->ev_start, st));
     for(int pass = 0; pass < spp; ++pass){
-        rc = ppm_phases(s, r, pass, (uint32_t) (P.sample_offset + pass));
+        rc = ppm_phases(s, r, pass, (uint32_t) ((int64_t) P.sample_offset + pass));
         if(rc) return rc;
         launch_ppm_gather(st, s->sd, w.pb, s->hb, s->grid, r.hp_count(s), r.n_local, fr, r.count ? s->ppm_cand : nullptr,
                           r.count ? s->ppm_acc : nullptr, s->d_pc);

@@ -50,11 +50,15 @@ HPT_DEV unsigned long long wave_sum(unsigned long long v){
     return v;
 }
 
-// grid cell of a point: floorf((p - scene_min) / cell) per axis (ppm_cu.cu:34-38, 256-260)
+// grid cell of a point: floorf((p - scene_min) / cell) per axis (ppm_cu.cu:34-38, 256-260), clamped to [-2^30, 2^30]
+// in float before the conversion (NaN to -2^30), so that it is defined for every input and c +- 1 cannot overflow
+HPT_DEV int cell_axis(float p, float smin, float cell){
+    return (int) fminf(fmaxf(floorf((p - smin) / cell), -1073741824.0f), 1073741824.0f);
+}
 HPT_DEV void cell_of(const PpmFrame &fr, f3 p, int &gx, int &gy, int &gz){
-    gx = (int) floorf((p.x - fr.smin[0]) / fr.cell);
-    gy = (int) floorf((p.y - fr.smin[1]) / fr.cell);
-    gz = (int) floorf((p.z - fr.smin[2]) / fr.cell);
+    gx = cell_axis(p.x, fr.smin[0], fr.cell);
+    gy = cell_axis(p.y, fr.smin[1], fr.cell);
+    gz = cell_axis(p.z, fr.smin[2], fr.cell);
 }
 // bucket of a cell: the reference's spatial hash (ppm_cu.cu:28-30) through a 32-bit finaliser, masked to the table
 HPT_DEV uint32_t bucket_of(int gx, int gy, int gz, uint32_t buckets){

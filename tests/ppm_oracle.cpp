@@ -2,14 +2,13 @@
 // every sum defined as DESIGN.md "PPM" defines it.  Built by tests/ppm_oracle.py with the flags of oracle/Makefile;
 // the shared math (BSDF, intersections, PCG) is oracle/ref_math.hpp, which the HIP kernels match bit for bit.
 //
-// Closest hit: the reference's brute-force scan (include/geometric.cuh:327-388).  Gather: a std::map from cell to
-// the ascending list of deposit slots; brute != 0 instead scans every deposit slot for every one of the 27 cells
-// (the double loop the map must agree with).
+// Closest hit: the reference's brute-force scan (include/geometric.cuh:327-388).  Gather: the valid deposits sorted by
+// (cell, slot), each cell a contiguous run of ascending slots; brute != 0 instead scans every deposit slot for every one
+// of the 27 cells (the double loop the sorted grid must agree with).
 #include "../oracle/ref_math.hpp"
 
+#include <algorithm>
 #include <cstdint>
-#include <map>
-#include <tuple>
 #include <vector>
 
 using namespace orc;
@@ -56,20 +55,63 @@ Hit closest(const Sc &sc, V3 ro, V3 rd){
 struct HitPoint { bool valid; V3 pos, normal, wo, thr; RMat mtl; };
 struct Deposit { bool valid; V3 pos, normal, wi, flux; int cx, cy, cz; };
 
+// floorf((p - mn) / cell) clamped to [-2^30, 2^30] in float (NaN to -2^30): defined for every input, c +- 1 fits
+int cell_axis(float p, float mn, float cell){
+    return (int) fminf(fmaxf(floorf((p - mn) / cell), -1073741824.0f), 1073741824.0f);
+}
 void cell_of(V3 p, V3 mn, float cell, int &gx, int &gy, int &gz){
-    gx = (int) floorf((p.x - mn.x) / cell);
-    gy = (int) floorf((p.y - mn.y) / cell);
-    gz = (int) floorf((p.z - mn.z) / cell);
+    gx = cell_axis(p.x, mn.x, cell);
+    gy = cell_axis(p.y, mn.y, cell);
+    gz = cell_axis(p.z, mn.z, cell);
+}
+
+// The valid deposits by (cell, ascending slot): cell(x, y, z) yields the run of slots of one cell.
+struct Grid {
+    struct E { int cx, cy, cz; uint32_t slot; };
+    std::vector<E> e;
+    void build(const std::vector<Deposit> &deps){
+        e.clear();
+        for(size_t k = 0; k < deps.size(); ++k) if(deps[k].valid) e.push_back(E{ deps[k].cx, deps[k].cy, deps[k].cz, (uint32_t) k });
+        std::sort(e.begin(), e.end(), [](const E &a, const E &b){
+            if(a.cx != b.cx) return a.cx < b.cx;
+            if(a.cy != b.cy) return a.cy < b.cy;
+            if(a.cz != b.cz) return a.cz < b.cz;
+            return a.slot < b.slot;
+        });
+    }
+    std::pair<const E *, const E *> cell(int x, int y, int z) const {
+        auto less = [](const E &a, const E &b){
+            if(a.cx != b.cx) return a.cx < b.cx;
+            if(a.cy != b.cy) return a.cy < b.cy;
+            return a.cz < b.cz;
+        };
+        const E key{ x, y, z, 0u };
+        auto r = std::equal_range(e.begin(), e.end(), key, less);
+        return { e.data() + (r.first - e.begin()), e.data() + (r.second - e.begin()) };
+    }
+};
+
+// median (element n / 2 after sorting, as hpt_ppm_get_stats takes it) and maximum of per-hit-point counts
+void median_max(std::vector<uint32_t> v, uint64_t &med, uint64_t &mx){
+    med = mx = 0;
+    if(v.empty()) return;
+    std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
+    med = v[v.size() / 2];
+    mx = *std::max_element(v.begin(), v.end());
 }
 
 } // namespace
 
 // stats_out: photons, photon_rays, deposits, hit_points, direct_pixels (summed over passes).
 // flux_out (optional, W*H*3): the accumulated flux of every pixel's hit point in the LAST pass.
+// work_out (optional, 6): candidates, accepted (summed over passes), then the median and maximum over the LAST pass's
+// hit points of candidates and of accepted pairs (cand_median, cand_max, acc_median, acc_max of hpt_ppm_stats).
+// pos_out (optional, W*H*3): every pixel's hit point position in the LAST pass, NaN where it has none.
 extern "C" int ppm_oracle_render(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt,
                                  const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl,
                                  float radius, const float *smin, const float *smax, uint64_t seed, int sample_offset,
-                                 int max_delta, int output_sum, int brute, float *image, uint64_t *stats_out, float *flux_out){
+                                 int max_delta, int output_sum, int brute, float *image, uint64_t *stats_out, float *flux_out,
+                                 uint64_t *work_out, float *pos_out){
     Sc sc{ (const RLight *) lights, nl, (const RSphere *) spheres, ns, (const RTriangle *) tris, nt };
     const RCamera &cam = *(const RCamera *) camera;
     if(max_delta <= 0) max_delta = 64;
@@ -82,9 +124,10 @@ extern "C" int ppm_oracle_render(const void *lights, int nl, const void *spheres
     std::vector<V3> sum(npx, v3(0, 0, 0)), img(npx);
     std::vector<HitPoint> hps(npx);
     std::vector<Deposit> deps((size_t) n_ph * light_depth);
-    uint64_t st[5] = { 0, 0, 0, 0, 0 };
+    std::vector<uint32_t> pcand(npx), pacc(npx);
+    uint64_t st[5] = { 0, 0, 0, 0, 0 }, ncand = 0, nacc = 0;
     for(int pass = 0; pass < spp; ++pass){
-        const uint32_t pidx = (uint32_t) (sample_offset + pass);
+        const uint32_t pidx = (uint32_t) ((int64_t) sample_offset + pass);
         uint64_t direct = 0, nhp = 0, ndep = 0, rays = 0;
         // eye pass, ppm_cu.cu:64-150
 #pragma omp parallel for schedule(dynamic, 16) reduction(+:direct, nhp)
@@ -184,19 +227,24 @@ extern "C" int ppm_oracle_render(const void *lights, int nl, const void *spheres
             }
         }
         // gather in the defined order: 27 cells (z, y, x from -1 to +1), ascending slot inside a cell
-        std::map<std::tuple<int, int, int>, std::vector<uint32_t>> grid;
-        if(!brute) for(size_t k = 0; k < deps.size(); ++k) if(deps[k].valid) grid[std::make_tuple(deps[k].cx, deps[k].cy, deps[k].cz)].push_back((uint32_t) k);
-#pragma omp parallel for schedule(dynamic, 16)
+        Grid grid;
+        if(!brute) grid.build(deps);
+#pragma omp parallel for schedule(dynamic, 16) reduction(+:ncand, nacc)
         for(int64_t idx = 0; idx < (int64_t) npx; ++idx){
             const HitPoint &hp = hps[idx];
+            pcand[idx] = pacc[idx] = 0;
+            if(pos_out){ const V3 p = hp.valid ? hp.pos : v3(NAN, NAN, NAN); pos_out[idx * 3] = p.x; pos_out[idx * 3 + 1] = p.y; pos_out[idx * 3 + 2] = p.z; }
             if(!hp.valid){ if(flux_out){ flux_out[idx * 3] = flux_out[idx * 3 + 1] = flux_out[idx * 3 + 2] = 0.0f; } continue; }
             int cx, cy, cz;
             cell_of(hp.pos, mn, cell, cx, cy, cz);
             V3 acc = v3(0, 0, 0);
+            uint32_t nc = 0, na = 0;
             auto visit = [&](const Deposit &dp){
+                ++nc;
                 if(!(dot(hp.normal, dp.normal) > 0.01f)) return;
                 V3 dd = hp.pos - dp.pos;
                 if(!(dot(dd, dd) < r2)) return;
+                ++na;
                 V3 brdf = bsdf_evaluate(hp.mtl, hp.wo, dp.wi, hp.normal);
                 if(is_valid_color(brdf)) acc = acc + dp.flux * brdf * hp.thr;
             };
@@ -205,17 +253,25 @@ extern "C" int ppm_oracle_render(const void *lights, int nl, const void *spheres
                 if(brute){
                     for(const Deposit &dp : deps) if(dp.valid && dp.cx == gx && dp.cy == gy && dp.cz == gz) visit(dp);
                 } else {
-                    auto it = grid.find(std::make_tuple(gx, gy, gz));
-                    if(it != grid.end()) for(uint32_t k : it->second) visit(deps[k]);
+                    auto run = grid.cell(gx, gy, gz);
+                    for(const Grid::E *q = run.first; q != run.second; ++q) visit(deps[q->slot]);
                 }
             }
+            pcand[idx] = nc; pacc[idx] = na; ncand += nc; nacc += na;
             if(flux_out){ flux_out[idx * 3] = acc.x; flux_out[idx * 3 + 1] = acc.y; flux_out[idx * 3 + 2] = acc.z; }
             V3 radiance = acc / fmaxf(kPi * r2, 1e-6f);
             if(is_valid_color(radiance)) img[idx] = img[idx] + clamp_radiance(radiance, 15.0f);
         }
         for(size_t k = 0; k < npx; ++k){ V3 c = img[k]; if(!is_valid_color(c)) c = v3(0, 0, 0); sum[k] = sum[k] + c; }
         st[0] += (uint64_t) n_ph; st[1] += rays; st[2] += ndep; st[3] += nhp; st[4] += direct;
+        if(work_out && pass + 1 == spp){
+            std::vector<uint32_t> c, a;
+            for(size_t k = 0; k < npx; ++k) if(hps[k].valid){ c.push_back(pcand[k]); a.push_back(pacc[k]); }
+            median_max(c, work_out[2], work_out[3]);
+            median_max(a, work_out[4], work_out[5]);
+        }
     }
+    if(work_out){ work_out[0] = ncand; work_out[1] = nacc; }
     for(size_t k = 0; k < npx; ++k){
         V3 v = sum[k];
         if(!output_sum && spp != 1) v = v / (float) spp;

@@ -146,8 +146,8 @@ extern "C" int sppm_oracle_render(const void *lights, int nl, const void *sphere
             }
         }
         // gather with the pixel's own radius, the cull, and the update
-        std::map<std::tuple<int, int, int>, std::vector<uint32_t>> grid;
-        for(size_t q = 0; q < deps.size(); ++q) if(deps[q].valid) grid[std::make_tuple(deps[q].cx, deps[q].cy, deps[q].cz)].push_back((uint32_t) q);
+        Grid grid;
+        grid.build(deps);
 #pragma omp parallel for schedule(dynamic, 16) reduction(+:ncand, nacc)
         for(int64_t idx = 0; idx < (int64_t) npx; ++idx){
             // D += the guarded direct term (k_resolve)
@@ -169,10 +169,9 @@ extern "C" int sppm_oracle_render(const void *lights, int nl, const void *sphere
             V3 acc = v3(0, 0, 0);
             uint32_t m = 0;
             for(int z = z0; z <= z1; z++) for(int y = y0; y <= y1; y++) for(int x = x0; x <= x1; x++){
-                auto it = grid.find(std::make_tuple(cx + x, cy + y, cz + z));
-                if(it == grid.end()) continue;
-                for(uint32_t q : it->second){
-                    const Deposit &dp = deps[q];
+                auto run = grid.cell(cx + x, cy + y, cz + z);
+                for(const Grid::E *q = run.first; q != run.second; ++q){
+                    const Deposit &dp = deps[q->slot];
                     ++ncand;
                     if(!(dot(hp.normal, dp.normal) > 0.01f)) continue;
                     V3 dd = hp.pos - dp.pos;

@@ -87,8 +87,8 @@ def test_oracle_tiny_radius_reaches_no_deposit(plib, small_input):
 
 
 def test_oracle_grid_gather_equals_brute_force_double_loop(plib):
-    """Two triangles (a diffuse floor, a glossy wall) under a spot light: the map-based gather and the scan over every
-    deposit for each of the 27 cells give the same accumulated flux, bit for bit."""
+    """Two triangles (a diffuse floor, a glossy wall) under a spot light: the sorted grid's gather and the scan over every
+    deposit for each of the 27 cells give the same accumulated flux, bit for bit, and examine the same pairs."""
     from path_tracing_amd.layouts import LIGHT, SPHERE, TRIANGLE
     tr = np.zeros(2, TRIANGLE)
     tr[0]["v0"], tr[0]["v1"], tr[0]["v2"] = (-1, 0, -1), (1, 0, -1), (0, 0, 1)
@@ -102,8 +102,10 @@ def test_oracle_grid_gather_equals_brute_force_double_loop(plib):
     from path_tracing_amd.layouts import CAMERA
     cam = np.zeros((), CAMERA)
     cam["eye"] = (0, 0.6, 2.0); cam["UL"] = (-0.5, 1.0, 1.0); cam["dx"] = (1 / 16, 0, 0); cam["dy"] = (0, -1 / 16, 0)
-    img_a, st_a, fa = ppm_oracle.render(plib, L, sp, tr, cam, 16, 16, spl=2000, radius=0.2, seed=2, want_flux=True)
-    img_b, st_b, fb = ppm_oracle.render(plib, L, sp, tr, cam, 16, 16, spl=2000, radius=0.2, seed=2, want_flux=True, brute=True)
+    img_a, st_a, fa = ppm_oracle.render(plib, L, sp, tr, cam, 16, 16, spl=2000, radius=0.2, seed=2, want_flux=True, want_work=True)
+    img_b, st_b, fb = ppm_oracle.render(plib, L, sp, tr, cam, 16, 16, spl=2000, radius=0.2, seed=2, want_flux=True, brute=True,
+                                        want_work=True)
     assert st_a["deposits"] > 100 and st_a["hit_points"] > 0
     assert fa.any()
     assert fa.tobytes() == fb.tobytes() and img_a.tobytes() == img_b.tobytes()
+    assert st_a == st_b and st_a["accepted"] > 0 and st_a["cand_max"] >= st_a["cand_median"] > 0
