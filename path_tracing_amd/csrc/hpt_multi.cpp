@@ -13,25 +13,19 @@
 // if it cannot be loaded or a communicator cannot be made the call fails (no silent substitute).  Exchange
 // mode 1 (explicit, for boxes without RCCL and for tests that put several ranks on ONE device, which RCCL
 // refuses) moves the buffers with hipMemcpyPeerAsync instead.
-#include "../../include/hpt.h"
-#include "hpt_scene.h"
+#include "hpt_host.h"
 
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 
 #include <chrono>
-#include <cstring>
 #include <mutex>
-#include <string>
 #include <thread>
-#include <vector>
 
-namespace hpt { int fail_with(int code, const std::string &msg); }
+using hpt::fail;
+using hpt::DevBuf;
 
 namespace {
-
-using hpt::fail_with;
 
 struct Rccl {
     void *handle = nullptr;
@@ -62,10 +56,8 @@ Rccl &rccl(){
     return r;
 }
 
-#define MHIP_TRY(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) \
-    return fail_with(e_ == hipErrorOutOfMemory ? HPT_ERR_NOMEM : HPT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while(0)
 #define NCCL_TRY(expr) do { ncclResult_t r_ = (expr); if(r_ != ncclSuccess) \
-    return fail_with(HPT_ERR_DEVICE, std::string(#expr) + ": " + rccl().GetErrorString(r_)); } while(0)
+    return fail(HPT_ERR_DEVICE, std::string(#expr) + ": " + rccl().GetErrorString(r_)); } while(0)
 
 } // namespace
 
@@ -74,9 +66,8 @@ struct hpt_multi {
     std::vector<int> dev;
     std::vector<hpt_scene *> scene;
     std::vector<hipStream_t> stream;
-    std::vector<float *> d_local; size_t cap_local = 0;       // floats per device
-    float *d_gathered = nullptr; size_t cap_gathered = 0;     // on dev[0]
-    float *d_image = nullptr; size_t cap_image = 0;           // on dev[0]
+    std::vector<DevBuf<float>> d_local;                       // one per rank, on dev[rank]
+    DevBuf<float> d_gathered, d_image;                        // on dev[0]
     std::vector<ncclComm_t> comm;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     std::vector<double> render_ms;
@@ -89,25 +80,13 @@ namespace {
 
 int ensure_buffers(hpt_multi *m, size_t n_local, size_t W, size_t H){
     size_t nloc = n_local * 3;
-    if(nloc > m->cap_local){
-        for(int d = 0; d < m->n; ++d){
-            MHIP_TRY(hipSetDevice(m->dev[d]));
-            hipFree(m->d_local[d]); m->d_local[d] = nullptr;
-            MHIP_TRY(hipMalloc((void **) &m->d_local[d], nloc * sizeof(float)));
-        }
-        m->cap_local = nloc;
+    for(int d = 0; d < m->n; ++d) if(nloc > m->d_local[d].capacity()){
+        HIP_TRY(hipSetDevice(m->dev[d]));
+        HIP_TRY(m->d_local[d].reserve(nloc));
     }
-    MHIP_TRY(hipSetDevice(m->dev[0]));
-    if(nloc * m->n > m->cap_gathered){
-        hipFree(m->d_gathered); m->d_gathered = nullptr; m->cap_gathered = 0;
-        MHIP_TRY(hipMalloc((void **) &m->d_gathered, nloc * m->n * sizeof(float)));
-        m->cap_gathered = nloc * m->n;
-    }
-    if(W * H * 3 > m->cap_image){
-        hipFree(m->d_image); m->d_image = nullptr; m->cap_image = 0;
-        MHIP_TRY(hipMalloc((void **) &m->d_image, W * H * 3 * sizeof(float)));
-        m->cap_image = W * H * 3;
-    }
+    HIP_TRY(hipSetDevice(m->dev[0]));
+    HIP_TRY(m->d_gathered.reserve(nloc * m->n));
+    HIP_TRY(m->d_image.reserve(W * H * 3));
     return HPT_OK;
 }
 
@@ -133,15 +112,15 @@ int fan_out(hpt_multi *m, F render){
     }
     for(std::thread &t : th) t.join();
     for(int d = 0; d < m->n; ++d)
-        if(rc[d] != HPT_OK) return fail_with(rc[d], "device " + std::to_string(m->dev[d]) + " (rank " + std::to_string(d) + "): " + msg[d]);
+        if(rc[d] != HPT_OK) return fail(rc[d], "device " + std::to_string(m->dev[d]) + " (rank " + std::to_string(d) + "): " + msg[d]);
     return HPT_OK;
 }
 
 // packed local framebuffers -> [rank][local slot] on dev[0] -> row-major image -> host
 int exchange_and_assemble(hpt_multi *m, size_t n_local, int W, int H, const hpt_params *params, float *host_image){
     const size_t count = n_local * 3;
-    MHIP_TRY(hipSetDevice(m->dev[0]));
-    MHIP_TRY(hipEventRecord(m->ev_a, m->stream[0]));
+    HIP_TRY(hipSetDevice(m->dev[0]));
+    HIP_TRY(hipEventRecord(m->ev_a, m->stream[0]));
     if(m->exchange == 0){
         Rccl &R = rccl();
         NCCL_TRY(R.GroupStart());
@@ -151,29 +130,30 @@ int exchange_and_assemble(hpt_multi *m, size_t n_local, int W, int H, const hpt_
         for(int d = 0; d < m->n && first_error.empty(); ++d){
             hipError_t e = hipSetDevice(m->dev[d]);
             if(e != hipSuccess){ first_error = std::string("hipSetDevice: ") + hipGetErrorString(e); break; }
-            ncclResult_t r = R.Gather(m->d_local[d], d == 0 ? m->d_gathered : nullptr, count, ncclFloat, 0, m->comm[d], m->stream[d]);
+            ncclResult_t r = R.Gather(m->d_local[d].get(), d == 0 ? m->d_gathered.get() : nullptr, count, ncclFloat, 0, m->comm[d], m->stream[d]);
             if(r != ncclSuccess) first_error = std::string("ncclGather (rank ") + std::to_string(d) + "): " + R.GetErrorString(r);
         }
         ncclResult_t ge = R.GroupEnd();
-        if(!first_error.empty()){ (void) hipSetDevice(m->dev[0]); return fail_with(HPT_ERR_DEVICE, first_error); }
-        if(ge != ncclSuccess) return fail_with(HPT_ERR_DEVICE, std::string("ncclGroupEnd: ") + R.GetErrorString(ge));
-        MHIP_TRY(hipSetDevice(m->dev[0]));
+        if(!first_error.empty()){ (void) hipSetDevice(m->dev[0]); return fail(HPT_ERR_DEVICE, first_error); }
+        if(ge != ncclSuccess) return fail(HPT_ERR_DEVICE, std::string("ncclGroupEnd: ") + R.GetErrorString(ge));
+        HIP_TRY(hipSetDevice(m->dev[0]));
     } else {
         for(int d = 0; d < m->n; ++d){
+            float *to = m->d_gathered.get() + d * count; const float *from = m->d_local[d].get();
             if(m->dev[d] == m->dev[0])
-                MHIP_TRY(hipMemcpyAsync(m->d_gathered + d * count, m->d_local[d], count * sizeof(float), hipMemcpyDeviceToDevice, m->stream[0]));
+                HIP_TRY(hipMemcpyAsync(to, from, count * sizeof(float), hipMemcpyDeviceToDevice, m->stream[0]));
             else
-                MHIP_TRY(hipMemcpyPeerAsync(m->d_gathered + d * count, m->dev[0], m->d_local[d], m->dev[d], count * sizeof(float), m->stream[0]));
+                HIP_TRY(hipMemcpyPeerAsync(to, m->dev[0], from, m->dev[d], count * sizeof(float), m->stream[0]));
         }
     }
-    MHIP_TRY(hipEventRecord(m->ev_b, m->stream[0]));
+    HIP_TRY(hipEventRecord(m->ev_b, m->stream[0]));
     hpt_params p; memset(&p, 0, sizeof p);
     if(params) p = *params;
     p.rank = 0; p.world = m->n;
-    int rc = hpt_untile(m->d_gathered, m->d_image, W, H, &p, m->stream[0]);
+    int rc = hpt_untile(m->d_gathered.get(), m->d_image.get(), W, H, &p, m->stream[0]);
     if(rc) return rc;
-    MHIP_TRY(hipMemcpyAsync(host_image, m->d_image, (size_t) W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, m->stream[0]));
-    MHIP_TRY(hipStreamSynchronize(m->stream[0]));
+    HIP_TRY(hipMemcpyAsync(host_image, m->d_image.get(), (size_t) W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, m->stream[0]));
+    HIP_TRY(hipStreamSynchronize(m->stream[0]));
     float ms = 0.f;
     if(hipEventElapsedTime(&ms, m->ev_a, m->ev_b) == hipSuccess) m->gather_ms = ms;
     return HPT_OK;
@@ -181,8 +161,8 @@ int exchange_and_assemble(hpt_multi *m, size_t n_local, int W, int H, const hpt_
 
 template <typename F>
 int multi_render(hpt_multi *m, int W, int H, const hpt_params *params, float *host_image, F render_rank){
-    if(!m) return fail_with(HPT_ERR_INVALID, "null fan-out handle");
-    if(!host_image) return fail_with(HPT_ERR_INVALID, "null image");
+    if(!m) return fail(HPT_ERR_INVALID, "null fan-out handle");
+    if(!host_image) return fail(HPT_ERR_INVALID, "null image");
     int restore = 0; hipGetDevice(&restore);
     hpt_params p; memset(&p, 0, sizeof p);
     if(params) p = *params;
@@ -209,12 +189,12 @@ void hpt_multi_destroy(hpt_multi *m){
     for(int d = 0; d < (int) m->dev.size(); ++d){
         hipSetDevice(m->dev[d]);
         if(d < (int) m->scene.size() && m->scene[d]) hpt_scene_destroy(m->scene[d]);
-        if(d < (int) m->d_local.size()) hipFree(m->d_local[d]);
+        if(d < (int) m->d_local.size()) m->d_local[d].release();
         if(d < (int) m->stream.size() && m->stream[d]) hipStreamDestroy(m->stream[d]);
     }
     if(!m->dev.empty()){
         hipSetDevice(m->dev[0]);
-        hipFree(m->d_gathered); hipFree(m->d_image);
+        m->d_gathered.release(); m->d_image.release();
         if(m->ev_a) hipEventDestroy(m->ev_a);
         if(m->ev_b) hipEventDestroy(m->ev_b);
     }
@@ -224,49 +204,50 @@ void hpt_multi_destroy(hpt_multi *m){
 
 int hpt_multi_create(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt,
                      const int *device_ids, int num_devices, int exchange, hpt_multi **out){
-    if(!out) return fail_with(HPT_ERR_INVALID, "null out handle");
+    if(!out) return fail(HPT_ERR_INVALID, "null out handle");
     *out = nullptr;
-    if(exchange != 0 && exchange != 1) return fail_with(HPT_ERR_INVALID, "exchange must be 0 (RCCL) or 1 (peer copies)");
+    if(exchange != 0 && exchange != 1) return fail(HPT_ERR_INVALID, "exchange must be 0 (RCCL) or 1 (peer copies)");
     int visible = 0;
-    MHIP_TRY(hipGetDeviceCount(&visible));
+    HIP_TRY(hipGetDeviceCount(&visible));
     if(num_devices <= 0) num_devices = visible;
-    if(num_devices <= 0 || num_devices > 64) return fail_with(HPT_ERR_INVALID, "no HIP device (or more than 64 ranks)");
+    if(num_devices <= 0 || num_devices > 64) return fail(HPT_ERR_INVALID, "no HIP device (or more than 64 ranks)");
     hpt_multi *m = new hpt_multi();
     m->n = num_devices; m->exchange = exchange;
     for(int d = 0; d < num_devices; ++d){
         int id = device_ids ? device_ids[d] : d;
-        if(id < 0 || id >= visible){ delete m; return fail_with(HPT_ERR_INVALID, "device id outside [0, hipGetDeviceCount)"); }
+        if(id < 0 || id >= visible){ delete m; return fail(HPT_ERR_INVALID, "device id outside [0, hipGetDeviceCount)"); }
         m->dev.push_back(id);
     }
     if(exchange == 0){
         for(int a = 0; a < num_devices; ++a) for(int b = a + 1; b < num_devices; ++b)
-            if(m->dev[a] == m->dev[b]){ delete m; return fail_with(HPT_ERR_INVALID, "RCCL exchange needs distinct devices (several ranks on one device: exchange = 1)"); }
-        if(!rccl().error.empty()){ delete m; return fail_with(HPT_ERR_DEVICE, rccl().error); }
+            if(m->dev[a] == m->dev[b]){ delete m; return fail(HPT_ERR_INVALID, "RCCL exchange needs distinct devices (several ranks on one device: exchange = 1)"); }
+        if(!rccl().error.empty()){ delete m; return fail(HPT_ERR_DEVICE, rccl().error); }
     }
     int restore = 0; hipGetDevice(&restore);
-    m->scene.assign(num_devices, nullptr); m->stream.assign(num_devices, nullptr); m->d_local.assign(num_devices, nullptr);
+    m->scene.assign(num_devices, nullptr); m->stream.assign(num_devices, nullptr);
+    m->d_local = std::vector<DevBuf<float>>(num_devices);
     m->render_ms.assign(num_devices, 0.0);
     // flatten + BVH once, upload everywhere
     hpt::HostScene hs;
     const char *err = hpt::build_host_scene(lights, nl, spheres, ns, tris, nt, hs);
     int rc = HPT_OK;
-    if(err && *err) rc = fail_with(HPT_ERR_INVALID, err);
+    if(err && *err) rc = fail(HPT_ERR_INVALID, err);
     for(int d = 0; d < num_devices && rc == HPT_OK; ++d){
         hipError_t e = hipSetDevice(m->dev[d]);
         if(e == hipSuccess) e = hipStreamCreateWithFlags(&m->stream[d], hipStreamNonBlocking);
-        if(e != hipSuccess){ rc = fail_with(HPT_ERR_DEVICE, std::string("device set-up: ") + hipGetErrorString(e)); break; }
+        if(e != hipSuccess){ rc = fail(HPT_ERR_DEVICE, std::string("device set-up: ") + hipGetErrorString(e)); break; }
         rc = hpt::scene_upload(hs, lights, nl, spheres, ns, tris, nt, &m->scene[d]);
     }
     if(rc == HPT_OK){
         hipError_t e = hipSetDevice(m->dev[0]);
         if(e == hipSuccess) e = hipEventCreate(&m->ev_a);
         if(e == hipSuccess) e = hipEventCreate(&m->ev_b);
-        if(e != hipSuccess) rc = fail_with(HPT_ERR_DEVICE, std::string("event set-up: ") + hipGetErrorString(e));
+        if(e != hipSuccess) rc = fail(HPT_ERR_DEVICE, std::string("event set-up: ") + hipGetErrorString(e));
     }
     if(rc == HPT_OK && exchange == 0){
         m->comm.assign(num_devices, nullptr);
         ncclResult_t r = rccl().CommInitAll(m->comm.data(), num_devices, m->dev.data());
-        if(r != ncclSuccess){ m->comm.clear(); rc = fail_with(HPT_ERR_DEVICE, std::string("ncclCommInitAll: ") + rccl().GetErrorString(r)); }
+        if(r != ncclSuccess){ m->comm.clear(); rc = fail(HPT_ERR_DEVICE, std::string("ncclCommInitAll: ") + rccl().GetErrorString(r)); }
     }
     if(rc == HPT_OK && exchange == 1){
         // peer access for the copies into the root's buffer (already-enabled is fine)
@@ -282,7 +263,7 @@ int hpt_multi_create(const void *lights, int nl, const void *spheres, int ns, co
         if(nt) m->h_tris.assign((const unsigned char *) tris, (const unsigned char *) tris + (size_t) nt * HPT_TRIANGLE_BYTES);
     }
     hipSetDevice(restore);
-    if(rc != HPT_OK){ std::string keep = hpt_last_error(); hpt_multi_destroy(m); return fail_with(rc, keep); }
+    if(rc != HPT_OK){ std::string keep = hpt_last_error(); hpt_multi_destroy(m); return fail(rc, keep); }
     *out = m;
     return HPT_OK;
 }
@@ -290,7 +271,7 @@ int hpt_multi_create(const void *lights, int nl, const void *spheres, int ns, co
 int hpt_multi_num_devices(const hpt_multi *m){ return m ? m->n : 0; }
 
 int hpt_multi_set_groups(hpt_multi *m, const int32_t *obj_kind, const int32_t *obj_index, const int32_t *obj_group, int num_objects){
-    if(!m) return fail_with(HPT_ERR_INVALID, "null fan-out handle");
+    if(!m) return fail(HPT_ERR_INVALID, "null fan-out handle");
     for(int d = 0; d < m->n; ++d){
         int rc = hpt_scene_set_groups(m->scene[d], obj_kind, obj_index, obj_group, num_objects);
         if(rc) return rc;
@@ -301,19 +282,19 @@ int hpt_multi_set_groups(hpt_multi *m, const int32_t *obj_kind, const int32_t *o
 int hpt_multi_render_pt(hpt_multi *m, const void *camera, int W, int H, int eye_depth, int spp,
                         const hpt_params *params, float *host_image){
     return multi_render(m, W, H, params, host_image, [&](int d, const hpt_params &q){
-        return hpt_render_pt_device(m->scene[d], camera, W, H, eye_depth, spp, &q, m->d_local[d], m->stream[d]);
+        return hpt_render_pt_device(m->scene[d], camera, W, H, eye_depth, spp, &q, m->d_local[d].get(), m->stream[d]);
     });
 }
 
 int hpt_multi_render_bdpt(hpt_multi *m, const void *camera, int W, int H, int eye_depth, int light_depth, int spp, int spl,
                           const hpt_params *params, float *host_image){
     return multi_render(m, W, H, params, host_image, [&](int d, const hpt_params &q){
-        return hpt_render_bdpt_device(m->scene[d], camera, W, H, eye_depth, light_depth, spp, spl, &q, m->d_local[d], m->stream[d]);
+        return hpt_render_bdpt_device(m->scene[d], camera, W, H, eye_depth, light_depth, spp, spl, &q, m->d_local[d].get(), m->stream[d]);
     });
 }
 
 int hpt_multi_get_timing(const hpt_multi *m, double *render_ms_per_device, double *gather_ms, double *total_ms){
-    if(!m) return fail_with(HPT_ERR_INVALID, "null fan-out handle");
+    if(!m) return fail(HPT_ERR_INVALID, "null fan-out handle");
     if(render_ms_per_device) for(int d = 0; d < m->n; ++d) render_ms_per_device[d] = m->render_ms[d];
     if(gather_ms) *gather_ms = m->gather_ms;
     if(total_ms) *total_ms = m->total_ms;
@@ -326,12 +307,9 @@ namespace hpt {
 
 // the fan-out kept by the one-shot wrappers: reused when the next call hands over byte-identical arrays
 bool multi_matches(const hpt_multi *m, int n_devices, const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt){
-    auto same = [](const std::vector<unsigned char> &kept, const void *given, size_t bytes){
-        return kept.size() == bytes && (bytes == 0 || memcmp(kept.data(), given, bytes) == 0);
-    };
     return m && m->n == n_devices && nl >= 0 && ns >= 0 && nt >= 0 &&
-           same(m->h_lights, lights, (size_t) nl * HPT_LIGHT_BYTES) && same(m->h_spheres, spheres, (size_t) ns * HPT_SPHERE_BYTES) &&
-           same(m->h_tris, tris, (size_t) nt * HPT_TRIANGLE_BYTES);
+           same_bytes(m->h_lights, lights, (size_t) nl * HPT_LIGHT_BYTES) && same_bytes(m->h_spheres, spheres, (size_t) ns * HPT_SPHERE_BYTES) &&
+           same_bytes(m->h_tris, tris, (size_t) nt * HPT_TRIANGLE_BYTES);
 }
 
 } // namespace hpt

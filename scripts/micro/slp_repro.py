@@ -40,7 +40,8 @@ def build():
     print(subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout.splitlines()[0])
     for tag, fl in (("off", flags), ("on", flags.replace("-fno-slp-vectorize", ""))):
         objs = []
-        for f in ("pt_kernels.hip", "bdpt_kernels.hip", "hpt_api.cpp", "hpt_multi.cpp"):
+        for f in ("pt_kernels.hip", "bdpt_kernels.hip", "ppm_kernels.hip", "hpt_api.cpp", "render_pt.cpp", "render_bdpt.cpp", "render_ppm.cpp",
+                  "hpt_multi.cpp"):
             path = os.path.join(OUT if f == "pt_kernels.hip" else CSRC, f)
             o = os.path.join(OUT, "%s_%s.o" % (os.path.splitext(f)[0], tag))
             subprocess.check_call(["/opt/rocm/bin/hipcc"] + fl.split() + ["-I", CSRC, "-x", "hip", "-c", "-o", o, path])
