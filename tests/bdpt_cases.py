@@ -1,0 +1,287 @@
+"""Case table of the bidirectional coverage suite: scenes and render shapes at which the five kernels of
+csrc/bdpt_kernels.hip, the host loop of render_bdpt.cpp and the per-group trees of build_bdpt_host_scene can go wrong
+and the checks at the end of test_gpu_parity.py do not look.  A plain module: no GPU, no tests.
+
+  depths      eye_depth != light_depth (hist_pos_eta / hist_pdf are strided by the eye depth; t_idx, real_light and
+              the MIS walk mix the two)
+  nlv         light-vertex counts n_lv = lights * spl * light_depth off the 8-entry step of k_bdpt_reduce and the
+              64-vertex chunk of k_bdpt_connect: 1, 9, 63, 65, and 1036
+  deep        per-group trees deeper than 12 levels (30 000-triangle mesh, 20 000 random triangles)
+  groups      negative and scattered group ids, interleaved insertion, a sphere-only group, a flat one-quad group,
+              coincident duplicates in another group than their originals
+  parallel    a parallel light whose light reaches the floor (open ceiling), alone and beside a cone light
+  max_delta   a delta-bounce cap below the default on the glass / mirror scene
+  edge        empty, lights only, one triangle, spheres only, glass only, no lights
+  far         a scene 64 times larger, hundreds of units from the origin
+
+Every case is `Case(name, make, dark)`; make() returns
+    (L, sp, tr, order, (eye, look_at, view_up, fov), W, H, eye_depth, light_depth, spp, spl, seed, max_delta)
+and `dark` is None or the reason why the case is exempt from test_bdpt_cases_cpu.py's conditions (lit share >= 0.5,
+connections > 0) -- EXEMPT_CONNECTIONS names the ones that cannot connect at all.
+
+Observed on the CPU oracle (oracle.bdpt_render, 8 threads; lit = share of pixels with a non-zero channel):
+  depths-e1-l1-spl1      n_lv     4  lit  32.1 %  connections     1107  0.20 s  (dark)
+  depths-e1-l5-spl3      n_lv    60  lit 100.0 %  connections    34805  0.20 s
+  depths-e6-l1-spl5      n_lv    20  lit  98.1 %  connections    36538  0.22 s
+  depths-e2-l7-spl3      n_lv    84  lit 100.0 %  connections    76394  0.26 s
+  depths-e7-l2-spl5      n_lv    40  lit 100.0 %  connections   138495  0.17 s
+  depths-e3-l5-spl13     n_lv   260  lit 100.0 %  connections   474090  0.09 s
+  depths-e5-l3-spl1      n_lv    12  lit 100.0 %  connections    30124  0.01 s
+  nlv-l1-spl1            n_lv     1  lit   1.6 %  connections      554  0.01 s  (dark)
+  nlv-l3-spl3            n_lv     9  lit 100.0 %  connections    14601  0.01 s
+  nlv-l7-spl9            n_lv    63  lit 100.0 %  connections   103950  0.03 s
+  nlv-l5-spl13           n_lv    65  lit 100.0 %  connections   132393  0.03 s
+  nlv-l1-spl63           n_lv    63  lit 100.0 %  connections   169126  0.03 s
+  nlv-1036               n_lv  1036  lit 100.0 %  connections   426209  0.10 s
+  deep-mesh30k           n_lv    48  lit 100.0 %  connections    36221  3.30 s
+  deep-random20k         n_lv    48  lit 100.0 %  connections    30357  2.67 s
+  groups-201             n_lv     6  lit 100.0 %  connections    11356  0.01 s   44 of 768 pixels differ from one group
+  groups-202             n_lv    12  lit 100.0 %  connections    23866  0.01 s   62 of 768
+  parallel-open          n_lv    24  lit  90.9 %  connections    21239  0.02 s   698 of 768 pixels differ from illum 0
+  parallel-open-cone     n_lv    48  lit  91.4 %  connections    72437  0.04 s   697 of 768
+  max_delta-1            n_lv    60  lit 100.0 %  connections   199031  0.05 s   18.3 % of pixels differ from the default cap
+  max_delta-2            n_lv    60  lit 100.0 %  connections   219118  0.05 s   5.1 %
+  max_delta-3            n_lv    60  lit 100.0 %  connections   222943  0.05 s   0.7 %
+  edge-empty             n_lv     0  lit   0.0 %  connections        0  0.00 s  (dark)
+  edge-lights_only       n_lv    24  lit   4.2 %  connections        0  0.00 s  (dark)
+  edge-one_triangle      n_lv    24  lit  13.9 %  connections      177  0.00 s  (dark)
+  edge-spheres_only      n_lv    24  lit   7.8 %  connections      161  0.00 s  (dark)
+  edge-delta_only        n_lv    24  lit   4.2 %  connections        0  0.00 s  (dark)
+  edge-no_lights         n_lv     0  lit   0.0 %  connections        0  0.00 s  (dark)
+  far (seed 201)         n_lv     8  lit 100.0 %  connections    22991  0.02 s   (seed 202: 100 %; 203, 204: under 1 %)
+"""
+import collections
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(_HERE)
+for _p in (_ROOT, _HERE):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from path_tracing_amd import scene_io as sio                       # noqa: E402
+from path_tracing_amd.layouts import LIGHT, SPHERE, TRIANGLE       # noqa: E402
+from test_gpu_parity import _random_scene                          # noqa: E402
+
+INPUT_TXT = os.path.join(_HERE, "golden", "scenes", "input.txt")
+CORNELL_CAM = (sio.CORNELL_EYE, sio.CORNELL_LOOK, sio.CORNELL_UP, 50.0)
+
+Case = collections.namedtuple("Case", "name make dark")
+
+# (eye_depth, light_depth, spl) on input.txt's four lights: n_lv = 4, 60, 20, 84, 40, 260, 12
+DEPTHS = [(1, 1, 1), (1, 5, 3), (6, 1, 5), (2, 7, 3), (7, 2, 5), (3, 5, 13), (5, 3, 1)]
+# (light_depth, spl) on input.txt's first light alone: n_lv = 1, 9, 63, 65, 63.  (7, 1) is left out: 2 % lit.
+ODD_NLV = [(1, 1), (3, 3), (7, 9), (5, 13), (1, 63)]
+BIG_NLV = (7, 37)                    # on all four lights: 4 * 37 * 7 = 1036 = 16 * 64 + 12 = 129 * 8 + 4
+MAX_DELTAS = [1, 2, 3]
+GROUP_IDS = [-3, 0, 7, 100, 5, 2, 11]
+SPHERE_ONLY_GROUP, QUAD_ONLY_GROUP = 100, 11
+GROUP_SEEDS = [201, 202]
+FAR_SCALE, FAR_SHIFT, FAR_SEED = 64.0, (300.0, -200.0, 500.0), 201
+
+
+def single_group(sp, tr):
+    """(kind, index, group) of the implicit grouping: the spheres, then the triangles, in group 0."""
+    return sio.object_order(None, sp, tr)
+
+
+def _input():
+    sc = sio.load_scene(INPUT_TXT)
+    L, sp, tr = sio.flatten_for_pt(sc)
+    return sc, L, sp, tr, sio.object_order(sc)
+
+
+def _input_cam(sc):
+    return (tuple(sc.eye), tuple(sc.look_at), tuple(sc.view_up), float(sc.fov))
+
+
+# ---- depths, n_lv, max_delta: input.txt with its two groups ----------------------------------------------------------
+def depth_case(eye_depth, light_depth, spl):
+    sc, L, sp, tr, order = _input()
+    return L, sp, tr, order, _input_cam(sc), 40, 28, eye_depth, light_depth, 2, spl, 8, 0
+
+
+def nlv_case(light_depth, spl):
+    sc, L, sp, tr, order = _input()
+    return L[:1].copy(), sp, tr, order, _input_cam(sc), 40, 28, 3, light_depth, 2, spl, 8, 0
+
+
+def big_nlv_case():
+    sc, L, sp, tr, order = _input()
+    return L, sp, tr, order, _input_cam(sc), 24, 20, 3, BIG_NLV[0], 1, BIG_NLV[1], 8, 0
+
+
+def max_delta_case(max_delta):
+    """max_delta 0 = the default cap (64), the image the capped ones must differ from."""
+    sc, L, sp, tr, order = _input()
+    return L, sp, tr, order, _input_cam(sc), 48, 36, 4, 3, 2, 5, 8, max_delta
+
+
+# ---- deep per-group trees --------------------------------------------------------------------------------------------
+def deep_case(which):
+    L, sp, tr = sio.cornell_with_sphere(30000) if which == "mesh30k" else sio.cornell_random_triangles(20000)
+    return L, sp, tr, single_group(sp, tr), CORNELL_CAM, 32, 24, 3, 3, 1, 16, 3, 0
+
+
+# ---- groups ----------------------------------------------------------------------------------------------------------
+def grouped_scene(seed):
+    """_random_scene(seed) plus a recoloured coincident copy of triangles 40-59, one more sphere and one axis-aligned
+    quad.  Returns (L, sp, tr, order): the objects in a seeded shuffled insertion order (spheres and triangles, and the
+    groups, interleaved), group ids from GROUP_IDS; the added sphere is alone in SPHERE_ONLY_GROUP (a group without a
+    tree), the quad alone in QUAD_ONLY_GROUP (a flat box: the degenerate-axis widening), and every duplicate sits in
+    another group than its original (a tie across groups: the later group in map order wins)."""
+    L, sp0, tr0 = _random_scene(sio, seed)
+    dup = tr0[40:60].copy()
+    dup["mtl"]["base_color"] = (0.1, 0.8, 0.1)
+    quad = sio._tris_from([(-0.25, -0.2, 0.2, 0.1, -0.2, 0.2, 0.1, -0.2, 0.55), (-0.25, -0.2, 0.2, 0.1, -0.2, 0.55, -0.25, -0.2, 0.55)],
+                          [(0.8, 0.8, 0.2, 1.0, 0.0, 0.0)] * 2)
+    tr = np.concatenate([tr0, dup, quad])
+    tr["id"] = np.arange(len(tr))
+    lone = np.zeros(1, SPHERE)
+    lone[0]["center"] = (0.28, -0.3, 0.3); lone[0]["r"] = 0.12
+    lone[0]["mtl"]["base_color"] = (0.2, 0.6, 0.9); lone[0]["mtl"]["roughness"] = 0.6
+    sp = np.concatenate([sp0, lone])
+    sp["id"] = np.arange(len(sp))
+    n0, nd = len(tr0), len(dup)
+    rng = np.random.default_rng(seed + 1000)
+    shared = [g for g in GROUP_IDS if g not in (SPHERE_ONLY_GROUP, QUAD_ONLY_GROUP)]
+    g_sp = [shared[int(k)] for k in rng.integers(0, len(shared), size=len(sp0))] + [SPHERE_ONLY_GROUP]
+    g_tr = [shared[int(k)] for k in rng.integers(0, len(shared), size=n0)]
+    g_tr += [shared[(shared.index(g_tr[40 + k]) + 1 + int(rng.integers(0, len(shared) - 1))) % len(shared)] for k in range(nd)]
+    g_tr += [QUAD_ONLY_GROUP, QUAD_ONLY_GROUP]
+    objs = [(0, i, g_sp[i]) for i in range(len(sp))] + [(1, i, g_tr[i]) for i in range(len(tr))]
+    objs = [objs[int(k)] for k in rng.permutation(len(objs))]
+    order = tuple(np.asarray([o[c] for o in objs], np.int32) for c in range(3))
+    return L, sp, tr, order
+
+
+def groups_case(seed):
+    L, sp, tr, order = grouped_scene(seed)
+    return L, sp, tr, order, CORNELL_CAM, 32, 24, 4, 3, 2, 2, seed, 0
+
+
+# ---- a parallel light that arrives -----------------------------------------------------------------------------------
+def open_box_scene(with_cone=False, parallel_on=True):
+    """_random_scene(203) -- one parallel light in the Cornell box -- without the two ceiling triangles."""
+    L, sp, tr = _random_scene(sio, 203)
+    assert len(L) == 1 and int(L[0]["is_parallel"]) == 1
+    ceiling = (tr["v0"][:, 1] > 0.49) & (tr["v1"][:, 1] > 0.49) & (tr["v2"][:, 1] > 0.49)
+    assert int(ceiling.sum()) == 2
+    tr = tr[~ceiling].copy()
+    tr["id"] = np.arange(len(tr))
+    L = L.copy()
+    if not parallel_on:
+        L["illum"] = 0.0
+        L["light_ball"]["mtl_old"]["Kd"] = 0.0
+    if with_cone:
+        L = np.concatenate([L, sio._one_light((0.2, 0.4, 0.3), (0.0, -1.0, 0.1), (0.9, 0.7, 0.5), 40.0, 0, 0.05)])
+    return L, sp, tr
+
+
+def parallel_case(with_cone, parallel_on=True):
+    L, sp, tr = open_box_scene(with_cone, parallel_on)
+    return L, sp, tr, single_group(sp, tr), CORNELL_CAM, 32, 24, 4, 4, 2, 6, 203, 0
+
+
+# ---- edge scenes -----------------------------------------------------------------------------------------------------
+EDGE = ["empty", "lights_only", "one_triangle", "spheres_only", "delta_only", "no_lights"]
+
+
+def edge_case(which):
+    L0, sp0, tr0 = sio.flatten_for_pt(sio.load_scene(INPUT_TXT))
+    L, sp, tr = np.zeros(0, LIGHT), np.zeros(0, SPHERE), np.zeros(0, TRIANGLE)
+    if which == "lights_only":
+        L = L0
+    elif which == "one_triangle":
+        L, tr = L0, tr0[6:7].copy()
+    elif which == "spheres_only":
+        L, sp = L0, sp0
+    elif which == "delta_only":                       # the two glass spheres
+        L, sp = L0, sp0[3:5].copy()
+        assert (sp["mtl"]["eta"] > 0).all()
+    elif which == "no_lights":
+        sp, tr = sp0, tr0
+    cam = ((0.0, 0.0, -1.0), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), 50.0)
+    return L, sp, tr, single_group(sp, tr), cam, 40, 24, 3, 2, 2, 3, 4, 0
+
+
+# ---- far from the origin ---------------------------------------------------------------------------------------------
+def far_case(seed=FAR_SEED):
+    """_random_scene(seed) scaled by FAR_SCALE and moved by FAR_SHIFT, camera too; illum * FAR_SCALE^2 keeps the
+    irradiance.  Box tests and epsilons there work on coordinates of 200-600 with an ulp of 3e-5 to 6e-5."""
+    L, sp, tr = _random_scene(sio, seed)
+    s, sh = np.float32(FAR_SCALE), np.asarray(FAR_SHIFT, np.float32)
+    L, sp, tr = L.copy(), sp.copy(), tr.copy()
+    for k in ("v0", "v1", "v2"):
+        tr[k] = tr[k] * s + sh
+    sp["center"] = sp["center"] * s + sh
+    sp["r"] = sp["r"] * s
+    L["pos"] = L["pos"] * s + sh
+    L["light_ball"]["center"] = L["light_ball"]["center"] * s + sh
+    L["light_ball"]["r"] = L["light_ball"]["r"] * s
+    L["illum"] = L["illum"] * (s * s)
+    L["light_ball"]["mtl_old"]["Kd"] = L["light_ball"]["mtl_old"]["Kd"] * (s * s)
+    eye = tuple(float(v) for v in np.asarray(sio.CORNELL_EYE, np.float32) * s + sh)
+    look = tuple(float(v) for v in np.asarray(sio.CORNELL_LOOK, np.float32) * s + sh)
+    return L, sp, tr, single_group(sp, tr), (eye, look, sio.CORNELL_UP, 50.0), 32, 24, 3, 4, 2, 2, seed, 0
+
+
+# ---- the table -------------------------------------------------------------------------------------------------------
+def _bind(fn, *a):
+    return lambda: fn(*a)
+
+
+_NO_SURFACE = "no surface for an eye vertex: only light balls (seen directly) or nothing can be hit"
+CASES = (
+    [Case("depths-e%d-l%d-spl%d" % c, _bind(depth_case, *c),
+          "one eye vertex (no indirect light) against 4 emission points inside 60-degree cones" if c == (1, 1, 1) else None) for c in DEPTHS]
+    + [Case("nlv-l%d-spl%d" % c, _bind(nlv_case, *c),
+            "one light vertex: the emission point of one cone light lights what its cone sees, nothing else" if c == (1, 1) else None) for c in ODD_NLV]
+    + [Case("nlv-1036", big_nlv_case, None)]
+    + [Case("deep-" + w, _bind(deep_case, w), None) for w in ("mesh30k", "random20k")]
+    + [Case("groups-%d" % s, _bind(groups_case, s), None) for s in GROUP_SEEDS]
+    + [Case("parallel-open", _bind(parallel_case, False), None), Case("parallel-open-cone", _bind(parallel_case, True), None)]
+    + [Case("max_delta-%d" % m, _bind(max_delta_case, m), None) for m in MAX_DELTAS]
+    + [Case("edge-empty", _bind(edge_case, "empty"), "nothing in the scene"),
+       Case("edge-lights_only", _bind(edge_case, "lights_only"), _NO_SURFACE),
+       Case("edge-one_triangle", _bind(edge_case, "one_triangle"), "one triangle covers a few per cent of the image"),
+       Case("edge-spheres_only", _bind(edge_case, "spheres_only"), "five spheres in front of a void"),
+       Case("edge-delta_only", _bind(edge_case, "delta_only"), "two glass spheres in front of a void"),
+       Case("edge-no_lights", _bind(edge_case, "no_lights"), "no lights: the renderer returns a black image at once")]
+    + [Case("far", far_case, None)]
+)
+CASE_BY_NAME = {c.name: c for c in CASES}
+assert len(CASE_BY_NAME) == len(CASES)
+# no eye vertex to connect (empty, lights_only), no light vertex to connect it to (no_lights), or only glass vertices,
+# whose BSDF value is zero towards every light vertex so that no connection reaches its visibility test (delta_only)
+EXEMPT_CONNECTIONS = ("edge-empty", "edge-lights_only", "edge-no_lights", "edge-delta_only")
+ALL_ZERO = ("edge-empty", "edge-no_lights")
+
+_REFERENCE = {}
+
+
+def n_light_vertices(args):
+    return len(args[0]) * args[10] * args[8]
+
+
+def oracle_render(oracle_mod, args):
+    """(image, stats) of the CPU oracle for the 13-tuple a case's make() returns."""
+    L, sp, tr, order, (eye, look, up, fov), W, H, ed, ld, spp, spl, seed, max_delta = args
+    return oracle_mod.bdpt_render(L, sp, tr, order, eye, look, up, fov, W, H, ed, ld, spp, spl, seed=seed, max_delta=max_delta)
+
+
+def reference(oracle_mod, name):
+    """(args, image, stats) of a case of the table, computed once per process and shared; callers must not write to them."""
+    if name not in _REFERENCE:
+        args = CASE_BY_NAME[name].make()
+        img, st = oracle_render(oracle_mod, args)
+        img.setflags(write=False)
+        _REFERENCE[name] = (args, img, st)
+    return _REFERENCE[name]
+
+
+def lit_share(img):
+    return float((np.asarray(img) != 0).any(axis=-1).mean())
