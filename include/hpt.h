@@ -337,6 +337,75 @@ int hpt_tonemap_host(const float *linear_rgb, unsigned char *rgb8, int64_t num_p
 void hpt_tonemap_table(float thresholds_out[256]);
 void hpt_tonemap_reference(const float *linear_rgb, unsigned char *rgb8, int64_t num_pixels, int bgr);
 
+/* ---- guides and denoiser ----------------------------------------------------------------------------
+ * The reference's GUI renders 8 spp per frame and throws its accumulation away whenever the camera moves
+ * (src/main.cpp:406-466); it has no denoiser.  These calls add the standard two steps for such sample counts:
+ * cheap noise-free guide images of the first rough surface behind every pixel, and an edge-avoiding a-trous wavelet
+ * filter (Dammertz et al. 2010) over the noisy radiance, steered by them.
+ *
+ * hpt_render_guides: for sample s = 0 .. spp-1, photon mapping's eye pass of pass index (low 32 bits of)
+ * sample_offset + s -- streams (seed ^ eye key, pixel, pass), jitter, free delta bounces capped at max_delta, all as
+ * in hpt_render_ppm's pass of that index.  A pixel whose pass ends in a hit point (the first non-delta surface) adds
+ * the hit material's base colour to A, the ray-facing normal to N, the position to P and one to C, float adds in
+ * sample order; pixels that end on a light ball, miss or die add nothing.  Then albedo = A / (float) C, normal =
+ * N / (float) C, position = P / (float) C per channel (all zero where C = 0) and coverage = (float) C.  The normal is
+ * NOT renormalised: a pixel that straddles an edge gets a shorter normal, which lowers its weight across the edge.
+ * Outputs are host images, row-major, row 0 = top: W*H*3 floats (coverage: W*H); any may be NULL, not all four.
+ * params: seed, sample_offset, max_delta and tile as for hpt_render_ppm; world other than 0 or 1, a non-zero
+ * reserved, any flag but HPT_FLAG_TIME_KERNELS, or spp < 1 return HPT_ERR_INVALID.  One device.  hpt_ppm_stats
+ * afterwards holds hit_points and direct_pixels of the call and, under TIME_KERNELS, ms_eye.
+ *
+ * The filter.  valid(p): coverage[p] > 0.  a(p) = max(albedo[p], 1e-3f) per channel.  c_0(p) = colour[p] / a(p) with
+ * HPT_DENOISE_DEMODULATE (valid pixels), else colour[p].  Taps h = {1/16, 1/4, 3/8, 1/4, 1/16}.  Falloff
+ * e(x) = q^8, q = fmaxf(0, 1 - x * 0.125f), by three squarings: a polynomial stand-in for exp(-x) (the library calls
+ * no device transcendental on a path that is compared bit for bit) with compact support, e(x) = 0 exactly for x >= 8.
+ * Level k = 0 .. iterations-1, stride s = 2^k; sc = sigma_color * 2^-k; inv_c = 1 / (sc * sc), inv_n = 1 / sigma_normal^2,
+ * inv_p = 1 / sigma_position^2, computed in float on the host.  An invalid pixel keeps its value.  For a valid p = (x, y):
+ * for j = -2..2 (outer), i = -2..2 (inner), q = (x + i s, y + j s), skipped when outside the image or invalid:
+ *   xc = (dc.x dc.x + dc.y dc.y + dc.z dc.z) * inv_c with dc = c_k(p) - c_k(q);  xn likewise from normal[p] - normal[q];
+ *   t = n(p).x d.x + n(p).y d.y + n(p).z d.z with d = position[q] - position[p] (q's distance from p's tangent plane),
+ *   xp = t * t * inv_p;   w = h[j+2] * h[i+2] * e(xc) * e(xn) * e(xp), left to right (a term switched off is 1.0f);
+ *   sum += c_k(q) * w per channel, wsum += w;   c_{k+1}(p) = sum / wsum (the centre tap makes wsum >= 9/64).
+ *   A valid pixel whose 24 other taps are all skipped keeps its value, c_{k+1}(p) = c_k(p): fl(fl(c * 9/64) / (9/64))
+ *   is not c for every float, and a level whose stride exceeds the image must hand its input on unchanged.
+ * Output c_n(p) * a(p) with DEMODULATE, else c_n(p); an invalid pixel outputs colour[p] exactly.  The tap order is part
+ * of the definition; everything is IEEE float, evaluated as written.  Inputs are expected to be finite.
+ *
+ * hpt_denoiser_create allocates, on the current device, the packed guides and two colour buffers of a W x H image
+ * (80 bytes per pixel).  hpt_denoiser_set_guides packs four DEVICE images with the layouts of hpt_render_guides; they
+ * stay set for every later run (the GUI sets them when the camera moves and runs once per frame).  hpt_denoiser_run
+ * filters d_linear_rgb into d_out (device, W*H*3 floats each, not overlapping); both calls only enqueue on
+ * hip_stream, so they compose with hpt_untile before and hpt_tonemap after.  p NULL = all defaults.  Run before
+ * set_guides, iterations outside [0, 8], an unknown flag, a NaN sigma or overlapping images return HPT_ERR_INVALID.
+ * With HPT_DENOISE_TIME the run is bracketed by HIP events: hpt_denoiser_last_ms waits for it and returns the time of
+ * the colour pack and of all levels, hpt_denoiser_level_ms the first `cap` levels' own times (0 past the last level).
+ * hpt_denoise_host takes and returns host images (upload, set_guides, run, download). */
+typedef struct hpt_denoise_params {
+    int32_t iterations;     /* levels, 1..8; 0 -> 5.  Level k samples at stride 2^k */
+    float sigma_color;      /* 0 -> 1.0;  < 0 -> colour term off (weight 1) */
+    float sigma_normal;     /* 0 -> 0.5;  < 0 -> off */
+    float sigma_position;   /* 0 -> 0.05 (the library's one absolute length default, PPM's radius); < 0 -> off */
+    int32_t flags;          /* HPT_DENOISE_*; other bits: HPT_ERR_INVALID */
+} hpt_denoise_params;
+#define HPT_DENOISE_DEMODULATE 1
+#define HPT_DENOISE_TIME 2
+
+int hpt_render_guides(hpt_scene *scene, const void *camera, int W, int H, int spp,
+                      const hpt_params *params,
+                      float *albedo, float *normal, float *position, float *coverage);
+
+typedef struct hpt_denoiser hpt_denoiser;
+int hpt_denoiser_create(int W, int H, hpt_denoiser **out);
+int hpt_denoiser_set_guides(hpt_denoiser *d, const void *d_albedo, const void *d_normal,
+                            const void *d_position, const void *d_coverage, void *hip_stream);
+int hpt_denoiser_run(hpt_denoiser *d, const void *d_linear_rgb, void *d_out,
+                     const hpt_denoise_params *p, void *hip_stream);
+int hpt_denoiser_last_ms(const hpt_denoiser *d, double *ms_pack, double *ms_filter);
+int hpt_denoiser_level_ms(const hpt_denoiser *d, double *ms_levels, int cap);
+void hpt_denoiser_destroy(hpt_denoiser *d);
+int hpt_denoise_host(const float *linear_rgb, const float *albedo, const float *normal, const float *position,
+                     const float *coverage, float *out, int W, int H, const hpt_denoise_params *p);
+
 /* ---- the acceleration structure, exported (tests) -------------------------------------
  * The reference has no acceleration structure (include/geometric.cuh:293-388 scan every primitive); the tree the
  * kernels walk is this library's own, and the work counts the bench's roofline is built from (hpt_stats.boxes_*,

@@ -29,6 +29,8 @@ FLAG_TIME_KERNELS = 8
 FLAG_RUSSIAN_ROULETTE = 16
 FLAG_SINGLE_PIPELINE = 32
 FLAG_NO_HOST_WAIT = 64
+DENOISE_DEMODULATE = 1
+DENOISE_TIME = 2
 
 
 class HptError(RuntimeError):
@@ -71,6 +73,18 @@ class PpmStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DenoiseParams(C.Structure):
+    """hpt_denoise_params (include/hpt.h): zeros select the defaults (5 levels, sigmas 1.0 / 0.5 / 0.05); a negative
+    sigma switches its term off."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("flags", C.c_int32)]
+
+
+def make_denoise_params(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_position=0.0, demodulate=True, time=False) -> DenoiseParams:
+    return DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position),
+                         (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TIME if time else 0))
 
 
 class BvhInfo(C.Structure):
@@ -125,12 +139,17 @@ def load_library() -> C.CDLL:
                      "hpt_multi_render_pt", "hpt_multi_render_bdpt", "hpt_multi_get_timing", "hpt_wrapper_set_devices",
                      "hpt_probe_functions", "hpt_tonemap", "hpt_tonemap_host", "hpt_bvh_export_host", "hpt_scene_export_bvh",
                      "hpt_render_ppm", "hpt_ppm_get_stats", "hpt_ppm_render_wrapper",
-                     "hpt_sppm_create", "hpt_sppm_render", "hpt_sppm_reset", "hpt_sppm_read_state"):
+                     "hpt_sppm_create", "hpt_sppm_render", "hpt_sppm_reset", "hpt_sppm_read_state",
+                     "hpt_render_guides", "hpt_denoiser_create", "hpt_denoiser_set_guides", "hpt_denoiser_run",
+                     "hpt_denoiser_last_ms", "hpt_denoiser_level_ms", "hpt_denoise_host"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
             lib.hpt_sppm_destroy.restype = None
             lib.hpt_sppm_destroy.argtypes = [C.c_void_p]
+        if hasattr(lib, "hpt_denoiser_destroy"):
+            lib.hpt_denoiser_destroy.restype = None
+            lib.hpt_denoiser_destroy.argtypes = [C.c_void_p]
         lib.hpt_scene_destroy.restype = None
         lib.hpt_wrapper_cache_clear.restype = None
         lib.hpt_wrapper_cache_clear.argtypes = []
@@ -260,6 +279,18 @@ class Scene:
         The scene must stay open while the state lives."""
         return Sppm(self, camera, W, H, eye_depth, light_depth, spl, radius, alpha, params, scene_min, scene_max)
 
+    def render_guides(self, camera, W, H, spp=4, params: Params | None = None) -> dict:
+        """First-hit guide images for the denoiser (include/hpt.h, hpt_render_guides): the means over spp eye-pass samples
+        of base colour, ray-facing normal and position of the first non-delta surface, and the number of samples that
+        found one.  dict(albedo, normal, position: float32 [H, W, 3]; coverage: float32 [H, W])."""
+        params = params or make_params()
+        cam = np.ascontiguousarray(camera, CAMERA)
+        g = dict(albedo=np.empty((H, W, 3), np.float32), normal=np.empty((H, W, 3), np.float32),
+                 position=np.empty((H, W, 3), np.float32), coverage=np.empty((H, W), np.float32))
+        _check(self._lib.hpt_render_guides(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), _vp(g["albedo"]),
+                                           _vp(g["normal"]), _vp(g["position"]), _vp(g["coverage"])))
+        return g
+
     def stats(self) -> dict:
         st = Stats()
         _check(self._lib.hpt_get_stats(self._h, C.byref(st)))
@@ -338,6 +369,69 @@ class Sppm:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _dptr(x) -> C.c_void_p:
+    """A device pointer: an int, or anything with data_ptr() (a torch tensor on the device)."""
+    return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+
+
+class Denoiser:
+    """Edge-avoiding a-trous filter on the device (include/hpt.h, hpt_denoiser_*) for W x H images.  Guides and images
+    are DEVICE buffers (ints or torch tensors, float32, the layouts of Scene.render_guides); set_guides once per camera
+    position, run once per frame.  Both only enqueue on `stream`.  Host arrays: denoise()."""
+
+    def __init__(self, W, H):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        self.W, self.H = W, H
+        _check(self._lib.hpt_denoiser_create(int(W), int(H), C.byref(self._h)))
+
+    def set_guides(self, albedo, normal, position, coverage, stream: int = 0):
+        _check(self._lib.hpt_denoiser_set_guides(self._h, _dptr(albedo), _dptr(normal), _dptr(position), _dptr(coverage), C.c_void_p(stream)))
+
+    def run(self, linear_rgb, out, params: DenoiseParams | None = None, stream: int = 0):
+        params = params or make_denoise_params()
+        _check(self._lib.hpt_denoiser_run(self._h, _dptr(linear_rgb), _dptr(out), C.byref(params), C.c_void_p(stream)))
+
+    def last_ms(self) -> dict:
+        """Times of the last run with DENOISE_TIME (waits for it): dict(pack, filter, levels [8])."""
+        a, b = C.c_double(), C.c_double()
+        lv = (C.c_double * 8)()
+        _check(self._lib.hpt_denoiser_last_ms(self._h, C.byref(a), C.byref(b)))
+        _check(self._lib.hpt_denoiser_level_ms(self._h, lv, 8))
+        return dict(pack=a.value, filter=b.value, levels=list(lv))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.hpt_denoiser_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def denoise(image, guides, iterations=0, sigma_color=0, sigma_normal=0, sigma_position=0, demodulate=True) -> np.ndarray:
+    """Filters a host image [H, W, 3] with host guides (the dict of Scene.render_guides) through hpt_denoise_host:
+    upload, set_guides, run, download.  Zeros select the defaults; a negative sigma switches its term off."""
+    img = np.ascontiguousarray(image, np.float32)
+    H, W = img.shape[:2]
+    g = [np.ascontiguousarray(guides[k], np.float32) for k in ("albedo", "normal", "position", "coverage")]
+    if img.shape != (H, W, 3) or any(a.shape != (H, W, 3) for a in g[:3]) or g[3].shape != (H, W):
+        raise ValueError("denoise: image and guides must be [H, W, 3] (coverage [H, W]) of one size")
+    out = np.empty((H, W, 3), np.float32)
+    p = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_position, demodulate)
+    _check(load_library().hpt_denoise_host(_vp(img), _vp(g[0]), _vp(g[1]), _vp(g[2]), _vp(g[3]), _vp(out), W, H, C.byref(p)))
+    return out
 
 
 class MultiScene:
@@ -437,6 +531,11 @@ def tonemap(image) -> np.ndarray:
     out = np.zeros(img.shape, np.uint8)
     _check(load_library().hpt_tonemap_host(_vp(img), _vp(out), C.c_int64(img.size // 3), 0))
     return out
+
+
+def tonemap_device(d_linear_rgb, d_rgb8, num_pixels: int, bgr: bool = False, stream: int = 0):
+    """hpt_tonemap on device buffers (ints or torch tensors), enqueued on `stream`: the step after Denoiser.run."""
+    _check(load_library().hpt_tonemap(_dptr(d_linear_rgb), _dptr(d_rgb8), C.c_int64(num_pixels), 1 if bgr else 0, C.c_void_p(stream)))
 
 
 def wrapper_set_devices(n: int) -> None:

@@ -8,6 +8,8 @@
 //   --gpus N          render on N devices of this node inside the blocking call (image tiles, RCCL gather)
 //   --radius R        photon search radius of --mode ppm, initial radius of --mode sppm (reference: PPM_RADIUS 0.05)
 //   --alpha A         radius reduction of --mode sppm (default 0.7)
+//   --denoise         filter the frame before it is saved: --guide-spp N guide samples (default 4), then the edge-avoiding
+//                     a-trous filter (--denoise-iterations, --sigma-color, --sigma-normal, --sigma-position; 0 = default)
 // --mode pt, bdpt, ppm and sppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
 // reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
 // averaged, on one device; sppm the same passes into one progressive state whose radius shrinks per pixel.
@@ -31,6 +33,9 @@ int main(int argc, char **argv){
     std::string mode = "pt", output_file = "output.png", input_file = "../../input.txt", device = "gpu", obj_file;
     int width = 0, height = 0, max_depth = EYE_DEPTH;
     long long seed = -1;
+    bool denoise = false;
+    int guide_spp = 4;
+    hpt_denoise_params filter = { 0, 0.0f, 0.0f, 0.0f, 0 };
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -48,6 +53,12 @@ int main(int argc, char **argv){
         else if(arg == "--gpus" && i + 1 < argc) hpt_host::g_devices = std::max(1, std::stoi(argv[++i]));
         else if(arg == "--radius" && i + 1 < argc) hpt_host::g_ppm_radius = std::stof(argv[++i]);
         else if(arg == "--alpha" && i + 1 < argc) hpt_host::g_sppm_alpha = std::stof(argv[++i]);
+        else if(arg == "--denoise") denoise = true;
+        else if(arg == "--guide-spp" && i + 1 < argc) guide_spp = std::stoi(argv[++i]);
+        else if(arg == "--denoise-iterations" && i + 1 < argc) filter.iterations = std::stoi(argv[++i]);
+        else if(arg == "--sigma-color" && i + 1 < argc) filter.sigma_color = std::stof(argv[++i]);
+        else if(arg == "--sigma-normal" && i + 1 < argc) filter.sigma_normal = std::stof(argv[++i]);
+        else if(arg == "--sigma-position" && i + 1 < argc) filter.sigma_position = std::stof(argv[++i]);
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
@@ -64,7 +75,11 @@ int main(int argc, char **argv){
                       << "  --rr              unbiased Russian roulette (pt mode; not in the reference, off by default)\n"
                       << "  --gpus <int>      devices of this node to render on (image tiles, RCCL gather; default: 1; pt and bdpt)\n"
                       << "  --radius <float>  photon search radius of ppm mode, initial radius of sppm mode (default: 0.05)\n"
-                      << "  --alpha <float>   radius reduction of sppm mode, in (0, 1] (default: 0.7); --spp is its number of passes\n";
+                      << "  --alpha <float>   radius reduction of sppm mode, in (0, 1] (default: 0.7); --spp is its number of passes\n"
+                      << "  --denoise         denoise the frame before saving it (every mode; with --gpus on device 0)\n"
+                      << "  --guide-spp <int> guide samples per pixel of --denoise (default: 4)\n"
+                      << "  --denoise-iterations <int>  filter levels, 1..8 (default: 5)\n"
+                      << "  --sigma-color/--sigma-normal/--sigma-position <float>  edge-stopping widths (defaults: 1.0, 0.5, 0.05; < 0: off)\n";
             return 0;
         }
     }
@@ -116,6 +131,13 @@ int main(int argc, char **argv){
     std::cout << "\n";
     auto diff = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - start_time);
     std::cout << "[Render] Finished in " << diff.count() << " ms.\n";
+
+    if(denoise){
+        auto t0 = std::chrono::steady_clock::now();
+        if(!denoise_frame(mode, cam, frame_results.data(), W, H, guide_spp, filter)) return -1;
+        auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0);
+        std::cout << "[Denoise] " << guide_spp << " guide spp, finished in " << ms.count() << " ms.\n";
+    }
 
     std::cout << "[Save] Writing to " << output_file << "...\n";
     std::string err;

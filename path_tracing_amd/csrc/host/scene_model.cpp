@@ -470,6 +470,31 @@ void run_cuda_sppm(CudaCamera cam, float3 *image_buffer, int light_depth, int ey
     hpt_sppm_destroy(state);
 }
 
+bool denoise_frame(const std::string &mode, CudaCamera cam, float3 *image_buffer, int W, int H, int guide_spp, hpt_denoise_params filter){
+    MovedScene &ms = mode == "bdpt" ? g_bdpt : (mode == "ppm" || mode == "sppm") ? g_ppm : g_pt;
+    if(!ms.ready()){ std::cerr << "denoise_frame: no scene moved to the device" << std::endl; return false; }
+    hpt_scene *scene = ms.device, *own = nullptr;
+    int rc = HPT_OK;
+    if(!scene){
+        rc = hpt_scene_create(ms.flat.lights.data(), (int) ms.flat.lights.size(), ms.flat.spheres.data(), (int) ms.flat.spheres.size(),
+                              ms.flat.triangles.data(), (int) ms.flat.triangles.size(), &own);
+        scene = own;
+    }
+    const size_t npx = (size_t) W * H;
+    std::vector<float> albedo(npx * 3), normal(npx * 3), position(npx * 3), coverage(npx), out(npx * 3);
+    if(rc == HPT_OK){
+        hpt_params p = run_params();
+        p.flags = 0; p.rank = 0; p.world = 0; p.samples_per_pass = 0; p.reserved = 0;
+        rc = hpt_render_guides(scene, &cam, W, H, guide_spp, &p, albedo.data(), normal.data(), position.data(), coverage.data());
+    }
+    filter.flags = HPT_DENOISE_DEMODULATE;
+    if(rc == HPT_OK) rc = hpt_denoise_host(&image_buffer->x, albedo.data(), normal.data(), position.data(), coverage.data(), out.data(), W, H, &filter);
+    if(rc == HPT_OK) memcpy(&image_buffer->x, out.data(), npx * 3 * sizeof(float));
+    else std::cerr << "denoise_frame: " << hpt_last_error() << std::endl;
+    if(own) hpt_scene_destroy(own);
+    return rc == HPT_OK;
+}
+
 // ---- C entry points (tests, Python: scene_io.load_scene_fast / load_obj) ---------------------------------------
 extern "C" {
 

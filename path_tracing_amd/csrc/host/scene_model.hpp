@@ -14,6 +14,7 @@
 // The device records are the ones of include/hpt_reference_api.hpp (CudaLight, CudaSphere, ...).
 #pragma once
 #include "../../../include/hpt_reference_api.hpp"
+#include "../../../include/hpt.h"
 
 #include <cstdint>
 #include <map>
@@ -130,3 +131,8 @@ void run_cuda_ppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye
 // Progressive photon mapping on the scene moved by move_data_to_cuda_ppm: one state (hpt_sppm_*), `passes` passes of
 // `light_sample` photons per light, initial radius hpt_host::g_ppm_radius, alpha hpt_host::g_sppm_alpha; one device.
 void run_cuda_sppm(CudaCamera cam, float3 *image_buffer, int light_depth, int eye_depth, int W, int H, int passes);
+// Denoises in place the frame a run_cuda_* call of `mode` ("pt", "bdpt", "ppm" or "sppm") returned for the scene moved
+// for that mode: guide_spp guide samples (hpt_render_guides, the run's seed) and the a-trous filter with demodulation
+// (hpt_denoise_host; zeros in `filter` select the defaults).  A fan-out over several devices has no single scene: the
+// moved records are uploaded once more to the current device (device 0) for the guides, and the filter runs there.
+bool denoise_frame(const std::string &mode, CudaCamera cam, float3 *image_buffer, int W, int H, int guide_spp, hpt_denoise_params filter);

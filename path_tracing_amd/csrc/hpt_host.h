@@ -1,5 +1,5 @@
 // Host side of libhpt.so, shared by its translation units (hpt_api.cpp, render_pt.cpp, render_bdpt.cpp, render_ppm.cpp,
-// hpt_multi.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
+// denoise.cpp, hpt_multi.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
 // Internal and host only; compiled as HIP because it includes the launch interfaces.
 #pragma once
 #include "../../include/hpt.h"
@@ -7,6 +7,7 @@
 #include "pt_kernels.h"
 #include "bdpt_kernels.h"
 #include "ppm_kernels.h"
+#include "denoise_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -142,6 +143,7 @@ struct hpt_scene {
         hpt::PpmHitBuf hb{}; hpt::PpmGrid grid{};    // views of the buffers above, filled by ppm_prepare
         hpt::DevBuf<uint32_t> cand, acc;
         hpt::DevBuf<hpt::PpmCounters> pc;
+        hpt::DevBuf<float4> g_alb, g_nrm, g_pos;     // hpt_render_guides: per-pixel sums over the call's samples (GuideAccum)
         std::vector<hipEvent_t> marks;               // TIME_KERNELS: five events per pass (eye, photon, grid, gather, end)
         hpt_ppm_stats stats{};
     } pm;

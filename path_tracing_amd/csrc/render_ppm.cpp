@@ -1,5 +1,6 @@
 // Photon mapping's host side (include/hpt.h, hpt_render_ppm and hpt_sppm_*): the pass both share (eye, photon and grid
-// phases), its workspace and statistics, the one-shot render and the progressive state.
+// phases), its workspace and statistics, the one-shot render and the progressive state; and hpt_render_guides, which
+// runs the eye phase alone.
 #include "hpt_host.h"
 
 #include <new>
@@ -32,6 +33,9 @@ constexpr ParamRules kPpmParams{ "hpt_render_ppm renders the whole image on one 
                                  HPT_FLAG_OUTPUT_SUM | HPT_FLAG_TIME_KERNELS | HPT_FLAG_COUNT_WORK,
                                  "hpt_render_ppm accepts HPT_FLAG_OUTPUT_SUM, TIME_KERNELS and COUNT_WORK only",
                                  0, "hpt_params.reserved must be zero for hpt_render_ppm" };
+constexpr ParamRules kGuideParams{ "hpt_render_guides renders the whole image on one device: world must be 0 or 1",
+                                   HPT_FLAG_TIME_KERNELS, "hpt_render_guides accepts HPT_FLAG_TIME_KERNELS only",
+                                   0, "hpt_params.reserved must be zero for hpt_render_guides" };
 constexpr ParamRules kSppmParams{ "progressive photon mapping renders the whole image on one device: world must be 0 or 1",
                                   0, "hpt_sppm_create: hpt_params.flags must be zero (render flags go to hpt_sppm_render)",
                                   0, "hpt_params.reserved must be zero for progressive photon mapping" };
@@ -91,52 +95,69 @@ int ppm_prepare(hpt_scene *s, PpmRun &r, int light_depth, int spl, int passes){
 
 void ppm_mark(hpt_scene *s, const PpmRun &r, int pass, int k){ if(r.timek) hipEventRecord(s->pm.marks[(size_t) pass * 5 + k], nullptr); }
 
+// The trace step and the queue look that the eye and the photon phase share, on pass[0]'s buffers.
+struct PpmStep {
+    hpt_scene *s; const PpmRun &r; hipStream_t st; PassBuffers &w; uint32_t *no_shadow; int budget;
+    PpmStep(hpt_scene *s_, const PpmRun &r_) : s(s_), r(r_), st(nullptr), w(s_->ws.pass[0]), no_shadow(w.counters.get() + 4 * r_.M + 1),
+                                                budget(resume_walk_fits(s_->geo.sd) ? kTraceBudget : 0) {}
+    // closest-hit rays of the queue in cnt[it] (it = 0: the identity queue), the PT path's split trace step
+    void trace(int it, const uint32_t *queue, uint32_t *cnt, uint32_t *lcnt, uint32_t max_items) const {
+        TraceSplit split{ w.lqueue[0].get(), &lcnt[it], w.lqueue[1].get(), no_shadow, budget };
+        launch_trace(st, s->geo.sd, w.pb, w.sb, queue, &cnt[it], max_items, nullptr, nullptr, 0, s->geo.stack_levels, false, nullptr, &split, nullptr, 0u);
+        if(budget > 0) launch_trace_resume(st, s->geo.sd, w.pb, w.sb, true, false, max_items, nullptr, split, nullptr, 0u, w.deep_stack.get());
+    }
+    // the host looks at a queue's length before an iteration that only delta bounces can fill
+    int queue_empty(const uint32_t *cnt, bool &empty) const {
+        HIP_TRY(hipMemcpyAsync(w.h_count, cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        empty = *w.h_count == 0u;
+        return HPT_OK;
+    }
+};
+
+// The eye phase of photon-mapping pass `pidx` (the counters zeroed by the caller): slot = local pixel, stream
+// (seed ^ kPpmEyeKey, pixel, pass), jitter first.  Leaves the hit points in s->pm.hb (their number in r.hp_count(s))
+// and the direct terms in pass[0].pb.col.  hpt_render_guides runs this phase alone.
+int ppm_eye_phase(hpt_scene *s, const PpmRun &r, const PpmStep &step, uint32_t pidx){
+    const hpt_params &P = r.P;
+    hipStream_t st = step.st;
+    PassBuffers &w = step.w;
+    uint32_t *eq = w.counters.get(), *elc = w.counters.get() + r.M;
+    launch_generate(st, r.tl, r.cam, w.pb, &eq[0], 1, pidx, P.seed ^ kPpmEyeKey, nullptr);
+    int cur = 0;
+    for(int it = 0; it < r.eye_iters; ++it){
+        if(it >= 1){ bool empty; if(int rc = step.queue_empty(&eq[it], empty)) return rc; if(empty) break; }
+        const uint32_t *q = it == 0 ? nullptr : w.queue[cur].get();
+        step.trace(it, q, eq, elc, r.n_local);
+        launch_ppm_eye_shade(st, s->geo.sd, w.pb, s->pm.hb, q, &eq[it], r.n_local, w.queue[cur ^ 1].get(), &eq[it + 1], r.hp_count(s), P.max_delta, s->pm.pc.get());
+        cur ^= 1;
+    }
+    return HPT_OK;
+}
+
 // The eye, photon and grid phases of photon-mapping pass `pidx`, marks 0-3 of the call's pass `pass`: the hit points
 // in s->pm.hb (their number in r.hp_count(s)), the direct terms in pass[0].pb.col, the deposits' grid in s->pm.grid.
 int ppm_phases(hpt_scene *s, const PpmRun &r, int pass, uint32_t pidx){
     const hpt_params &P = r.P;
     const PpmFrame &fr = r.fr;
-    const uint32_t n_local = r.n_local, n_ph = r.n_ph, n_dep = r.n_dep;
+    const uint32_t n_ph = r.n_ph, n_dep = r.n_dep;
     const int M = r.M, light_depth = r.light_depth;
-    hipStream_t st = nullptr;
-    PassBuffers &w = s->ws.pass[0];
-    uint32_t *eq = w.counters.get(), *elc = w.counters.get() + M, *pq = w.counters.get() + 2 * M, *plc = w.counters.get() + 3 * M;
-    uint32_t *hp_count = r.hp_count(s), *no_shadow = w.counters.get() + 4 * M + 1;
-    const int budget = resume_walk_fits(s->geo.sd) ? kTraceBudget : 0;
-    // closest-hit rays of the queue in cnt[it] (it = 0: the identity queue), the PT path's split trace step
-    auto trace = [&](int it, const uint32_t *queue, uint32_t *cnt, uint32_t *lcnt, uint32_t max_items){
-        TraceSplit split{ w.lqueue[0].get(), &lcnt[it], w.lqueue[1].get(), no_shadow, budget };
-        launch_trace(st, s->geo.sd, w.pb, w.sb, queue, &cnt[it], max_items, nullptr, nullptr, 0, s->geo.stack_levels, false, nullptr, &split, nullptr, 0u);
-        if(budget > 0) launch_trace_resume(st, s->geo.sd, w.pb, w.sb, true, false, max_items, nullptr, split, nullptr, 0u, w.deep_stack.get());
-    };
-    // the host looks at a queue's length before an iteration that only delta bounces can fill
-    auto queue_empty = [&](const uint32_t *cnt, bool &empty) -> int {
-        HIP_TRY(hipMemcpyAsync(w.h_count, cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        empty = *w.h_count == 0u;
-        return HPT_OK;
-    };
+    const PpmStep step(s, r);
+    hipStream_t st = step.st;
+    PassBuffers &w = step.w;
+    uint32_t *pq = w.counters.get() + 2 * M, *plc = w.counters.get() + 3 * M;
     HIP_TRY(hipMemsetAsync(w.counters.get(), 0, (size_t) r.n_counters * sizeof(uint32_t), st));
     ppm_mark(s, r, pass, 0);
-    // eye pass: slot = local pixel, stream (seed ^ kPpmEyeKey, pixel, pass), jitter first
-    launch_generate(st, r.tl, r.cam, w.pb, &eq[0], 1, pidx, P.seed ^ kPpmEyeKey, nullptr);
-    int cur = 0;
-    for(int it = 0; it < r.eye_iters; ++it){
-        if(it >= 1){ bool empty; if(int rc = queue_empty(&eq[it], empty)) return rc; if(empty) break; }
-        const uint32_t *q = it == 0 ? nullptr : w.queue[cur].get();
-        trace(it, q, eq, elc, n_local);
-        launch_ppm_eye_shade(st, s->geo.sd, w.pb, s->pm.hb, q, &eq[it], n_local, w.queue[cur ^ 1].get(), &eq[it + 1], hp_count, P.max_delta, s->pm.pc.get());
-        cur ^= 1;
-    }
+    if(int rc = ppm_eye_phase(s, r, step, pidx)) return rc;
     ppm_mark(s, r, pass, 1);
     if(n_ph){
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) s->pm.grid.key, (int) r.buckets, n_dep, st));
         launch_ppm_emit(st, s->geo.sd, w.pb, &pq[0], n_ph, r.spl, P.seed, pidx, fr);
-        cur = 0;
+        int cur = 0;
         for(int it = 0; it < r.ph_iters; ++it){
-            if(it >= light_depth){ bool empty; if(int rc = queue_empty(&pq[it], empty)) return rc; if(empty) break; }
+            if(it >= light_depth){ bool empty; if(int rc = step.queue_empty(&pq[it], empty)) return rc; if(empty) break; }
             const uint32_t *q = it == 0 ? nullptr : w.queue[cur].get();
-            trace(it, q, pq, plc, n_ph);
+            step.trace(it, q, pq, plc, n_ph);
             launch_ppm_photon_shade(st, s->geo.sd, w.pb, s->pm.grid, q, &pq[it], n_ph, w.queue[cur ^ 1].get(), &pq[it + 1], light_depth,
                                     P.max_delta, fr, s->pm.pc.get());
             cur ^= 1;
@@ -234,6 +255,67 @@ int hpt_render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth
     launch_finalize(st, tl, s->ws.accum.get(), s->ws.local_own.get(), (P.flags & HPT_FLAG_OUTPUT_SUM) ? 1.0f : (float) spp);
     rc = untile_to_host(s, tl, st, host_image, s->tm.ev_stop);
     if(rc) return rc;
+    return ppm_collect_stats(s, r, spp);
+}
+
+// First-hit guide buffers (include/hpt.h): PPM's eye pass per sample, its hit points summed per pixel, the means
+// un-tiled into whichever host images the caller asks for.  Blocking, one device.
+int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
+                      float *albedo, float *normal, float *position, float *coverage){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(!camera) return fail(HPT_ERR_INVALID, "null camera");
+    if(spp < 1) return fail(HPT_ERR_INVALID, "spp must be >= 1");
+    if(!albedo && !normal && !position && !coverage) return fail(HPT_ERR_INVALID, "hpt_render_guides: every output is null");
+    if(int rcd = on_scene_device(s)) return rcd;
+    PpmRun r;
+    hpt_params &P = r.P;
+    if(int rcp = take_params(params, kGuideParams, P)) return rcp;
+    int rc = make_tiling(W, H, &P, r.tl);
+    if(rc) return rc;
+    ppm_scene_bounds(s);
+    for(int a = 0; a < 3; ++a){ r.fr.smin[a] = s->pm.min[a]; r.fr.smax[a] = s->pm.max[a]; }
+    r.fr.cell = 0.05f; r.fr.r2 = 0.05f * 0.05f;                             // no photons: the grid is not built
+    set_camera(r.cam, camera);
+    rc = ppm_prepare(s, r, 1, 0, spp);
+    if(rc) return rc;
+    const size_t n_local = r.n_local;
+    hipError_t e = reserve_all(n_local, s->pm.g_alb, s->pm.g_nrm, s->pm.g_pos);
+    if(e != hipSuccess) return fail_hip("guide accumulators", e);
+    const GuideAccum ga{ s->pm.g_alb.get(), s->pm.g_nrm.get(), s->pm.g_pos.get() };
+
+    const PpmStep step(s, r);
+    hipStream_t st = step.st;
+    HIP_TRY(hipMemsetAsync(s->pm.pc.get(), 0, sizeof(PpmCounters), st));
+    HIP_TRY(hipMemsetAsync(ga.alb_cnt, 0, n_local * sizeof(float4), st));
+    HIP_TRY(hipMemsetAsync(ga.nrm, 0, n_local * sizeof(float4), st));
+    HIP_TRY(hipMemsetAsync(ga.pos, 0, n_local * sizeof(float4), st));
+    HIP_TRY(hipEventRecord(s->tm.ev_start, st));
+    for(int pass = 0; pass < spp; ++pass){
+        HIP_TRY(hipMemsetAsync(step.w.counters.get(), 0, (size_t) r.n_counters * sizeof(uint32_t), st));
+        ppm_mark(s, r, pass, 0);
+        rc = ppm_eye_phase(s, r, step, (uint32_t) ((int64_t) P.sample_offset + pass));
+        if(rc) return rc;
+        launch_guides_accumulate(st, s->geo.sd, s->pm.hb, r.hp_count(s), r.n_local, ga);
+        for(int k = 1; k <= 4; ++k) ppm_mark(s, r, pass, k);                // the eye phase is the only one: ms_eye
+    }
+    float *outs[4] = { albedo, normal, position, coverage };
+    const size_t npx = (size_t) W * H;
+    std::vector<float> tmp;
+    for(int which = 0; which < 4; ++which){
+        if(!outs[which]) continue;
+        launch_guides_resolve(st, r.n_local, ga, which, s->ws.local_own.get());
+        launch_untile(st, r.tl, s->ws.local_own.get(), s->ws.image_own.get());
+        HIP_TRY(hipGetLastError());
+        if(which < 3){
+            HIP_TRY(hipMemcpy(outs[which], s->ws.image_own.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            tmp.resize(npx * 3);
+            HIP_TRY(hipMemcpy(tmp.data(), s->ws.image_own.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
+            for(size_t k = 0; k < npx; ++k) coverage[k] = tmp[k * 3];
+        }
+    }
+    HIP_TRY(hipEventRecord(s->tm.ev_stop, st));
+    HIP_TRY(hipEventSynchronize(s->tm.ev_stop));
     return ppm_collect_stats(s, r, spp);
 }
 
