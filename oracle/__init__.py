@@ -19,7 +19,8 @@ class PtOpts(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("rng_mode", C.c_int), ("trig_mode", C.c_int),
                 ("sample_offset", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int),
                 ("threads", C.c_int), ("glass_shadow_opaque", C.c_int), ("max_delta", C.c_int),
-                ("output_sum", C.c_int), ("russian_roulette", C.c_int), ("ball_draw_reversed", C.c_int)]
+                ("output_sum", C.c_int), ("russian_roulette", C.c_int), ("ball_draw_reversed", C.c_int),
+                ("rcp_nudge_ulps", C.c_int), ("rcp_nudge_mask", C.c_int)]
 
 
 class PtStats(C.Structure):
@@ -62,11 +63,14 @@ def _p(a):
 
 def pt_render(lights, spheres, tris, camera, W, H, max_depth, spp, *, seed=1, rng_mode=0, trig_mode=0,
               sample_offset=0, window=None, threads=0, glass_shadow_opaque=0, max_delta=64, output_sum=False, ball_draw_reversed=False, russian_roulette=False,
-              bvh=None):
+              bvh=None, rcp_nudge=(0, 0)):
     """Unidirectional PT + NEE (restates src/pt_cu.cu:20-250).  Returns (image[H,W,3] f32, stats dict).
     Pixels outside `window` = (x0, y0, x1, y1) stay zero.  bvh: the dict path_tracing_amd.export_bvh_host /
     Scene.export_bvh return -- triangles are then found by walking that tree on the host (same image as the scan) and
-    stats carry boxes_* / tris_*: the independent count behind the bench's algorithmic bytes."""
+    stats carry boxes_* / tris_*: the independent count behind the bench's algorithmic bytes.
+    rcp_nudge = (ulps, sign_mask), with bvh only: the walk's three reciprocals are moved `ulps` float neighbours before
+    use, up where the axis bit of sign_mask (1 x, 2 y, 4 z) is set and down otherwise -- a reciprocal that is not
+    correctly rounded.  Triangle tests and the scan are untouched, so a conservative tree still gives the scan's image."""
     img = np.zeros((H, W, 3), np.float32)
     o = PtOpts()
     o.seed, o.rng_mode, o.trig_mode, o.sample_offset = int(seed), rng_mode, trig_mode, sample_offset
@@ -74,6 +78,7 @@ def pt_render(lights, spheres, tris, camera, W, H, max_depth, spp, *, seed=1, rn
     o.threads, o.glass_shadow_opaque, o.max_delta, o.output_sum = threads, glass_shadow_opaque, max_delta, int(output_sum)
     o.ball_draw_reversed = int(ball_draw_reversed)
     o.russian_roulette = int(russian_roulette)
+    o.rcp_nudge_ulps, o.rcp_nudge_mask = int(rcp_nudge[0]), int(rcp_nudge[1])
     st = PtStats()
     cam = np.ascontiguousarray(camera)
     lights = np.ascontiguousarray(lights)

@@ -39,6 +39,8 @@ struct OraclePtOpts {
     int russian_roulette;   // 1: unbiased roulette after every non-delta bounce (NOT in the reference; default off)
     int ball_draw_reversed; // 1: the three uniforms of a unit-ball try fill z,y,x (argument evaluation
                             //    order of make_float3(u(),u(),u()) is unspecified, geometric.cuh:410)
+    int rcp_nudge_ulps;     // host walk only: each per-axis reciprocal is moved this many float neighbours before use,
+    int rcp_nudge_mask;     //    up where the axis bit (1 = x, 2 = y, 4 = z) is set, down otherwise (0 ulps = exact division)
 };
 
 struct OraclePtStats {
@@ -75,6 +77,7 @@ struct Scene {
     const RTriangle *tris; int nt;
     std::vector<float> cos_cutoff;     // cosf(light.cutoff), hoisted (pt_cu.cu:73,79,168)
     const OracleBvh *bvh = nullptr;    // non-null: triangles are found by walking the library's tree instead of the scan
+    int nudge_ulps = 0, nudge_mask = 0; // OraclePtOpts::rcp_nudge_*: the walk's reciprocals only, never a triangle test or the scan
 };
 
 // ---- host walk of the exported tree ----------------------------------------------------------
@@ -86,13 +89,25 @@ struct Scene {
 // preferring the lower ordinal at equal t.
 constexpr uint32_t kLeaf = 0x80000000u, kNoChild = 0xFFFFFFFFu, kDone = 0xFFFFFFFEu;
 
+// `ulps` float neighbours away from v, up or down: what a reciprocal that is not correctly rounded may return
+static inline float nudged(float v, int ulps, bool up){
+    for(int k = 0; k < ulps; ++k) v = nextafterf(v, up ? INFINITY : -INFINITY);
+    return v;
+}
+
 struct WalkRay {
     float ix, iy, iz, ox, oy, oz;
-    WalkRay(const OracleBvh &b, V3 ro, V3 rd){
+    WalkRay(const Scene &sc, V3 ro, V3 rd){
+        const OracleBvh &b = *sc.bvh;
         float dx = fabsf(rd.x) > 1e-20f ? rd.x : copysignf(1e-20f, rd.x);
         float dy = fabsf(rd.y) > 1e-20f ? rd.y : copysignf(1e-20f, rd.y);
         float dz = fabsf(rd.z) > 1e-20f ? rd.z : copysignf(1e-20f, rd.z);
         ix = 1.0f / dx; iy = 1.0f / dy; iz = 1.0f / dz;
+        if(sc.nudge_ulps > 0){
+            ix = nudged(ix, sc.nudge_ulps, (sc.nudge_mask & 1) != 0);
+            iy = nudged(iy, sc.nudge_ulps, (sc.nudge_mask & 2) != 0);
+            iz = nudged(iz, sc.nudge_ulps, (sc.nudge_mask & 4) != 0);
+        }
         ox = (b.qorigin[0] - ro.x) * ix; oy = (b.qorigin[1] - ro.y) * iy; oz = (b.qorigin[2] - ro.z) * iz;
         ix *= b.qscale[0]; iy *= b.qscale[1]; iz *= b.qscale[2];
     }
@@ -126,7 +141,7 @@ static inline uint32_t node_step(const OracleBvh &b, const WalkRay &r, uint32_t 
 // closest triangle hit below best_t (ties: lower ordinal); returns the INPUT index of the triangle or -1
 int walk_closest(const Scene &sc, V3 ro, V3 rd, float &best_t, uint32_t best_ord, uint64_t &boxes, uint64_t &tris){
     const OracleBvh &b = *sc.bvh;
-    WalkRay r(b, ro, rd);
+    WalkRay r(sc, ro, rd);
     uint32_t stk[128]; int sp = 0;
     uint32_t cur = 0u;
     int found = -1;
@@ -151,7 +166,7 @@ int walk_closest(const Scene &sc, V3 ro, V3 rd, float &best_t, uint32_t best_ord
 // true when an opaque triangle blocks (1e-3, max_d)
 bool walk_any(const Scene &sc, V3 p1, V3 dir, float max_d, bool glass_opaque, uint64_t &boxes, uint64_t &tris){
     const OracleBvh &b = *sc.bvh;
-    WalkRay r(b, p1, dir);
+    WalkRay r(sc, p1, dir);
     uint32_t stk[128]; int sp = 0;
     uint32_t cur = 0u;
     for(;;){
@@ -447,6 +462,7 @@ int oracle_pt_render_bvh(const void *lights, int nl, const void *spheres, int ns
     for(int i = 0; i < nl; ++i) sc.cos_cutoff[i] = cosf(sc.lights[i].cutoff);
     RCamera cam; memcpy(&cam, camera, sizeof cam);
     OraclePtOpts o = *opts;
+    sc.nudge_ulps = o.rcp_nudge_ulps; sc.nudge_mask = o.rcp_nudge_mask;
     int x1 = o.x1 > 0 ? std::min(o.x1, W) : W, y1 = o.y1 > 0 ? std::min(o.y1, H) : H;
     int x0 = std::max(o.x0, 0), y0 = std::max(o.y0, 0);
     if(o.max_delta <= 0) o.max_delta = 64;

@@ -209,11 +209,9 @@ def edge_case(which):
 
 
 # ---- far from the origin ---------------------------------------------------------------------------------------------
-def far_case(seed=FAR_SEED):
-    """_random_scene(seed) scaled by FAR_SCALE and moved by FAR_SHIFT, camera too; illum * FAR_SCALE^2 keeps the
-    irradiance.  Box tests and epsilons there work on coordinates of 200-600 with an ulp of 3e-5 to 6e-5."""
-    L, sp, tr = _random_scene(sio, seed)
-    s, sh = np.float32(FAR_SCALE), np.asarray(FAR_SHIFT, np.float32)
+def transform_scene(L, sp, tr, scale, shift):
+    """Copies of the records scaled by `scale` and moved by `shift`; illum * scale^2 keeps the irradiance."""
+    s, sh = np.float32(scale), np.asarray(shift, np.float32)
     L, sp, tr = L.copy(), sp.copy(), tr.copy()
     for k in ("v0", "v1", "v2"):
         tr[k] = tr[k] * s + sh
@@ -224,8 +222,19 @@ def far_case(seed=FAR_SEED):
     L["light_ball"]["r"] = L["light_ball"]["r"] * s
     L["illum"] = L["illum"] * (s * s)
     L["light_ball"]["mtl_old"]["Kd"] = L["light_ball"]["mtl_old"]["Kd"] * (s * s)
-    eye = tuple(float(v) for v in np.asarray(sio.CORNELL_EYE, np.float32) * s + sh)
-    look = tuple(float(v) for v in np.asarray(sio.CORNELL_LOOK, np.float32) * s + sh)
+    return L, sp, tr
+
+
+def transform_point(p, scale, shift):
+    return tuple(float(v) for v in np.asarray(p, np.float32) * np.float32(scale) + np.asarray(shift, np.float32))
+
+
+def far_case(seed=FAR_SEED):
+    """_random_scene(seed) scaled by FAR_SCALE and moved by FAR_SHIFT, camera too; illum * FAR_SCALE^2 keeps the
+    irradiance.  Box tests and epsilons there work on coordinates of 200-600 with an ulp of 3e-5 to 6e-5."""
+    L, sp, tr = transform_scene(*_random_scene(sio, seed), FAR_SCALE, FAR_SHIFT)
+    eye = transform_point(sio.CORNELL_EYE, FAR_SCALE, FAR_SHIFT)
+    look = transform_point(sio.CORNELL_LOOK, FAR_SCALE, FAR_SHIFT)
     return L, sp, tr, single_group(sp, tr), (eye, look, sio.CORNELL_UP, 50.0), 32, 24, 3, 4, 2, 2, seed, 0
 
 
