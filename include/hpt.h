@@ -359,13 +359,18 @@ void hpt_tonemap_reference(const float *linear_rgb, unsigned char *rgb8, int64_t
  * HPT_DENOISE_DEMODULATE (valid pixels), else colour[p].  Taps h = {1/16, 1/4, 3/8, 1/4, 1/16}.  Falloff
  * e(x) = q^8, q = fmaxf(0, 1 - x * 0.125f), by three squarings: a polynomial stand-in for exp(-x) (the library calls
  * no device transcendental on a path that is compared bit for bit) with compact support, e(x) = 0 exactly for x >= 8.
- * Level k = 0 .. iterations-1, stride s = 2^k; sc = sigma_color * 2^-k; inv_c = 1 / (sc * sc), inv_n = 1 / sigma_normal^2,
- * inv_p = 1 / sigma_position^2, computed in float on the host.  An invalid pixel keeps its value.  For a valid p = (x, y):
+ * Level k = 0 .. iterations-1, stride s = 2^k; sc = sigma_color * 2^-k; inv_c = inv(sc), inv_n = inv(sigma_normal),
+ * inv_p = inv(sigma_position) with inv(s) = fminf(1.0f / (s * s), FLT_MAX), computed in float on the host.  The clamp acts
+ * where s * s is so small (a denormal, or 0) that the quotient is inf: unclamped, the centre tap's x = 0 * inf would be
+ * NaN and its weight 0.  With FLT_MAX the centre weighs 9/64 as always and another tap takes part only where its
+ * difference squares to (almost) zero, which is the limit of the definition.  A sigma so large that s * s overflows
+ * gives inv = 0, every x = 0 and e = 1: the term is as good as off.  An invalid pixel keeps its value.  For a valid p = (x, y):
  * for j = -2..2 (outer), i = -2..2 (inner), q = (x + i s, y + j s), skipped when outside the image or invalid:
  *   xc = (dc.x dc.x + dc.y dc.y + dc.z dc.z) * inv_c with dc = c_k(p) - c_k(q);  xn likewise from normal[p] - normal[q];
  *   t = n(p).x d.x + n(p).y d.y + n(p).z d.z with d = position[q] - position[p] (q's distance from p's tangent plane),
  *   xp = t * t * inv_p;   w = h[j+2] * h[i+2] * e(xc) * e(xn) * e(xp), left to right (a term switched off is 1.0f);
- *   sum += c_k(q) * w per channel, wsum += w;   c_{k+1}(p) = sum / wsum (the centre tap makes wsum >= 9/64).
+ *   sum += c_k(q) * w per channel, wsum += w;   c_{k+1}(p) = sum / wsum.  The centre tap has x = 0 in every term at every
+ *   sigma > 0 (inv is finite), so wsum >= 9/64.
  *   A valid pixel whose 24 other taps are all skipped keeps its value, c_{k+1}(p) = c_k(p): fl(fl(c * 9/64) / (9/64))
  *   is not c for every float, and a level whose stride exceeds the image must hand its input on unchanged.
  * Output c_n(p) * a(p) with DEMODULATE, else c_n(p); an invalid pixel outputs colour[p] exactly.  The tap order is part

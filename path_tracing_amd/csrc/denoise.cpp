@@ -2,6 +2,7 @@
 // ping-pong colour buffers, the argument checks, the per-level constants and the optional HIP-event timing.
 #include "hpt_host.h"
 
+#include <cfloat>
 #include <cmath>
 #include <new>
 
@@ -51,6 +52,10 @@ int take_denoise_params(const hpt_denoise_params *p, hpt_denoise_params &D){
     if(D.sigma_position == 0.0f) D.sigma_position = 0.05f;
     return HPT_OK;
 }
+
+// 1 / (s * s), FLT_MAX where s * s is so small that the quotient overflows: an infinite inverse would turn the centre
+// tap's zero difference into NaN (include/hpt.h, "the filter")
+float inv_sq(float s){ return fminf(1.0f / (s * s), FLT_MAX); }
 
 bool overlap(const void *a, const void *b, size_t bytes){
     const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
@@ -111,12 +116,12 @@ int hpt_denoiser_run(hpt_denoiser *d, const void *d_linear_rgb, void *d_out, con
     DenoiseLevel L{};
     L.W = d->W; L.H = d->H; L.demod = demod;
     L.use_c = D.sigma_color > 0.0f; L.use_n = D.sigma_normal > 0.0f; L.use_p = D.sigma_position > 0.0f;
-    L.inv_n = L.use_n ? 1.0f / (D.sigma_normal * D.sigma_normal) : 0.0f;
-    L.inv_p = L.use_p ? 1.0f / (D.sigma_position * D.sigma_position) : 0.0f;
+    L.inv_n = L.use_n ? inv_sq(D.sigma_normal) : 0.0f;
+    L.inv_p = L.use_p ? inv_sq(D.sigma_position) : 0.0f;
     for(int k = 0; k < D.iterations; ++k){
         L.stride = 1 << k;
         const float sc = D.sigma_color * ldexpf(1.0f, -k);      // the colour tolerance halves per level
-        L.inv_c = L.use_c ? 1.0f / (sc * sc) : 0.0f;
+        L.inv_c = L.use_c ? inv_sq(sc) : 0.0f;
         const int last = k + 1 == D.iterations;
         launch_atrous(st, L, d->g, d->ping[k & 1].get(), d->ping[(k + 1) & 1].get(), (float *) d_out, last);
         if(timed) HIP_TRY(hipEventRecord(d->ev[k + 2], st));

@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- CPU restatement of the edge-avoiding a-trous filter as include/hpt.h ("guides and
 // denoiser") defines it: every operation an IEEE float operation in the order written there.  Built by
 // tests/denoise_oracle.py with ppm_oracle.CXXFLAGS (-ffp-contract=off), so the HIP kernels must match it bit for bit.
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -15,6 +16,9 @@ float falloff(float x){
     q *= q; q *= q; q *= q;
     return q;
 }
+
+// the clamp keeps 0 * inv at the centre tap from being 0 * inf
+float inv_sq(float s){ return fminf(1.0f / (s * s), FLT_MAX); }
 
 } // namespace
 
@@ -41,12 +45,12 @@ extern "C" int denoise_oracle_run(const float *colour, const float *albedo, cons
     }
     auto keep = [&](int level){ if(levels_out) memcpy(levels_out + (size_t) level * npx * 3, cur.data(), npx * 3 * sizeof(float)); };
     keep(0);
-    const float inv_n = use_n ? 1.0f / (sigma_normal * sigma_normal) : 0.0f;
-    const float inv_p = use_p ? 1.0f / (sigma_position * sigma_position) : 0.0f;
+    const float inv_n = use_n ? inv_sq(sigma_normal) : 0.0f;
+    const float inv_p = use_p ? inv_sq(sigma_position) : 0.0f;
     for(int k = 0; k < iterations; ++k){
         const int s = 1 << k;
         const float sc = sigma_color * ldexpf(1.0f, -k);
-        const float inv_c = use_c ? 1.0f / (sc * sc) : 0.0f;
+        const float inv_c = use_c ? inv_sq(sc) : 0.0f;
 #pragma omp parallel for schedule(static)
         for(int y = 0; y < H; ++y) for(int x = 0; x < W; ++x){
             const size_t p = (size_t) y * W + x;

@@ -1,6 +1,8 @@
 """Guide buffers on the MI355X: Scene.render_guides against the oracle (tests/guides_oracle.cpp) byte for byte, NULL
 outputs, argument errors, other renders on the scene untouched by it, and the end-to-end check that denoising a
-4 spp path-traced image with the default parameters brings it closer to a 4096 spp one."""
+4 spp path-traced image with the default parameters brings it closer to a 4096 spp one.  Beyond the first cases: 17
+samples (the count is integer bits in a float lane), a sample_offset that crosses 2^31 inside one call, other tile
+edges, 1 x 1 and one-row images, and a workspace that grows, shrinks and grows again."""
 import ctypes as C
 
 import numpy as np
@@ -43,6 +45,63 @@ def test_render_guides_matches_the_oracle(hpt, sio, glib, case):
     if name == "input_delta_cap":
         full, _ = guides_oracle.render(glib, L, sp, tr, cam, W, H, spp, seed=11)
         assert full["coverage"].sum() > ref["coverage"].sum()          # the cap ends paths the default lets through
+
+
+def _check_guides(hpt, glib, scene, L, sp, tr, cam, W, H, spp, **kw):
+    got = scene.render_guides(cam, W, H, spp, hpt.make_params(seed=11, **kw))
+    okw = {k: v for k, v in kw.items() if k != "tile"}          # the images do not depend on the tile edge
+    ref, hp = guides_oracle.render(glib, L, sp, tr, cam, W, H, spp, seed=11, **okw)
+    assert scene.ppm_stats()["hit_points"] == sum(hp)
+    for k in KEYS:
+        assert got[k].tobytes() == ref[k].tobytes(), (k, float(np.abs(got[k] - ref[k]).max()))
+    return got, ref
+
+
+def test_seventeen_samples_count_in_a_float_lane(hpt, sio, glib):
+    W, H, spp = 23, 19, 17
+    L, sp, tr, cam = _load(sio, "input", W, H)
+    with hpt.Scene(L, sp, tr) as s:
+        _, ref = _check_guides(hpt, glib, s, L, sp, tr, cam, W, H, spp)
+    cov = ref["coverage"]
+    assert ((cov > 0) & (cov < spp)).any() and (cov == spp).any() and cov.max() == spp
+
+
+def test_sample_offset_crosses_2_to_the_31_within_one_call(hpt, sio, glib):
+    W, H = 50, 37
+    L, sp, tr, cam = _load(sio, "input", W, H)
+    with hpt.Scene(L, sp, tr) as s:
+        _, ref = _check_guides(hpt, glib, s, L, sp, tr, cam, W, H, 4, sample_offset=2 ** 31 - 2)
+        _, low = _check_guides(hpt, glib, s, L, sp, tr, cam, W, H, 2, sample_offset=2 ** 31 - 2)
+    assert ref["coverage"].max() == 4 and ref["normal"].tobytes() != low["normal"].tobytes()     # passes 2^31 and 2^31 + 1 count
+
+
+@pytest.mark.parametrize("tile", [8, 64])
+def test_a_non_default_tile_gives_the_same_guides(hpt, sio, glib, tile):
+    W, H = 50, 37
+    L, sp, tr, cam = _load(sio, "input", W, H)
+    with hpt.Scene(L, sp, tr) as s:
+        got, _ = _check_guides(hpt, glib, s, L, sp, tr, cam, W, H, 3, tile=tile)
+        default = s.render_guides(cam, W, H, 3, hpt.make_params(seed=11))
+    assert all(got[k].tobytes() == default[k].tobytes() for k in KEYS)
+
+
+@pytest.mark.parametrize("size", [(1, 1), (40, 1)])
+def test_one_pixel_and_one_row(hpt, sio, glib, size):
+    W, H = size
+    L, sp, tr, cam = _load(sio, "input", W, H)
+    with hpt.Scene(L, sp, tr) as s:
+        _, ref = _check_guides(hpt, glib, s, L, sp, tr, cam, W, H, 5)
+    assert ref["coverage"].max() == 5
+
+
+def test_the_guide_workspace_grows_shrinks_and_grows(hpt, sio, glib):
+    L, sp, tr, big = _load(sio, "input", 64, 56)
+    small = _load(sio, "input", 9, 7)[3]
+    with hpt.Scene(L, sp, tr) as s:
+        first, _ = _check_guides(hpt, glib, s, L, sp, tr, big, 64, 56, 3)
+        _check_guides(hpt, glib, s, L, sp, tr, small, 9, 7, 3)
+        third, _ = _check_guides(hpt, glib, s, L, sp, tr, big, 64, 56, 3)
+    assert all(first[k].tobytes() == third[k].tobytes() for k in KEYS) and first["coverage"].max() == 3
 
 
 def test_null_outputs(hpt, sio):
