@@ -151,9 +151,12 @@ struct Builder {
 
     static constexpr int kBins = 16;
     // Subtrees of more than kParallelMin triangles are built on their own host thread while the parent goes on with the
-    // sibling (at most as many threads at a time as the process may use CPUs).  The tree does not depend on it: a subtree over
-    // prims[first, first + count) only reads and permutes that range, its triangles keep that range of leaf slots
-    // (leaf order = the final order of prims), and node numbers -- the only thing the thread schedule decides -- are
+    // sibling (at most as many threads at a time as the process may use CPUs).  The tree does not depend on it, nor on how
+    // many CPUs there are: a subtree over prims[first, first + count) only reads and permutes that range, and which
+    // primitives go left at a node is a function of the node's set alone, so every leaf gets the same SET of triangles and
+    // the same range of leaf slots whichever partition ran above it.  The ORDER inside a range is not such a function -- the
+    // big nodes' partition is stable and std::partition is not, and which of the two a node gets depends on the CPU count
+    // -- so make_leaf puts every leaf into input order.  Node numbers, the one thing the thread schedule decides, are
     // replaced by the breadth-first renumbering afterwards.
     static constexpr int kParallelMin = 8192;
     static int parallel_levels(){ int l = 0; while((2 << l) <= usable_cpus() && l < 6) ++l; return l; }     // 2^levels subtree threads at most
@@ -170,7 +173,10 @@ struct Builder {
         }
     }
 
-    uint32_t make_leaf(int first, int count) const {
+    uint32_t make_leaf(int first, int count){
+        // canonical leaf order: by input index (a leaf holds 8 triangles at most: insertion sort)
+        for(int i = first + 1; i < first + count; ++i)
+            for(int j = i; j > first && prims[j].index < prims[j - 1].index; --j) std::swap(prims[j], prims[j - 1]);
         return kLeafFlag | (((uint32_t) first + tri_base) << 3) | (uint32_t) (count - 1);
     }
 
@@ -215,6 +221,13 @@ struct Builder {
         return build_node(first, count, depth, bb, cb, par_levels);
     }
 
+    // bin of a centroid: (int) of the scaled offset clamped to [0, kBins) -- written so that a NaN or an offset beyond int
+    // (centroids of records with non-finite coordinates, where a caller lets them in) is never converted: NaN goes to bin 0
+    static int bin_of(float cen, float lo, float scale){
+        const float f = (cen - lo) * scale;
+        return f >= 1.0f ? (f < (float) kBins ? (int) f : kBins - 1) : 0;
+    }
+
     struct Bins { Box box[3][kBins]; int cnt[3][kBins]; void reset(){ for(int a = 0; a < 3; ++a) for(int b = 0; b < kBins; ++b){ box[a][b].reset(); cnt[a][b] = 0; } } };
 
     // Builds the subtree over prims[first, first+count) whose primitive boxes span bb and whose centroids span cb; returns its
@@ -245,8 +258,7 @@ struct Builder {
                     const Prim &p = prims[i];
                     for(int ax = 0; ax < 3; ++ax){
                         if(!use[ax]) continue;
-                        int b = (int) ((p.cen[ax] - cb.mn[ax]) * scale[ax]);
-                        b = std::min(std::max(b, 0), kBins - 1);
+                        const int b = bin_of(p.cen[ax], cb.mn[ax], scale[ax]);
                         bins.box[ax][b].grow(p.box); bins.cnt[ax][b]++;
                     }
                 }
@@ -279,11 +291,7 @@ struct Builder {
             }
             if(best_axis >= 0){
                 const float sc = scale[best_axis], lo = cb.mn[best_axis];
-                auto goes_left = [&](const Prim &p){
-                    int b = (int) ((p.cen[best_axis] - lo) * sc);
-                    b = std::min(std::max(b, 0), kBins - 1);
-                    return b <= best_bin;
-                };
+                auto goes_left = [&](const Prim &p){ return bin_of(p.cen[best_axis], lo, sc) <= best_bin; };
                 if(big){
                     // stable partition through a scratch copy: every chunk counts (and gathers the children's bounds), then
                     // scatters to the offsets the counts give
@@ -327,7 +335,9 @@ struct Builder {
             mid = first + count / 2;
             std::nth_element(prims.begin() + first, prims.begin() + mid, prims.begin() + first + count,
                              [&](const Prim &a, const Prim &b){
-                                 if(a.cen[axis] != b.cen[axis]) return a.cen[axis] < b.cen[axis];
+                                 // (a NaN centroid sorts as +inf: '<' alone is no strict weak order among NaNs)
+                                 const float ca = a.cen[axis] == a.cen[axis] ? a.cen[axis] : INFINITY, cb2 = b.cen[axis] == b.cen[axis] ? b.cen[axis] : INFINITY;
+                                 if(ca != cb2) return ca < cb2;
                                  return a.index < b.index;
                              });
             range_bounds(first, mid - first, lbb, lcb, false);
@@ -449,20 +459,47 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
     if(const char *e = getenv("HPT_MAX_LEAF")){ int v = atoi(e); if(v >= 1 && v <= 8) B.max_leaf = v; }
 #endif
     B.prims.resize(nt);
+    // Dead triangles.  A record whose edge v1 - v0 or v2 - v0 has a component that is not finite -- a NaN or infinite
+    // coordinate, or two finite ones whose difference overflows -- is hit by no ray: in hit_triangle (pt_device_math.h; the
+    // reference's geometric.cuh:261-291) the determinant a = dot(e1, cross(rd, e2)) is then infinite or NaN, f = 1 / a is 0 or
+    // NaN, and t = f * (...) is 0 or NaN, which `t > kEps` rejects.  Such a record keeps its leaf slot (the slots are a
+    // permutation of the input; the scan kernels index them) but must not reach a box, pad_abs or the grid, where one
+    // infinity makes every plane NaN and every ray visit every node: it enters the build as a point at the low corner of the
+    // live triangles' box (the origin when there is none).
     Box scene_box; scene_box.reset();
     {   std::vector<Box> part((size_t) kChunks);
+        std::vector<std::vector<uint32_t>> dead((size_t) kChunks);          // input indices of the dead triangles, per chunk
         for(Box &b : part) b.reset();
         parallel_chunks((size_t) nt, [&](int c, size_t b0, size_t e0){
             for(size_t i = b0; i < e0; ++i){
                 Prim &p = B.prims[i];
-                p.box.reset();
-                p.box.grow(tris[i].v0); p.box.grow(tris[i].v1); p.box.grow(tris[i].v2);
-                for(int a = 0; a < 3; ++a) p.cen[a] = 0.5f * (p.box.mn[a] + p.box.mx[a]);
+                const RefTriangle &t = tris[i];
                 p.index = (uint32_t) i;
+                bool live = true;
+                for(int a = 0; a < 3; ++a) live = live && std::isfinite(t.v1[a] - t.v0[a]) && std::isfinite(t.v2[a] - t.v0[a]);
+                if(!live){
+                    // placed below, once the live triangles' box is known
+                    for(int a = 0; a < 3; ++a) p.box.mn[a] = p.box.mx[a] = p.cen[a] = 0.0f;
+                    dead[(size_t) c].push_back((uint32_t) i);
+                    continue;
+                }
+                p.box.reset();
+                p.box.grow(t.v0); p.box.grow(t.v1); p.box.grow(t.v2);
+                for(int a = 0; a < 3; ++a) p.cen[a] = 0.5f * (p.box.mn[a] + p.box.mx[a]);
                 part[(size_t) c].grow(p.box);
             }
         });
         for(const Box &b : part) scene_box.grow(b);
+        size_t ndead = 0; for(const std::vector<uint32_t> &d : dead) ndead += d.size();
+        if(ndead > 0){
+            float at[3];
+            for(int a = 0; a < 3; ++a) at[a] = ndead < (size_t) nt ? scene_box.mn[a] : 0.0f;
+            for(const std::vector<uint32_t> &d : dead) for(uint32_t i : d){
+                Prim &p = B.prims[i];
+                for(int a = 0; a < 3; ++a) p.box.mn[a] = p.box.mx[a] = p.cen[a] = at[a];
+            }
+            scene_box.grow(at);
+        }
     }
     float extent = 0.0f;
     if(nt > 0) for(int a = 0; a < 3; ++a){
