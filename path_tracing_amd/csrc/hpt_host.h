@@ -103,7 +103,7 @@ struct hpt_scene {
         hpt::DevBuf<float4> org_max, dir, contrib;                                          // sb
         hpt::PathBuf pb{}; hpt::ShadowBuf sb{};      // views of the buffers above, filled by ensure_pass
         hpt::DevBuf<uint32_t> queue[2];              // path queues (ping-pong)
-        hpt::DevBuf<uint32_t> squeue;                // shadow queue (path slots)
+        hpt::DevBuf<uint32_t> squeue;                // shadow queue (record indices)
         hpt::DevBuf<uint32_t> lqueue[2];             // rays set aside by the first trace launch: closest-hit, shadow
         hpt::DevBuf<uint32_t> deep_stack;            // stack levels of the resume launch past its LDS share (launch_trace_resume)
         hpt::DevBuf<uint32_t> counters;

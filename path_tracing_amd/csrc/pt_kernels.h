@@ -30,12 +30,14 @@ struct PathBuf {
     uint2 *hit;          // extend result: as_uint(t) | primitive code
 };
 
-// Pending shadow ray of a path, structure of arrays indexed by path slot (the shadow queue
-// itself is a compacted list of path slots).
+// Pending shadow rays of an iteration, structure of arrays indexed by RECORD index: k_shade stores the records of a
+// workgroup's chunk densely from the chunk's first queue position on (a path has at most one pending shadow ray, so a
+// chunk never has more records than queue positions, and never more than there are path slots).  The shadow queue is a
+// compacted list of record indices; the path slot a record belongs to travels in contrib.w.
 struct ShadowBuf {
     float4 *org_max;     // p1 xyz | max_d
     float4 *dir;         // unit direction xyz | unused
-    float4 *contrib;     // clamped contribution if unoccluded xyz | unused
+    float4 *contrib;     // clamped contribution if unoccluded xyz | path slot (as bits)
 };
 
 // Image tiling shared by ray generation, resolve and untile (see DESIGN.md "Tiling").

@@ -299,14 +299,15 @@ void k_connect(SceneDev sc, PathBuf pb, ShadowBuf sb, const uint32_t *squeue, co
     Tally tally; tally.boxes = 0; tally.tris = 0; tally.steps = 0; tally.wave_steps = 0;
     uint32_t rays = 0;
     for(uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock){
-        uint32_t path = squeue[i];
-        float4 a = sb.org_max[path], b = sb.dir[path];
+        uint32_t r = squeue[i];                                // shadow record index (k_shade)
+        float4 a = sb.org_max[r], b = sb.dir[r];
         uint32_t s0 = tally.steps;
         bool vis = segment_visible<BRUTE, COUNT>(sc, xyz(a), xyz(b), a.w, stk, tally);
         ++rays;
         if(COUNT) tally.wave_steps += wave_max_u32(tally.steps - s0);
         if(vis){
-            float4 c = sb.contrib[path];
+            float4 c = sb.contrib[r];
+            uint32_t path = f2u(c.w);
             float4 col = pb.col[path];
             col.x = col.x + c.x; col.y = col.y + c.y; col.z = col.z + c.z;
             pb.col[path] = col;
@@ -358,7 +359,10 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
     // ballot + mbcnt prefix, one LDS atomic per wave) and flushed with ONE global atomic per
     // queue: same-address global atomics saturate near 88 per microsecond on this chip.
     __shared__ uint32_t s_next[kShadeChunk];
-    __shared__ uint32_t s_shadow[kShadeChunk];
+    // A shadow record is stored at a queue position of this workgroup's own chunk, the chunk's first position + the
+    // record's rank among the chunk's records: [begin, end) ranges of workgroups are disjoint and a path has at most
+    // one pending shadow ray, so the records of a chunk are dense (full cache lines written here, coalesced reads in
+    // the trace launch) and the shadow-queue entries of a chunk are just begin + 0, 1, 2, ...
     __shared__ uint32_t s_cnt[4];          // [0] survivors, [1] shadow requests, [2],[3] global bases
     // Next-event estimation is evaluated DENSELY.  Only about a third of the lanes of a trip get past the cosine and
     // cone tests, and the BSDF value + pdf + MIS + shadow-record code behind them is ~30 % of this kernel's time
@@ -370,9 +374,11 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
     uint32_t (*stage)[64] = s_stage[threadIdx.x >> 6];
     uint32_t staged = 0u;                  // records waiting in this wave's staging area (wave-uniform)
     const uint32_t lane = threadIdx.x & 63u;
-    // evaluates the first n staged records, one per lane (pt_cu.cu:136-146 parallel lights, :179-196 ball lights)
-    auto flush_nee = [&](uint32_t n){
+    // evaluates the first n staged records, one per lane (pt_cu.cu:136-146 parallel lights, :179-196 ball lights);
+    // rec_base = first queue position of the chunk the records belong to (staged records never outlive their chunk)
+    auto flush_nee = [&](uint32_t n, uint32_t rec_base){
         bool want = false; uint32_t spath = 0u;
+        f3 c = mk3(0, 0, 0), org = mk3(0, 0, 0), dir = mk3(0, 0, 1); float dist = 0.0f;
         if(lane < n){
             HPT_SECTION(2, 3);                                         // section h: staged next-event evaluation
             f3 wo_l = mk3(u2f(stage[0][lane]), u2f(stage[1][lane]), u2f(stage[2][lane]));
@@ -403,17 +409,19 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
             if(is_valid_color(contrib)){
                 HPT_SECTION(5, 3);                                     // next-event contribution kept: shadow record written
                 want = true;
-                f3 c = clamp_radiance(contrib, 15.0f);
+                c = clamp_radiance(contrib, 15.0f);
+                org = p1;
                 f3 diff = p2 - p1;                              // geometric.cuh:298-303
-                float dist = length3(diff);
-                f3 dir = diff / dist;
-                sb.org_max[spath] = make_float4(p1.x, p1.y, p1.z, dist - 1e-3f);
-                sb.dir[spath] = make_float4(dir.x, dir.y, dir.z, 0.0f);
-                sb.contrib[spath] = make_float4(c.x, c.y, c.z, 0.0f);
+                dist = length3(diff);
+                dir = diff / dist;
             }
         }
-        uint32_t spos = lds_push(want, &s_cnt[1]);
-        if(want) s_shadow[spos] = spath;
+        uint32_t r = rec_base + lds_push(want, &s_cnt[1]);       // rank within the chunk -> record index
+        if(want){
+            sb.org_max[r] = make_float4(org.x, org.y, org.z, dist - 1e-3f);
+            sb.dir[r] = make_float4(dir.x, dir.y, dir.z, 0.0f);
+            sb.contrib[r] = make_float4(c.x, c.y, c.z, u2f(spath));   // the path slot rides along as bits
+        }
     };
 #ifdef HPT_SHADE_PROFILE
     g_hpt_probe = wc ? &wc->bd_pairs : nullptr;            // every thread stores the same value before it reads it
@@ -671,7 +679,7 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
             const unsigned long long cm = __ballot(nee);
             if(cm != 0ull){
                 const uint32_t k = (uint32_t) __popcll(cm);
-                if(staged + k > 64u){ flush_nee(staged); staged = 0u; }
+                if(staged + k > 64u){ flush_nee(staged, begin); staged = 0u; }
                 if(nee){
                     const uint32_t slot = staged + __builtin_amdgcn_mbcnt_hi((uint32_t) (cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) cm, 0u));
                     stage[0][slot] = f2u(n_wo.x); stage[1][slot] = f2u(n_wo.y); stage[2][slot] = f2u(n_wo.z);
@@ -689,7 +697,7 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
         uint32_t qpos = lds_push(alive, &s_cnt[0]);
         if(alive) s_next[qpos] = path;
     }
-    if(staged != 0u){ flush_nee(staged); staged = 0u; }
+    if(staged != 0u){ flush_nee(staged, begin); staged = 0u; }
     __syncthreads();
     if(threadIdx.x == 0){
         s_cnt[2] = s_cnt[0] ? atomicAdd(next_count, s_cnt[0]) : 0u;
@@ -697,7 +705,7 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
     }
     __syncthreads();
     for(uint32_t k = threadIdx.x; k < s_cnt[0]; k += kBlock) next_queue[s_cnt[2] + k] = s_next[k];
-    for(uint32_t k = threadIdx.x; k < s_cnt[1]; k += kBlock) squeue[s_cnt[3] + k] = s_shadow[k];
+    for(uint32_t k = threadIdx.x; k < s_cnt[1]; k += kBlock) squeue[s_cnt[3] + k] = begin + k;
     if(!STRIDED) break;
     }
     if(wc){
@@ -905,6 +913,8 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                     path = queue ? queue[i] : i;
                     bool start = true;
                     if(ANY){
+                        // a shadow-queue entry is a record index, not a path slot (k_shade); `path` keeps it, also through
+                        // s_long into the resume launch, and the slot is read with the contribution at the end
                         float4 a = sb.org_max[path], b = sb.dir[path];
                         ro = xyz(a); rd = xyz(b); tmax = a.w;
                         if(COUNT && !RESUME) n_rays += 1;
@@ -1108,10 +1118,11 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                 active = false;
                 if(!ANY) pb.hit[path] = make_uint2(f2u(best_t), best_prim);
                 else if(!blocked){
-                    float4 c = sb.contrib[path];
-                    float4 col = pb.col[path];
+                    float4 c = sb.contrib[path];                      // record index; the path slot is in .w
+                    const uint32_t slot = f2u(c.w);
+                    float4 col = pb.col[slot];
                     col.x = col.x + c.x; col.y = col.y + c.y; col.z = col.z + c.z;
-                    pb.col[path] = col;
+                    pb.col[slot] = col;
                 }
             }
         }
