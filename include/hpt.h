@@ -89,8 +89,18 @@ typedef struct hpt_params {
                                       * hence opt-in; the default looks at a 4-byte counter every other tail iteration.
                                       * Same image */
 
+/* Statistics of the LAST render on the scene, whichever integrator it was; every render starts them from zero.
+ *   always             ms_total, and the scene constants bvh_nodes, bvh_depth, n_tris, n_materials, ms_bvh_build and
+ *                      ms_upload, which never change for the life of the handle
+ *   hpt_render_pt*     split_budget, traced_rays_last_pass, long_rays_last_pass; with COUNT_WORK samples, closest_rays,
+ *                      shadow_rays, path_iters, boxes_*, tris_*, lane_steps_*, wave_steps_*, leaf_*; with TIME_KERNELS
+ *                      ms_extend .. ms_other, ms_resume and the launch counts n_*
+ *   hpt_render_bdpt*   with COUNT_WORK bd_*; with TIME_KERNELS ms_extend .. ms_other and n_extend .. n_other
+ *   hpt_render_ppm, hpt_sppm_render, hpt_render_guides
+ *                      nothing else: every other field is zero (their counts and phase times are in hpt_ppm_stats)
+ * A field no row names for the last render is zero. */
 typedef struct hpt_stats {
-    uint64_t samples;         /* camera samples traced by the last render */
+    uint64_t samples;         /* camera samples traced by the last render (PT with COUNT_WORK) */
     uint64_t closest_rays;    /* closest-hit rays */
     uint64_t shadow_rays;     /* any-hit rays */
     uint64_t boxes_closest;   /* child boxes slab-tested by closest-hit rays (2 per inner node); COUNT_WORK only */
@@ -150,7 +160,9 @@ int hpt_render_pt(hpt_scene *scene, const void *camera, int W, int H,
  * device knows, and for those the calling thread waits on a 4-byte read-back every other iteration -- i.e. on
  * scenes with delta materials the call MAY BLOCK THE HOST for most of the render's duration.  It never blocks
  * the device: both pipelines of a render keep running while the host waits.  With HPT_FLAG_NO_HOST_WAIT the call
- * only enqueues (blind launches instead of read-backs). */
+ * only enqueues (blind launches instead of read-backs).
+ * Work on one scene is ordered only by the streams the caller passes, and every blocking entry point uses the null
+ * stream.  Before a call on the same scene that uses another stream, the caller waits for the earlier one. */
 int hpt_render_pt_device(hpt_scene *scene, const void *camera, int W, int H,
                          int eye_depth, int spp, const hpt_params *params,
                          void *d_local, void *hip_stream);

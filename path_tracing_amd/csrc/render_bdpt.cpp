@@ -70,7 +70,6 @@ int hpt_render_bdpt_device(hpt_scene *s, const void *camera, int W, int H, int e
     if(rc) return rc;
     rc = ensure_bdpt_scene(s);
     if(rc) return rc;
-    s->ws.last_counter_stride = 0; s->ws.last_budget = 0;
 
     // light vertices: nl * spl subpaths of light_depth vertices each; the contribution table holds one 16-B entry
     // per (path slot, light vertex) pair and at least one image's worth of slots, so it is bounded here
@@ -93,6 +92,9 @@ int hpt_render_bdpt_device(hpt_scene *s, const void *camera, int W, int H, int e
                                      "the image size per rank or samples_per_pass");
     const int max_iters = eye_depth + P.max_delta + 1;
     int n_counters = 2 * (max_iters + 2);
+    // nothing is refused past this point: the counters of the last PT render stop being read before they can move (a call
+    // refused above leaves hpt_get_stats with what the last render reported)
+    s->ws.last_counter_stride = 0; s->ws.last_budget = 0;
     rc = ensure_workspace(s, slots, tl.n_local, n_counters);
     if(rc) return rc;
     rc = ensure_bdpt_workspace(s->bd, slots, eye_depth, (size_t) std::max(n_lv, 1));

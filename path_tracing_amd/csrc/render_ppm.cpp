@@ -205,7 +205,8 @@ int ppm_collect_stats(hpt_scene *s, const PpmRun &r, int passes){
             ps.cand_max = *std::max_element(c.begin(), c.end()); ps.acc_max = *std::max_element(a.begin(), a.end());
         }
     }
-    // hpt_get_stats after this render reports its total time only
+    // hpt_get_stats after this render reports its total time only: the per-class times are reset here, and the work
+    // counters it copies back were cleared on the stream when the render began
     reset_render_stats(s);
     s->tm.stats_pending = true;
     return HPT_OK;
@@ -241,6 +242,7 @@ int hpt_render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth
     PassBuffers &w = s->ws.pass[0];
     const Tiling &tl = r.tl;
     HIP_TRY(hipMemsetAsync(s->pm.pc.get(), 0, sizeof(PpmCounters), st));
+    HIP_TRY(hipMemsetAsync(s->ws.wc.get(), 0, sizeof(WorkCounters), st));     // nothing here counts into it: hpt_get_stats reads zeros
     HIP_TRY(hipMemsetAsync(s->ws.accum.get(), 0, (size_t) tl.n_local * sizeof(float4), st));
     if(r.n_dep) launch_ppm_iota(st, s->pm.grid.slot_in, r.n_dep);
     HIP_TRY(hipEventRecord(s->tm.ev_start, st));
@@ -286,6 +288,7 @@ int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, c
     const PpmStep step(s, r);
     hipStream_t st = step.st;
     HIP_TRY(hipMemsetAsync(s->pm.pc.get(), 0, sizeof(PpmCounters), st));
+    HIP_TRY(hipMemsetAsync(s->ws.wc.get(), 0, sizeof(WorkCounters), st));     // nothing here counts into it: hpt_get_stats reads zeros
     HIP_TRY(hipMemsetAsync(ga.alb_cnt, 0, n_local * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(ga.nrm, 0, n_local * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(ga.pos, 0, n_local * sizeof(float4), st));
@@ -418,6 +421,7 @@ int hpt_sppm_render(hpt_sppm *z, int passes, int32_t flags, float *host_image){
     hipStream_t st = nullptr;
     PassBuffers &w = s->ws.pass[0];
     HIP_TRY(hipMemsetAsync(s->pm.pc.get(), 0, sizeof(PpmCounters), st));
+    HIP_TRY(hipMemsetAsync(s->ws.wc.get(), 0, sizeof(WorkCounters), st));     // nothing here counts into it: hpt_get_stats reads zeros
     if(r.n_dep) launch_ppm_iota(st, s->pm.grid.slot_in, r.n_dep);
     HIP_TRY(hipEventRecord(s->tm.ev_start, st));
     for(int pass = 0; pass < passes; ++pass){

@@ -1,0 +1,221 @@
+"""The session table (session_cases.py) on the CPU oracles alone: conditions that keep the device comparison of
+tests/test_gpu_sessions.py from being vacuous.  A step whose expected image is black passes whatever the kernels do; two
+steps of one kind and size with the same expected bytes let the second pass on the first's stale buffer; a session whose
+steps never grow and then shrink what the integrators share never meets a buffer laid out for somebody else."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import session_cases as sc
+
+SIZED = [n for n in sc.NAMES if n not in ("A_fresh", "D", "F")]
+
+
+@pytest.fixture(scope="module")
+def orc(oracle_mod, tmp_path_factory):
+    return sc.Oracles(oracle_mod, tmp_path_factory.mktemp("session_oracles"))
+
+
+def _size_key(session, i):
+    """(kind, image size) of a render step: what two steps must share for one's stale result to pass as the other's."""
+    st = session.steps[i]
+    if st.kind != "sppm_render":
+        return st.kind, st.kw["W"], st.kw["H"]
+    made = [s for s in session.steps[:i] if s.kind == "sppm_create" and s.kw["name"] == st.kw["name"]][-1]
+    return st.kind, made.kw["W"], made.kw["H"]
+
+
+@pytest.mark.parametrize("name", sc.NAMES)
+def test_expected_results_are_lit_and_distinct(orc, name):
+    s = sc.session(name)
+    ex = sc.expected(orc, s)
+    assert len(ex) == len(s.steps)
+    seen = {}
+    for i, (st, e) in enumerate(zip(s.steps, ex)):
+        if e is not None and "image" in e:
+            img = e["image"]
+            assert np.isfinite(img).all() and img.min() >= 0.0, (name, i, st)
+            assert float(img.mean()) > 0.0, (name, i, st)
+        if st.kind in sc.RENDERS:
+            b = sc.result_bytes(e)
+            for j, bj in seen.get(_size_key(s, i), []):
+                if bj == b:
+                    assert st.repeat_of is not None and sc.result_bytes(ex[st.repeat_of]) == b, (name, j, i, st)
+            seen.setdefault(_size_key(s, i), []).append((i, b))
+        if st.repeat_of is not None:
+            first = s.steps[st.repeat_of]
+            assert st.repeat_of < i and first.kind == st.kind and first.repeat_of is None
+            assert sc.result_bytes(e) == sc.result_bytes(ex[st.repeat_of]), (name, i, st)
+    print("%s: %d steps, %d with an image" % (name, len(s.steps), sum(1 for e in ex if e is not None and "image" in e)))
+
+
+@pytest.mark.parametrize("name", SIZED)
+def test_sizes_rise_and_fall(name):
+    s = sc.session(name)
+    got = sc.size_conditions(s)
+    print(name, [(i, f) for i, f in sc.footprints(s)])
+    assert set(got) == ({"slots", "n_local", "n_lv", "deposits", "iters"} if name == "A" or name.startswith("R") else {"slots", "n_local"})
+    assert all(got.values()), got
+
+
+@pytest.mark.parametrize("name", sc.NAMES)
+def test_steps_stay_small_and_well_formed(name):
+    s = sc.session(name)
+    assert sc.bdpt_table_bytes(s) <= sc.BDPT_TABLE_LIMIT
+    nl = len(sc.scene(s.scene)["L"])
+    alive = set()
+    for i, st in enumerate(s.steps):
+        kw = st.kind != "refused" and st.kw or {}
+        assert kw.get("spp", 1) <= sc.MAX_SPP and kw.get("W", 1) * kw.get("H", 1) <= 200 * 136
+        assert nl * kw.get("spl", 0) * kw.get("light_depth", 1) <= 1 << 14             # photons, deposits and light vertices of a valid step
+        if st.kind == "stats":
+            assert s.steps[sc.last_render(s, i)].kind in sc.BLOCKING
+        if st.kind == "sppm_create":
+            assert st.kw["name"] not in alive
+            alive.add(st.kw["name"])
+        elif st.kind.startswith("sppm_"):
+            assert st.kw["name"] in alive
+            if st.kind == "sppm_destroy":
+                alive.discard(st.kw["name"])
+        if st.kind == "pt_device_rank":
+            earlier = [p.kw["rank"] for p in s.steps[:i] if p.kind == "pt_device_rank" and p.kw["group"] == st.kw["group"]]
+            assert earlier == list(range(st.kw["rank"]))
+        if st.kind == "untile":
+            assert [p.kw["rank"] for p in s.steps[:i] if p.kind == "pt_device_rank" and p.kw["group"] == st.kw["group"]] == list(range(sc.WORLD))
+
+
+def test_session_a_is_the_frame_sequence():
+    s = sc.session("A")
+    kinds = [st.kind for st in s.steps]
+    assert kinds == ["pt", "guides", "bdpt", "ppm", "pt", "stats", "ppm", "stats", "set_groups", "bdpt", "pt", "bdpt",
+                     "guides", "set_groups", "bdpt", "pt", "stats"]
+    size = [(st.kw.get("W"), st.kw.get("H")) for st in s.steps]
+    assert size[0] == size[1] == (48, 40) and size[2] == size[9] == size[14] == (32, 24) and size[3] == (64, 48)
+    assert size[4] == (7, 3) and s.steps[4].kw["flags"] == sc.COUNT_WORK and size[6] == (16, 16) and s.steps[3].kw["spl"] == 256
+    assert size[10] == (96, 64) and s.steps[10].kw["tile"] == 8 and s.steps[10].kw["samples_per_pass"] == 1 and size[12] == (1, 1)
+    big = s.steps[11].kw
+    assert (big["W"], big["H"], big["depth"], big["spl"], big["light_depth"]) == (16, 16, 12, 8, 4)
+    assert [s.steps[i].kw["which"] for i in (8, 13)] == ["file", "none"]
+    assert s.steps[14].repeat_of == 2 and s.steps[15].repeat_of == 0
+    fp = dict(sc.footprints(s))
+    # the large PT step grows every pass buffer; the deep BDPT step has fewer slots but more history entries and light vertices
+    assert fp[10]["slots"] > max(f["slots"] for i, f in fp.items() if i < 10) and s.steps[10].kw["spp"] >= 2
+    assert fp[11]["slots"] < fp[2]["slots"] and fp[11]["slots"] * big["depth"] > fp[2]["slots"] * s.steps[2].kw["depth"]
+    assert fp[11]["n_lv"] > fp[2]["n_lv"]
+    fresh = sc.session("A_fresh")
+    assert [st.kind for st in fresh.steps] == ["ppm", "stats"]
+
+
+def test_session_b_runs_one_shape_under_every_setting():
+    s = sc.session("B")
+    assert s.scene == "cornell2k"
+    pt = [st for st in s.steps if st.kind == "pt"]
+    assert len({(st.kw["W"], st.kw["H"], st.kw["depth"], st.kw["spp"], st.kw["samples_per_pass"]) for st in pt}) == 1
+    assert [(st.kw.get("flags", 0), st.kw.get("budget", 0)) for st in pt] == [
+        (0, 0), (sc.BRUTE_FORCE, 0), (sc.COUNT_WORK, 0), (sc.RUSSIAN_ROULETTE, 0), (sc.SINGLE_PIPELINE, 0), (sc.NO_HOST_WAIT, 0),
+        (sc.TIME_KERNELS, 0), (sc.OUTPUT_SUM, 0), (0, 1), (0, 63)]
+    deltas = [st.kw.get("max_delta", 0) for st in pt]
+    assert deltas[:5] == [250, 250, 1, 1, 0] and not any(deltas[5:])
+    for a, b in zip(s.steps, s.steps[1:]):
+        assert not (a.kind == "pt" and b.kind == "pt")                 # a PPM or guide step sits between any two
+        if a.kind in ("pt", "ppm") and a.kw.get("flags", 0) & sc.COUNT_WORK:
+            assert b.kind == "stats"
+    counting = [sc.n_local(st.kw) for st in s.steps if st.kind == "ppm" and st.kw["flags"] & sc.COUNT_WORK]
+    assert len(counting) >= 3 and any(b > a for a, b in zip(counting, counting[1:])) and any(b < a for a, b in zip(counting, counting[1:]))
+    other = [st.kw.get("flags", 0) for st in s.steps if st.kind in ("ppm", "guides")]
+    assert 0 in other and sc.TIME_KERNELS in other and sc.COUNT_WORK in other and (sc.COUNT_WORK | sc.TIME_KERNELS) in other
+
+
+def test_session_c_holds_two_states():
+    s = sc.session("C")
+    z = {st.kw["name"]: st.kw for st in s.steps if st.kind == "sppm_create"}
+    assert (z["Z1"]["W"], z["Z1"]["H"], z["Z1"]["radius"], z["Z1"]["alpha"], z["Z1"]["spl"]) == (48, 48, 0.05, 0.7, 256)
+    assert (z["Z2"]["W"], z["Z2"]["H"], z["Z2"]["radius"], z["Z2"]["alpha"], z["Z2"]["spl"], z["Z2"]["tile"]) == (40, 24, 0.08, 0.5, 8, 8)
+    for i, a in enumerate(s.steps):
+        if a.kind == "sppm_render":                                   # the state is read after every render
+            b = s.steps[i + 2] if s.steps[i + 1].kind == "stats" else s.steps[i + 1]
+            assert b.kind == "sppm_state" and b.kw["name"] == a.kw["name"]
+    after_counting = [i for i, st in enumerate(s.steps) if st.kind == "stats"]
+    assert len(after_counting) == 1 and s.steps[after_counting[0] - 1].kind == "sppm_render"
+    assert s.steps[after_counting[0] - 2].kind == "pt" and s.steps[after_counting[0] - 2].kw["flags"] == sc.COUNT_WORK
+    renders = [(st.kw["name"], st.kw["passes"]) for st in s.steps if st.kind == "sppm_render"]
+    assert {p for _, p in renders} == {1, 2} and all(a[0] != b[0] for a, b in zip(renders[:4], renders[1:4]))
+    kinds = [st.kind for st in s.steps]
+    reset, gone = kinds.index("sppm_reset"), kinds.index("sppm_destroy")
+    assert s.steps[reset].kw["name"] == "Z1" and s.steps[gone].kw["name"] == "Z2" and reset < gone
+    assert any(st.repeat_of is not None for st in s.steps[reset:gone] if st.kind == "sppm_render")
+    assert any(st.kind == "sppm_render" and st.kw["name"] == "Z1" for st in s.steps[gone:])
+    assert {"pt", "ppm", "guides"} <= set(kinds[:gone])
+    assert [st.kw["radius"] for st in s.steps if st.kind == "ppm"] == [0.13]
+
+
+def test_session_d_makes_every_refusal_and_renders_on():
+    s = sc.session("D")
+    last = max(i for i, st in enumerate(s.steps) if st.kind == "pt")
+    labels = [st.kw["label"] for st in s.steps[:last] if st.kind == "refused"]
+    assert labels == [r[0] for r in sc.REFUSALS] and len(labels) == 16
+    # the tail: a counting render, refusals, and the statistics of that render
+    tail = s.steps[last:]
+    assert tail[0].kw["flags"] == sc.COUNT_WORK and tail[-1].kind == "stats" and len(tail) >= 12
+    assert all(st.kind == "refused" for st in tail[1:-1]) and "BDPT light vertices > 2^24" in [st.kw["label"] for st in tail[1:-1]]
+    codes = {st.kw["label"]: st.kw["code"] for st in s.steps if st.kind == "refused"}
+    assert [k for k, c in codes.items() if c == sc.ERR_NOMEM] == ["PPM deposits > 2^30"]
+    nl = len(sc.scene("input")["L"])
+    by = {r[0]: dict(sc.VALID[r[1]], **r[2]) for r in sc.REFUSALS}
+    assert nl * by["BDPT light vertices > 2^24"]["spl"] * by["BDPT light vertices > 2^24"]["light_depth"] > 1 << 24
+    assert nl * by["PPM deposits > 2^30"]["spl"] * by["PPM deposits > 2^30"]["light_depth"] > 1 << 30
+    for i, st in enumerate(s.steps[:last]):
+        if st.kind != "refused":
+            continue
+        after = [p.kind for p in s.steps[i + 1:i + 8]]
+        assert {"pt", "bdpt", "ppm", "guides", "sppm_render", "sppm_state"} <= set(after), (i, after)
+        # the sizes a refused call names were rendered before it: no buffer grows on the way to the check that stops it
+        before = {(p.kind, p.kw["W"], p.kw["H"]) for p in s.steps[:i] if p.kind in ("pt", "bdpt", "ppm", "guides")}
+        assert {(k, 24, 16) for k in ("pt", "bdpt", "ppm", "guides")} <= before
+    zero = next(i for i, st in enumerate(s.steps) if st.kind == "refused" and st.kw["call"] == "sppm_render")
+    assert s.steps[zero].kw["passes"] == 0 and s.steps[zero + 1].kind == "sppm_state"
+
+
+def test_state_survives_a_refused_render(orc):
+    s = sc.session("D")
+    ex = sc.expected(orc, s)
+    zero = next(i for i, st in enumerate(s.steps) if st.kind == "refused" and st.kw["call"] == "sppm_render")
+    before = max(i for i in range(zero) if s.steps[i].kind == "sppm_state")
+    assert ex[zero + 1]["passes"] == ex[before]["passes"] > 0
+    assert ex[zero + 1]["radius2"].tobytes() == ex[before]["radius2"].tobytes()
+
+
+def test_sessions_e_and_f_are_the_listed_calls():
+    e = sc.session("E")
+    assert e.handle == "multi" and [st.kind for st in e.steps] == ["pt", "pt", "pt", "set_groups", "bdpt", "pt"]
+    assert [(st.kw["W"], st.kw["H"], st.kw.get("tile", 0)) for st in e.steps if st.kind == "pt"] == [(200, 136, 0), (24, 16, 32), (96, 64, 8), (200, 136, 0)]
+    assert e.steps[5].repeat_of == 0 and (e.steps[4].kw["W"], e.steps[4].kw["H"]) == (48, 40)
+    assert sc.tiling.tiling_dims(24, 16, 32, sc.WORLD)[2] == 1                      # one tile: two ranks have none
+    f = sc.session("F")
+    assert f.handle == "wrappers" and [st.kind for st in f.steps] == ["pt_wrapper", "bdpt_wrapper", "ppm_wrapper", "pt_wrapper", "pt_wrapper", "pt_wrapper"]
+    assert f.steps[1].kw["light_sample"] == 1 and f.steps[4].kw.get("changed") and f.steps[5].repeat_of == 0
+    assert (f.steps[3].kw["W"], f.steps[3].kw["H"]) != (f.steps[0].kw["W"], f.steps[0].kw["H"])
+    tr = sc.scene("input")["tr"]
+    assert (np.frombuffer(sc.changed_triangles(tr).tobytes(), np.float32).view(np.uint32) != np.frombuffer(tr.tobytes(), np.float32).view(np.uint32)).sum() == 1
+
+
+def test_random_sessions_are_functions_of_their_seeds():
+    assert sc.R_SEEDS == [1, 2, 3]
+    for seed in sc.R_SEEDS:
+        a, attempt = sc.random_session(seed)
+        b, again = sc.random_session(seed)
+        assert a == b and attempt == again and len(a.steps) == sc.R_STEPS and a == sc.session("R%d" % seed)
+        kinds = {st.kind for st in a.steps}
+        assert len(kinds) >= 8 and {"pt", "bdpt", "ppm", "guides"} <= kinds
+    assert len({repr(sc.session("R%d" % seed).steps) for seed in sc.R_SEEDS}) == 3
+    # another process, another hash seed: the same steps
+    code = "import session_cases as sc\nfor s in sc.R_SEEDS: print(repr(sc.random_session(s)))"
+    env = dict(os.environ, PYTHONHASHSEED="12345")
+    out = subprocess.check_output([sys.executable, "-c", code], cwd=os.path.dirname(os.path.abspath(__file__)), env=env, text=True)
+    assert out.splitlines() == [repr(sc.random_session(s)) for s in sc.R_SEEDS]
+    vocabulary = {st.kind for seed in sc.R_SEEDS for st in sc.session("R%d" % seed).steps}
+    assert {"pt_device_rank", "untile", "set_groups", "sppm_create", "sppm_render", "sppm_state", "sppm_destroy", "probe_closest",
+            "probe_visibility", "export_bvh", "stats", "refused"} <= vocabulary
