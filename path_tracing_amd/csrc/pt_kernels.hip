@@ -835,8 +835,12 @@ void k_tonemap(const float *linear, uint32_t *out_words, unsigned long long num_
 // Chunk size: 256 -> 47.3, 512 -> 45.5, 1024 -> 49.6, 2048 -> 59.3 (long chunks leave the tail of
 // a launch to a few workgroups); refill threshold 8 -> 51.0, 16 -> 49.6, 32 -> 48.6, 48 -> 48.0.
 // k_trace's registers are fitted to eight waves per SIMD -- vector AND scalar: left alone the compiler takes 106 SGPRs, and
-// more than 96 cap a CU at six 256-thread workgroups whatever the vector registers allow (80 with this attribute, the
-// rest spilled to lanes of a VGPR).  Measured against the unconstrained build: first launch 11.37 -> 11.00 ms, resume
+// more than 96 cap a CU at six 256-thread workgroups whatever the vector registers allow (78 with this attribute, the
+// rest spilled to lanes of a VGPR).  Per instantiation <COUNT, RESUME, TOP, PRIMARY> (scripts/isa_report.py): VGPRs / of them
+// spilled to scratch / SGPRs spilled to lanes = <0,0,1,0> 62 / 0 / 48, <0,0,1,1> 64 / 6 / 61, <0,1,0,0> 57 / 0 / 24,
+// <0,1,0,1> 63 / 0 / 44, <0,0,0,0> 61 / 0 / 50, <0,0,0,1> 64 / 6 / 77, <1,0,0,0> 64 / 11 / 61 (with two exits and a `continue`
+// in trace_chunk's loop: 64 / 2 / 54, 64 / 11 / 87, 58 / 0 / 36, 64 / 0 / 66, 64 / 2 / 59, 64 / 11 / 89, 64 / 56 / 65;
+// tests/test_trace_isa_cpu.py holds the VGPR side).  Measured against the unconstrained build: first launch 11.37 -> 11.00 ms, resume
 // 8.14 -> 7.70 per 64-spp pass of config 3, 14.00 -> 13.46 on the 1 M-triangle shape.  `make variant EXTRA=-DHPT_TRACE_WAVES=0`
 // builds without it, =7 with seven.
 #ifndef HPT_TRACE_WAVES
@@ -979,14 +983,16 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                     }
                 }
             }
-            if(!__any(active)){
-                if(exhausted) break;
-                continue;
-            }
-        } else if(idle == ~0ull){
-            break;                                      // chunk exhausted and every ray finished
         }
+        // ONE exit, after the refill, and no `continue`.  With an exit in each arm and a `continue` for "the refill started
+        // nobody" the register coalescer gives up on the loop-carried ray state and copies all of it (20-24 VGPRs) into a
+        // second register set at the top of every trip and back before the node walk: 44-48 v_mov per trip, 49 of the refill
+        // block's 66 VALU instructions (scripts/isa_report.py, profiles/r05_experiments.md).  This shape does the same thing:
+        //  - no refill and every lane idle happens only with the chunk exhausted (else the refill is taken): exit, as before;
+        //  - a refill that started nobody with rays left in the chunk falls through phases 1 and 2, which `active` guards
+        //    and which therefore do nothing (and count nothing), and comes round to the next refill -- the old `continue`.
         const unsigned long long idle_at_entry = __ballot(!active);
+        if(idle_at_entry == ~0ull && exhausted) break;  // chunk exhausted and every ray finished
         // phase 1: walk inner nodes until this lane holds a leaf (or its ray is finished); when only a
         // few lanes are still descending while others wait with a leaf, go and do the leaves first
         while(active && !(cur & kLeafFlag) && (RESUME || steps < step_limit)){

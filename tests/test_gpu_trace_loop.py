@@ -1,0 +1,145 @@
+"""The exits of trace_chunk's outer loop (csrc/pt_kernels.hip): the smallest renders in which a refill starts no lane or
+a wave has nothing to do, bit for bit against oracle.pt_render.
+
+The loop has one exit, after the refill: "every lane idle and the chunk exhausted".  A refill that starts nobody while the
+chunk still holds rays falls through the two phases and comes round again.  A wrong exit does not fail here, it hangs or
+drops rays, so every case is a few thousand paths at the most:
+
+  ragged-tiles   33 x 33 in 32-pixel tiles, 3 spp: three of the four tiles are almost all slots outside the image -- whole
+                 waves whose refill starts nobody while their chunk is not exhausted
+  dark-light     the light ball shut into an opaque sphere, 48 x 48 x 2 spp: the sphere pre-test stops every shadow ray, so
+                 the shadow waves refill and start no lane
+  turned-away    a camera that looks away from the scene, 40 x 24 x 2 spp: every primary ray misses; iteration 1 and every
+                 shadow queue are empty
+  deferred       cornell_with_sphere(2000), 64 x 64 x 4 spp, depth 4, max_delta 3: with a budget of one node step every ray
+                 that meets the tree is set aside (lanes go idle by deferral while the chunk still holds rays) and the resume
+                 launch walks nearly all of them, past its 12 LDS stack levels
+  queue-N        1 x 1, 7 x 9, 5 x 13 and 1 x 257 at 1 spp in one tile: first queues of 1, 63, 65 and 257 rays, a last wave
+                 narrower than the refill threshold
+
+each with the default node-step budget, unsplit (budget 63), budget 1, on one pipeline, and with HPT_FLAG_NO_HOST_WAIT
+(capped, strided grids: workgroups that walk several chunks or none).
+
+Observed on the CPU oracle (the scan): lit share / closest-hit rays / shadow rays / seconds
+  ragged-tiles 96.3 % / 9782 / 3907 / 0.1    dark-light 0 % / 14039 / 6534 / 0.1    turned-away 0 % / 1920 / 0 / 0.1
+  deferred 98.4 % / 62938 / 20076 / 1.4 to 1.9 (the scan over 2 000 triangles; computed once for its six tests)
+  queue-1 100 % / 4 / 2    queue-63 61.9 % / 195 / 78    queue-65 63.1 % / 188 / 76    queue-257 67.3 % / 724 / 286 (0.04 s each)
+"""
+import numpy as np
+import pytest
+
+import pt_cases as pc
+from path_tracing_amd import scene_io as sio
+from path_tracing_amd.layouts import SPHERE
+
+pytestmark = pytest.mark.gpu
+
+NO_SPLIT = 63                       # hpt_params.reserved budget bits: the trace step is not split
+FLAG_SINGLE_PIPELINE, FLAG_NO_HOST_WAIT = 32, 64          # include/hpt.h
+VARIANTS = {"default": (0, 0), "unsplit": (NO_SPLIT, 0), "budget-1": (1, 0),
+            "one-pipeline": (0, FLAG_SINGLE_PIPELINE), "no-host-wait": (0, FLAG_NO_HOST_WAIT)}
+QUEUE_SHAPES = {1: (1, 1), 63: (7, 9), 65: (5, 13), 257: (1, 257)}
+
+
+def _cornell_cam(W, H):
+    return sio.make_camera(sio.CORNELL_EYE, sio.CORNELL_LOOK, sio.CORNELL_UP, 50.0, W, H)
+
+
+def ragged_tiles():
+    L, sp, tr = sio.cornell_diffuse()
+    return L, sp, tr, _cornell_cam(33, 33), 33, 33, 4, 3, dict(seed=6, tile=32, samples_per_pass=3)
+
+
+LIGHT_AT, LIGHT_R, SHELL_R = (0.0, 0.15, 0.3), 0.03, 0.08
+
+
+def dark_light():
+    _, _, tr = sio.cornell_diffuse()
+    L = sio._one_light(LIGHT_AT, (0.0, -1.0, 0.0), (1.0, 1.0, 1.0), 180.0, 0, LIGHT_R)
+    sp = np.zeros(1, SPHERE)
+    sp[0]["center"] = LIGHT_AT; sp[0]["r"] = SHELL_R
+    sio._fill_mtl(sp[0], (0.7, 0.7, 0.7, 1.0, 0.0, 0.0))
+    return L, sp, tr, _cornell_cam(48, 48), 48, 48, 4, 2, dict(seed=12, samples_per_pass=2)
+
+
+def turned_away():
+    L, sp, tr = sio.cornell_diffuse()
+    cam = sio.make_camera((0.0, 0.0, -3.0), (0.0, 0.0, -10.0), sio.CORNELL_UP, 50.0, 40, 24)      # the box ends at z = -1.1
+    return L, sp, tr, cam, 40, 24, 4, 2, dict(seed=3, samples_per_pass=2)
+
+
+def deferred():
+    L, sp, tr = sio.cornell_with_sphere(2000)
+    return L, sp, tr, _cornell_cam(64, 64), 64, 64, 4, 4, dict(seed=3, max_delta=3, samples_per_pass=4)
+
+
+def queue_case(n):
+    W, H = QUEUE_SHAPES[n]
+    assert W * H == n
+    L, sp, tr = sio.cornell_diffuse()
+    return L, sp, tr, _cornell_cam(W, H), W, H, 4, 1, dict(seed=4, tile=1024, samples_per_pass=1)          # seed 4: the 1 x 1 image is lit
+
+
+CASES = {"ragged-tiles": ragged_tiles, "dark-light": dark_light, "turned-away": turned_away, "deferred": deferred}
+CASES.update({"queue-%d" % n: (lambda n=n: queue_case(n)) for n in QUEUE_SHAPES})
+_REFERENCE = {}
+
+
+def reference(oracle_mod, name):
+    """(args, image, stats) of a case by the oracle, computed once per process and shared read-only."""
+    if name not in _REFERENCE:
+        args = CASES[name]()
+        img, st = pc.oracle_render(oracle_mod, args)
+        img.setflags(write=False)
+        _REFERENCE[name] = (args, img, st)
+    return _REFERENCE[name]
+
+
+def check_reference(name, args, ref, st):
+    """What makes the case the case it is meant to be, on the oracle's side."""
+    L, sp, tr, cam, W, H, depth, spp, kw = args
+    lit = pc.lit_share(ref)
+    print("%s: oracle %.1f %% lit, %d closest-hit rays, %d shadow rays" % (name, 100.0 * lit, st["closest_rays"], st["shadow_rays"]))
+    if name == "dark-light":
+        assert st["shadow_rays"] > 1000 and not ref.any()
+    elif name == "turned-away":
+        assert st["closest_rays"] == W * H * spp and st["shadow_rays"] == 0 and not ref.any()
+    else:
+        assert lit > 0.5 and st["shadow_rays"] > 0
+    if name == "ragged-tiles":
+        assert W % kw["tile"] == 1 and H % kw["tile"] == 1
+    if name == "deferred":
+        assert st["closest_rays"] > W * H * spp
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("name", list(CASES))
+def test_trace_loop_exits(hpt, oracle_mod, name, variant):
+    args, ref, st = reference(oracle_mod, name)
+    check_reference(name, args, ref, st)
+    L, sp, tr, cam, W, H, depth, spp, kw = args
+    budget, flags = VARIANTS[variant]
+    p = hpt.make_params(**dict(kw, flags=flags))
+    p.reserved = budget << 1
+    with hpt.Scene(L, sp, tr) as scene:
+        img = scene.render_pt(cam, W, H, depth, spp, p)
+    print("%s, %s: %d pixels differ from the oracle (max abs %.3e), mean %.5f" % (
+        name, variant, int((img != ref).any(axis=-1).sum()), float(np.abs(img - ref).max()), float(img.mean())))
+    assert img.shape == ref.shape and np.isfinite(img).all()
+    assert np.array_equal(img, ref)
+
+
+def test_budget_one_defers_to_the_resume_launch(hpt, oracle_mod):
+    """The `deferred` case is what it claims: with budget 1 the resume launch runs (and not without a split)."""
+    args, ref, st = reference(oracle_mod, "deferred")
+    L, sp, tr, cam, W, H, depth, spp, kw = args
+    resumes = {}
+    with hpt.Scene(L, sp, tr) as scene:
+        for what, budget in (("budget-1", 1), ("unsplit", NO_SPLIT)):
+            p = hpt.make_params(**dict(kw, flags=hpt.FLAG_TIME_KERNELS))
+            p.reserved = budget << 1
+            img = scene.render_pt(cam, W, H, depth, spp, p)
+            resumes[what] = scene.stats()["n_resume"]            # launches are counted by the kernel timers only
+            assert np.array_equal(img, ref), what
+    print("resume launches:", resumes)
+    assert resumes["budget-1"] > 0 and resumes["unsplit"] == 0
