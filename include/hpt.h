@@ -423,6 +423,74 @@ void hpt_denoiser_destroy(hpt_denoiser *d);
 int hpt_denoise_host(const float *linear_rgb, const float *albedo, const float *normal, const float *position,
                      const float *coverage, float *out, int W, int H, const hpt_denoise_params *p);
 
+/* ---- progressive display ----------------------------------------------------------------------------
+ * The reference's GUI renders a few samples per frame and, after every frame, runs a host loop over every pixel and
+ * channel (src/main.cpp:421-531): running average, clamp / pow(1/2.2) / truncate, row flip into a three-panel
+ * framebuffer, and the squared byte differences it plots as "RMS history".  These two objects keep that state on the
+ * device, so a frame is hpt_render_*_device, hpt_untile, hpt_accum_add, hpt_display_present on one stream and only
+ * two 64-bit sums come back.
+ *
+ * All images are W*H*3 floats, row-major, row 0 = top, in device memory (the layout hpt_untile writes).  IEEE float,
+ * evaluated as written, per value v of the frame:
+ *   add       sum = sum + v; with HPT_ACCUM_MOMENTS also sq = sq + v * v.  K, the frame count, is a host counter that
+ *             is incremented when the call is enqueued.  d_mean_out, when not NULL, receives sum / (float) K (the
+ *             division happens at K = 1 too, as in main.cpp:470); it may be d_frame_rgb itself (in place), any other
+ *             overlap of the two is refused.
+ *   mean      sum / (float) K; K = 0 returns HPT_ERR_INVALID.
+ *   variance  the variance of the MEAN, needs HPT_ACCUM_MOMENTS.  K < 2: all zeros.  Otherwise m = sum / (float) K;
+ *             q = sq / (float) K; d = q - m * m; out = fmaxf(d, 0.0f) / (float) (K - 1).  Good for what a progressive
+ *             viewer asks of it: Monte-Carlo noise over tens of frames, whose relative variance is 1e-4 and up.  NOT a
+ *             general-purpose variance: q and m * m are rounded floats of nearly equal size, so below a relative
+ *             variance of about 1e-7 (2^-23) their difference is rounding, not signal (a constant frame gives exactly 0).
+ *   reset     zeroes the sums on the stream and sets K = 0; the reference's restart when the camera moves
+ *             (main.cpp:453-466) is reset followed by add.
+ * Every call only enqueues on hip_stream, except hpt_accum_read, which waits for the device and copies the sums to
+ * the host (for tests; either image may be NULL).  hpt_accum_create allocates on the current device, sums zeroed.
+ * W or H below 1 (or W*H above 2^28), an unknown flag, variance (or a sumsq read) without MOMENTS, a NULL handle, a
+ * NULL frame or output, and more than 2^24 adds -- (float) K stops being exact -- return HPT_ERR_INVALID with a
+ * message, before anything touches the device. */
+#define HPT_ACCUM_MOMENTS 1          /* also keep the per-channel sum of squares */
+typedef struct hpt_accum hpt_accum;
+int  hpt_accum_create(int W, int H, int32_t flags, hpt_accum **out);
+int  hpt_accum_add(hpt_accum *a, const void *d_frame_rgb, void *d_mean_out, void *hip_stream);
+int  hpt_accum_mean(hpt_accum *a, void *d_out, void *hip_stream);
+int  hpt_accum_variance(hpt_accum *a, void *d_out, void *hip_stream);
+int  hpt_accum_reset(hpt_accum *a, void *hip_stream);
+int64_t hpt_accum_count(const hpt_accum *a);
+int  hpt_accum_read(hpt_accum *a, float *sum, float *sumsq, int64_t *count);
+void hpt_accum_destroy(hpt_accum *a);
+
+/* hpt_display_present, the P-th call (P counts from 0), in one launch:
+ *   b[r][x][c] = the byte of d_linear_rgb[(r*W + x)*3 + c] under hpt_tonemap's threshold table, i.e. the bytes of
+ *                hpt_tonemap_reference(..., bgr = 0): NaN gives 0, anything >= 1 gives 255.
+ *   ssd_prev   = the sum over all 3*W*H values of (b - last)^2; 0 when P = 0 (the reference's is_first).
+ *   ssd_other  = the same sum against other's `last` (the reference's PPM-BDPT "DIFF RMS"); 0 when other is NULL.
+ *                other must be a different display of the same size on the same device that has presented at least
+ *                once, else HPT_ERR_INVALID.  The caller orders the two displays' work, as everywhere in this ABI.
+ *   d_rgb8, when not NULL:  d_rgb8[(flip ? H-1-r : r) * pitch + x_offset + 3*x + (bgr ? 2-c : c)] = b[r][x][c].
+ *                pitch_bytes = 0 means 3*W; pitch < x_offset + 3*W or x_offset < 0 return HPT_ERR_INVALID.  No
+ *                alignment is asked of the pointer, the pitch or the offset, and no byte outside the panel's H runs
+ *                of 3*W bytes is written, or read and written back: the three panels of one framebuffer are
+ *                pitch = 9*W, x_offset = panel*3*W (main.cpp:434-437) and may be presented from different streams.
+ *   then last = b and P += 1.  `last` is kept in canonical order (RGB, row 0 = top), so the metrics do not depend on flags.
+ * hpt_display_metrics waits for the last present only and returns its numbers: rms = sqrt((double) ssd) / 255.0; any
+ * output may be NULL; before any present (or after a reset) it returns HPT_ERR_INVALID.  The sums are exact 64-bit
+ * integers, so they do not depend on grid shape, workgroup order or device.
+ * Relation to the reference: main.cpp:502-530 adds powf(diff, 2) into a `float` in pixel order.  Every term is an
+ * integer <= 65025, so while the sum stays at or below 2^24 every partial sum is an exact integer and the reference's
+ * value equals this one; above 2^24 its float sum rounds at every step, and this is the number it approximates.
+ * hpt_display_reset sets P = 0 (the next present reports ssd_prev = 0).  hpt_display_create allocates on the current device. */
+#define HPT_DISPLAY_BGR    1     /* cv::Vec3b channel order in d_rgb8 */
+#define HPT_DISPLAY_FLIP_Y 2     /* image row r goes to output row H-1-r (main.cpp:431) */
+typedef struct hpt_display hpt_display;
+int  hpt_display_create(int W, int H, hpt_display **out);
+int  hpt_display_present(hpt_display *d, const void *d_linear_rgb, const hpt_display *other,
+                         void *d_rgb8, int64_t pitch_bytes, int64_t x_offset_bytes, int32_t flags, void *hip_stream);
+int  hpt_display_metrics(hpt_display *d, double *rms_prev, double *rms_other,
+                         uint64_t *ssd_prev, uint64_t *ssd_other, int64_t *presented);
+int  hpt_display_reset(hpt_display *d, void *hip_stream);
+void hpt_display_destroy(hpt_display *d);
+
 /* ---- the acceleration structure, exported (tests) -------------------------------------
  * The reference has no acceleration structure (include/geometric.cuh:293-388 scan every primitive); the tree the
  * kernels walk is this library's own, and the work counts the bench's roofline is built from (hpt_stats.boxes_*,

@@ -31,6 +31,9 @@ FLAG_SINGLE_PIPELINE = 32
 FLAG_NO_HOST_WAIT = 64
 DENOISE_DEMODULATE = 1
 DENOISE_TIME = 2
+ACCUM_MOMENTS = 1
+DISPLAY_BGR = 1
+DISPLAY_FLIP_Y = 2
 
 
 class HptError(RuntimeError):
@@ -141,7 +144,9 @@ def load_library() -> C.CDLL:
                      "hpt_render_ppm", "hpt_ppm_get_stats", "hpt_ppm_render_wrapper",
                      "hpt_sppm_create", "hpt_sppm_render", "hpt_sppm_reset", "hpt_sppm_read_state",
                      "hpt_render_guides", "hpt_denoiser_create", "hpt_denoiser_set_guides", "hpt_denoiser_run",
-                     "hpt_denoiser_last_ms", "hpt_denoiser_level_ms", "hpt_denoise_host"):
+                     "hpt_denoiser_last_ms", "hpt_denoiser_level_ms", "hpt_denoise_host",
+                     "hpt_accum_create", "hpt_accum_add", "hpt_accum_mean", "hpt_accum_variance", "hpt_accum_reset", "hpt_accum_read",
+                     "hpt_display_create", "hpt_display_present", "hpt_display_metrics", "hpt_display_reset"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -150,6 +155,13 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "hpt_denoiser_destroy"):
             lib.hpt_denoiser_destroy.restype = None
             lib.hpt_denoiser_destroy.argtypes = [C.c_void_p]
+        for name in ("hpt_accum_destroy", "hpt_display_destroy"):
+            if hasattr(lib, name):
+                getattr(lib, name).restype = None
+                getattr(lib, name).argtypes = [C.c_void_p]
+        if hasattr(lib, "hpt_accum_count"):
+            lib.hpt_accum_count.restype = C.c_int64
+            lib.hpt_accum_count.argtypes = [C.c_void_p]
         lib.hpt_scene_destroy.restype = None
         lib.hpt_wrapper_cache_clear.restype = None
         lib.hpt_wrapper_cache_clear.argtypes = []
@@ -432,6 +444,107 @@ def denoise(image, guides, iterations=0, sigma_color=0, sigma_normal=0, sigma_po
     p = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_position, demodulate)
     _check(load_library().hpt_denoise_host(_vp(img), _vp(g[0]), _vp(g[1]), _vp(g[2]), _vp(g[3]), _vp(out), W, H, C.byref(p)))
     return out
+
+
+class Accumulator:
+    """Running sum over frames on the device (include/hpt.h, hpt_accum_*) for W x H images: float32 adds in frame order,
+    with moments=True also the sum of squares.  Frames and outputs are DEVICE buffers (ints or torch tensors, float32,
+    W*H*3, row 0 = top); every call only enqueues on `stream`, except read()."""
+
+    def __init__(self, W, H, moments=False):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        self.W, self.H, self.moments = int(W), int(H), bool(moments)
+        _check(self._lib.hpt_accum_create(int(W), int(H), C.c_int32(ACCUM_MOMENTS if moments else 0), C.byref(self._h)))
+
+    def add(self, frame, mean_out=None, stream: int = 0):
+        """sum += frame; mean_out (may be `frame` itself) receives sum / count."""
+        _check(self._lib.hpt_accum_add(self._h, _dptr(frame), _dptr(mean_out) if mean_out is not None else None, C.c_void_p(stream)))
+
+    def mean(self, out, stream: int = 0):
+        _check(self._lib.hpt_accum_mean(self._h, _dptr(out), C.c_void_p(stream)))
+
+    def variance(self, out, stream: int = 0):
+        """The variance of the mean (moments=True); all zeros below two frames."""
+        _check(self._lib.hpt_accum_variance(self._h, _dptr(out), C.c_void_p(stream)))
+
+    def reset(self, stream: int = 0):
+        _check(self._lib.hpt_accum_reset(self._h, C.c_void_p(stream)))
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.hpt_accum_count(self._h))
+
+    def read(self) -> dict:
+        """Waits for the device: dict(sum [H, W, 3] f32, sumsq (the same, or None without moments), count int)."""
+        s = np.empty((self.H, self.W, 3), np.float32)
+        q = np.empty((self.H, self.W, 3), np.float32) if self.moments else None
+        k = C.c_int64()
+        _check(self._lib.hpt_accum_read(self._h, _vp(s), _vp(q), C.byref(k)))
+        return dict(sum=s, sumsq=q, count=int(k.value))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.hpt_accum_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Display:
+    """The bytes on screen and how much they moved (include/hpt.h, hpt_display_*): present() tone-maps a DEVICE image
+    (int or torch tensor, float32, W*H*3) into a panel of a uint8 framebuffer and sums the squared byte differences
+    against the previous present and against `other`, another Display; metrics() waits for the last present."""
+
+    def __init__(self, W, H):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        self.W, self.H = int(W), int(H)
+        _check(self._lib.hpt_display_create(int(W), int(H), C.byref(self._h)))
+
+    def present(self, linear, out=None, other=None, pitch=0, x_offset=0, bgr=False, flip_y=False, stream: int = 0):
+        flags = (DISPLAY_BGR if bgr else 0) | (DISPLAY_FLIP_Y if flip_y else 0)
+        _check(self._lib.hpt_display_present(self._h, _dptr(linear), other._h if other is not None else None,
+                                             _dptr(out) if out is not None else None, C.c_int64(pitch), C.c_int64(x_offset),
+                                             C.c_int32(flags), C.c_void_p(stream)))
+
+    def metrics(self) -> dict:
+        """dict(rms_prev, rms_other: float; ssd_prev, ssd_other, presented: int) of the last present."""
+        rp, ro = C.c_double(), C.c_double()
+        sp, so = C.c_uint64(), C.c_uint64()
+        n = C.c_int64()
+        _check(self._lib.hpt_display_metrics(self._h, C.byref(rp), C.byref(ro), C.byref(sp), C.byref(so), C.byref(n)))
+        return dict(rms_prev=rp.value, rms_other=ro.value, ssd_prev=int(sp.value), ssd_other=int(so.value), presented=int(n.value))
+
+    def reset(self, stream: int = 0):
+        _check(self._lib.hpt_display_reset(self._h, C.c_void_p(stream)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.hpt_display_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class MultiScene:

@@ -1,0 +1,29 @@
+// pt_cli --frames: the progressive loop of the reference's GUI (src/main.cpp:400-531) with its per-frame host work
+// done on the device.  This header names neither the reference's records nor HIP's, so both scene_model.cpp (which may
+// not see HIP headers, include/hpt_reference_api.hpp) and frame_loop.cpp (which needs them) can include it.
+#pragma once
+#include "../../../include/hpt.h"
+
+#include <string>
+#include <vector>
+
+namespace hpt_host {
+
+// What a frame loop needs of the scene moved for `mode` ("pt", "bdpt" or "ppm"): the single-device handle (null for a
+// fan-out over several devices), its photons / light samples per light, and the run's parameters with the seed taken
+// once, so that every frame of the loop draws from the same streams.  False when nothing was moved.  (scene_model.cpp)
+struct MovedRun { hpt_scene *scene = nullptr; int light_sample = 0; hpt_params params{}; };
+bool moved_run(const std::string &mode, MovedRun &out);
+
+// `frames` frames of `frame_spp` samples (ppm: passes) each, frame f (from 0) with sample_offset = f * frame_spp, every
+// frame accumulated and presented on the device (hpt_accum_add with mean-out, hpt_display_present) on one stream; pt
+// and bdpt never bring a frame to the host, ppm uploads its host image.  After frame f (counted from 1)
+// "<f> <rms_prev, %.9g>" is appended to `rms_log` (when not empty); the loop ends after `frames`, or earlier after a
+// frame >= 2 whose rms_prev <= until_rms (until_rms < 0: off).  `camera` is a CudaCamera; image (W*H*3 floats) receives
+// the final mean and rgb8 the last presented bytes (RGB, rows top to bottom).  Returns the number of frames rendered,
+// -1 after an error (reported on stderr).  (frame_loop.cpp, part of pt_cli only)
+int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
+                   int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,
+                   const std::string &rms_log);
+
+} // namespace hpt_host

@@ -10,10 +10,15 @@
 //   --alpha A         radius reduction of --mode sppm (default 0.7)
 //   --denoise         filter the frame before it is saved: --guide-spp N guide samples (default 4), then the edge-avoiding
 //                     a-trous filter (--denoise-iterations, --sigma-color, --sigma-normal, --sigma-position; 0 = default)
+//   --frames N        progressive: N frames of --frame-spp S samples (default: --spp; ppm: passes), frame f with sample offset
+//                     f * S, accumulated and presented on the device; --rms-log FILE gets "<frame> <rms>" per frame (the
+//                     reference GUI's RMS history, src/main.cpp:502-530), --until-rms R stops after a frame >= 2 whose rms <= R.
+//                     The PNG holds the last presented bytes.  pt, bdpt and ppm on one device.
 // --mode pt, bdpt, ppm and sppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
 // reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
 // averaged, on one device; sppm the same passes into one progressive state whose radius shrinks per pixel.
 #include "scene_model.hpp"
+#include "frame_loop.hpp"
 #include "../../../include/hpt.h"
 
 #include <algorithm>
@@ -36,6 +41,9 @@ int main(int argc, char **argv){
     bool denoise = false;
     int guide_spp = 4;
     hpt_denoise_params filter = { 0, 0.0f, 0.0f, 0.0f, 0 };
+    int frames = 0, frame_spp = 0;
+    double until_rms = -1.0;
+    std::string rms_log;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -59,6 +67,10 @@ int main(int argc, char **argv){
         else if(arg == "--sigma-color" && i + 1 < argc) filter.sigma_color = std::stof(argv[++i]);
         else if(arg == "--sigma-normal" && i + 1 < argc) filter.sigma_normal = std::stof(argv[++i]);
         else if(arg == "--sigma-position" && i + 1 < argc) filter.sigma_position = std::stof(argv[++i]);
+        else if(arg == "--frames" && i + 1 < argc) frames = std::stoi(argv[++i]);
+        else if(arg == "--frame-spp" && i + 1 < argc) frame_spp = std::stoi(argv[++i]);
+        else if(arg == "--until-rms" && i + 1 < argc) until_rms = std::stod(argv[++i]);
+        else if(arg == "--rms-log" && i + 1 < argc) rms_log = argv[++i];
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
@@ -79,7 +91,11 @@ int main(int argc, char **argv){
                       << "  --denoise         denoise the frame before saving it (every mode; with --gpus on device 0)\n"
                       << "  --guide-spp <int> guide samples per pixel of --denoise (default: 4)\n"
                       << "  --denoise-iterations <int>  filter levels, 1..8 (default: 5)\n"
-                      << "  --sigma-color/--sigma-normal/--sigma-position <float>  edge-stopping widths (defaults: 1.0, 0.5, 0.05; < 0: off)\n";
+                      << "  --sigma-color/--sigma-normal/--sigma-position <float>  edge-stopping widths (defaults: 1.0, 0.5, 0.05; < 0: off)\n"
+                      << "  --frames <int>    progressive: frames to accumulate and present on the device (pt, bdpt, ppm; one device)\n"
+                      << "  --frame-spp <int> samples (ppm: passes) per frame (default: --spp)\n"
+                      << "  --until-rms <float>  stop after a frame >= 2 whose RMS against the previous frame is <= this\n"
+                      << "  --rms-log <file>  one line \"<frame> <rms>\" per frame\n";
             return 0;
         }
     }
@@ -92,6 +108,14 @@ int main(int argc, char **argv){
     std::cout << " Output : " << output_file << "\n";
     std::cout << "====================================\n";
     if(mode != "pt" && mode != "bdpt" && mode != "ppm" && mode != "sppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm, sppm).\n"; return -1; }
+    const bool progressive = frames != 0 || frame_spp != 0 || until_rms >= 0.0 || !rms_log.empty();
+    if(progressive){
+        if(frames < 1){ std::cerr << "[Error] --frame-spp, --until-rms and --rms-log need --frames N (N >= 1).\n"; return -1; }
+        if(mode == "sppm"){ std::cerr << "[Error] --frames does not apply to --mode sppm: it keeps its own progressive state (use --spp for its passes).\n"; return -1; }
+        if(hpt_host::g_devices > 1){ std::cerr << "[Error] --frames renders on one device: it cannot be combined with --gpus above 1.\n"; return -1; }
+        if(frame_spp == 0) frame_spp = spp;
+        if(frame_spp < 1){ std::cerr << "[Error] --frame-spp must be at least 1.\n"; return -1; }
+    }
 
     hpt_host::SceneFile scene;
     if(!hpt_host::parse_scene_file(input_file, scene)){
@@ -124,7 +148,14 @@ int main(int argc, char **argv){
 
     std::cout << "[Render] Starting Render...\n";
     auto start_time = std::chrono::steady_clock::now();
-    if(mode == "bdpt") run_cuda_bdpt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp, spl);
+    std::vector<unsigned char> presented;
+    if(progressive){
+        const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
+                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log);
+        if(n < 0) return -1;
+        std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
+    }
+    else if(mode == "bdpt") run_cuda_bdpt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp, spl);
     else if(mode == "ppm") run_cuda_ppm(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
     else if(mode == "sppm") run_cuda_sppm(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
     else run_cuda_pt(cam, frame_results.data(), LIGHT_DEPTH, max_depth, W, H, spp);
@@ -141,7 +172,11 @@ int main(int argc, char **argv){
 
     std::cout << "[Save] Writing to " << output_file << "...\n";
     std::string err;
-    if(hpt_host::write_image(output_file, frame_results.data(), W, H, &err)) std::cout << "[Success] Image saved!\n";
+    const bool png = !(output_file.size() > 4 && output_file.compare(output_file.size() - 4, 4, ".pfm") == 0);
+    // a progressive run's PNG holds the last presented bytes (a denoised frame is tone-mapped afresh)
+    const bool ok = progressive && !denoise && png ? hpt_host::write_png_rgb8(output_file, presented.data(), W, H, &err)
+                                                   : hpt_host::write_image(output_file, frame_results.data(), W, H, &err);
+    if(ok) std::cout << "[Success] Image saved!\n";
     else std::cerr << "[Error] Failed to save image.\n";
     return 0;
 }

@@ -1,6 +1,7 @@
 // Host front-end of the PT / BDPT hot path: scene text + OBJ ingestion, flattening into the boundary records,
 // camera, the reference-named helper API and the output stage.  See scene_model.hpp for what each piece replaces.
 #include "scene_model.hpp"
+#include "frame_loop.hpp"
 #include "text_cursor.hpp"
 #include "../../../include/hpt.h"
 
@@ -493,6 +494,13 @@ bool denoise_frame(const std::string &mode, CudaCamera cam, float3 *image_buffer
     else std::cerr << "denoise_frame: " << hpt_last_error() << std::endl;
     if(own) hpt_scene_destroy(own);
     return rc == HPT_OK;
+}
+
+bool hpt_host::moved_run(const std::string &mode, MovedRun &out){
+    MovedScene &ms = mode == "bdpt" ? g_bdpt : mode == "ppm" ? g_ppm : g_pt;
+    if(!ms.ready()) return false;
+    out.scene = ms.device; out.light_sample = ms.light_sample; out.params = run_params();
+    return true;
 }
 
 // ---- C entry points (tests, Python: scene_io.load_scene_fast / load_obj) ---------------------------------------
