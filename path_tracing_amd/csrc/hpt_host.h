@@ -105,6 +105,7 @@ struct hpt_scene {
         hpt::DevBuf<uint32_t> queue[2];              // path queues (ping-pong)
         hpt::DevBuf<uint32_t> squeue;                // shadow queue (record indices)
         hpt::DevBuf<uint32_t> lqueue[2];             // rays set aside by the first trace launch: closest-hit, shadow
+        hpt::DevBuf<hpt::DeferredRay> rec;           // ... the closest-hit ones past iteration 0 as records (lqueue[0] lists their indices)
         hpt::DevBuf<uint32_t> deep_stack;            // stack levels of the resume launch past its LDS share (launch_trace_resume)
         hpt::DevBuf<uint32_t> counters;
         uint32_t *h_count = nullptr;                 // pinned read-back word

@@ -98,7 +98,15 @@ void launch_connect(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb,
 // merged closest-hit (equeue) + any-hit (squeue) launch; either queue may be absent (null count)
 // split != null && split->budget > 0: rays needing more than `budget` node steps are set aside into the
 // long queues (their counters must be zero on entry) and finished by a second launch
-struct TraceSplit { uint32_t *equeue, *ecount, *squeue, *scount; int budget; };
+// `rec`: the closest-hit rays set aside past iteration 0 travel as records, one per queue position at most; equeue then
+// holds record indices, not path slots.  Three 16-B cells in one place: a lane writes (and the resume launch reads) 48
+// contiguous bytes, the records of neighbouring lanes follow each other, and the kernels carry one pointer
+struct DeferredRay {
+    float4 org_t;          // origin, t of the closest hit so far (1e20: none)
+    float4 dir_slot;       // direction, path slot as bits
+    uint4 hit;             // best primitive (PathBuf::hit.y), its ordinal, two spare words
+};
+struct TraceSplit { uint32_t *equeue, *ecount, *squeue, *scount; int budget; DeferredRay *rec; };
 void launch_trace(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uint32_t *equeue,
                   const uint32_t *ecount, uint32_t max_extend, const uint32_t *squeue, const uint32_t *scount,
                   uint32_t max_shadow, int stack_levels, bool count, WorkCounters *wc,

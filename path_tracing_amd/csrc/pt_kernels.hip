@@ -837,10 +837,10 @@ void k_tonemap(const float *linear, uint32_t *out_words, unsigned long long num_
 // k_trace's registers are fitted to eight waves per SIMD -- vector AND scalar: left alone the compiler takes 106 SGPRs, and
 // more than 96 cap a CU at six 256-thread workgroups whatever the vector registers allow (78 with this attribute, the
 // rest spilled to lanes of a VGPR).  Per instantiation <COUNT, RESUME, TOP, PRIMARY> (scripts/isa_report.py): VGPRs / of them
-// spilled to scratch / SGPRs spilled to lanes = <0,0,1,0> 62 / 0 / 48, <0,0,1,1> 64 / 6 / 61, <0,1,0,0> 57 / 0 / 24,
-// <0,1,0,1> 63 / 0 / 44, <0,0,0,0> 61 / 0 / 50, <0,0,0,1> 64 / 6 / 77, <1,0,0,0> 64 / 11 / 61 (with two exits and a `continue`
+// spilled to scratch / SGPRs spilled to lanes = <0,0,1,0> 59 / 0 / 54, <0,0,1,1> 64 / 6 / 61, <0,1,0,0> 57 / 0 / 22,
+// <0,1,0,1> 63 / 0 / 44, <0,0,0,0> 57 / 0 / 60, <0,0,0,1> 64 / 6 / 77, <1,0,0,0> 64 / 11 / 61 (with two exits and a `continue`
 // in trace_chunk's loop: 64 / 2 / 54, 64 / 11 / 87, 58 / 0 / 36, 64 / 0 / 66, 64 / 2 / 59, 64 / 11 / 89, 64 / 56 / 65;
-// tests/test_trace_isa_cpu.py holds the VGPR side).  Measured against the unconstrained build: first launch 11.37 -> 11.00 ms, resume
+// tests/test_trace_isa_cpu.py and tests/test_trace_register_fit_cpu.py hold the VGPR side).  Measured against the unconstrained build: first launch 11.37 -> 11.00 ms, resume
 // 8.14 -> 7.70 per 64-spp pass of config 3, 14.00 -> 13.46 on the 1 M-triangle shape.  `make variant EXTRA=-DHPT_TRACE_WAVES=0`
 // builds without it, =7 with seven.
 #ifndef HPT_TRACE_WAVES
@@ -868,8 +868,8 @@ constexpr uint32_t kTraceShortQueue = 1u << 20;   // below this many rays a work
 template <bool ANY, bool COUNT, bool RESUME, bool TOP, bool PRIMARY>
 HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uint32_t *queue,
                          uint32_t end, uint32_t *stk, uint32_t *s_next, int refill_min, int node_min, WorkCounters *wc,
-                         uint32_t budget, uint32_t *s_long, uint32_t *s_nlong, const uint4 *top, const PrimaryGen &pg,
-                         uint32_t *deep, uint32_t deep_stride){
+                         uint32_t budget, DeferredRay *rec, uint32_t *s_long, uint32_t *s_nlong, const uint4 *top,
+                         const PrimaryGen &pg, uint32_t *deep, uint32_t deep_stride){
     bool active = false, exhausted = false;
     uint32_t path = 0u, cur = 0u, steps = 0u;
     int sp = 0;
@@ -895,8 +895,19 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                 if((int) lane == dleader) dbase = atomicAdd(s_nlong, dn);
                 dbase = (uint32_t) __shfl((int) dbase, dleader, 64);
                 if(defer){
-                    s_long[dbase + dprefix] = path;
-                    if(!ANY) pb.hit[path] = make_uint2(f2u(best_t), best_prim);
+                    if(!ANY && !PRIMARY && !COUNT){
+                        // a closest-hit ray leaves as a dense record: s_nlong started at the chunk's first queue position, a chunk
+                        // sets aside at most as many rays as it holds and the chunks' ranges are disjoint, so the places of two
+                        // chunks never meet (k_shade's argument for the shadow records).  Everything the resume launch needs to
+                        // start the ray is in the lane; pb.hit[path] is written by that launch alone
+                        DeferredRay *r = rec + (dbase + dprefix);
+                        r->org_t = make_float4(ro.x, ro.y, ro.z, best_t);
+                        r->dir_slot = make_float4(rd.x, rd.y, rd.z, u2f(path));
+                        r->hit = make_uint4(best_prim, best_ord, 0u, 0u);
+                    } else {
+                        s_long[dbase + dprefix] = path;
+                        if(!ANY) pb.hit[path] = make_uint2(f2u(best_t), best_prim);
+                    }
                     active = false;
                 }
             }
@@ -932,7 +943,18 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                         limit = tmax;
                     } else {
                         bool outside;
-                        if(PRIMARY){
+                        if(RESUME && !PRIMARY){
+                            // the queue entry is a record index: the ray, the closest hit of the first launch (the limit the walk
+                            // restarts with), its ordinal and the path slot, all from the record -- no gather through the slot
+                            const DeferredRay *r = rec + path;
+                            float4 o = r->org_t, d = r->dir_slot;
+                            uint4 h = r->hit;
+                            ro = xyz(o); rd = xyz(d);
+                            best_t = o.w; best_prim = h.x; best_ord = h.y;
+                            path = f2u(d.w);
+                            limit = best_t;
+                            outside = false;                                    // a ray that was set aside is inside the image
+                        } else if(PRIMARY){
                             // iteration 0 without a generate launch: the camera ray of this slot, recomputed (the first
                             // launch reads the identity queue, the resume launch the slots it was handed)
                             uint64_t rs_unused;
@@ -945,12 +967,14 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
                         }
                         if(outside) start = false;                          // slot outside the image
                         else if(RESUME){
-                            // restart with the closest hit of the first launch as the limit
-                            uint2 h = pb.hit[path];
-                            best_t = u2f(h.x); best_prim = h.y; best_ord = 0xFFFFFFFFu;
-                            if(best_prim != kHitMiss)
-                                best_ord = (best_prim & kHitRoundFlag) ? (best_prim & ~kHitRoundFlag) : f2u(sc.tris[(size_t) best_prim * 3].w);
-                            limit = best_t;
+                            if(PRIMARY){
+                                // iteration 0 handed slots over: restart with the closest hit of the first launch as the limit
+                                uint2 h = pb.hit[path];
+                                best_t = u2f(h.x); best_prim = h.y; best_ord = 0xFFFFFFFFu;
+                                if(best_prim != kHitMiss)
+                                    best_ord = (best_prim & kHitRoundFlag) ? (best_prim & ~kHitRoundFlag) : f2u(sc.tris[(size_t) best_prim * 3].w);
+                                limit = best_t;
+                            }
                         } else {
                             if(COUNT) n_rays += 1;
                             best_t = 1e20f; best_prim = kHitMiss; best_ord = 0xFFFFFFFFu;
@@ -1153,12 +1177,14 @@ HPT_DEV void trace_chunk(const SceneDev &sc, PathBuf pb, ShadowBuf sb, const uin
 }
 
 // Two-launch split of one trace step (budget != 0): the first launch gives every ray `budget` node
-// steps; rays that need more (the few that run deep into a dense mesh) are set aside -- their slots
-// collected in LDS and appended to the long queue with one global atomic per workgroup -- and a second
-// launch (RESUME) restarts them with the partial result as the limit.  Lanes of the first launch are
+// steps; rays that need more (the few that run deep into a dense mesh) are set aside -- appended to the
+// long queue with one global atomic per workgroup: shadow rays and the closest-hit rays of iteration 0 as
+// the queue entries they came with, collected in LDS, closest-hit rays of later iterations as records
+// (DeferredRay) written from the chunk's first queue position on -- and a second launch (RESUME) restarts
+// them with the partial result as the limit.  Lanes of the first launch are
 // therefore never parked on a long ray while the short rays around them wait for a refill; the result
 // is the same (closest hit with the ordinal tie-break, or the occlusion boolean, of the same ray).
-struct LongQueues { uint32_t *equeue, *ecount, *squeue, *scount; uint32_t budget; };
+struct LongQueues { uint32_t *equeue, *ecount, *squeue, *scount; uint32_t budget; DeferredRay *rec; };
 
 template <bool COUNT, bool RESUME, bool TOP, bool PRIMARY>
 __global__ __launch_bounds__(kBlock) HPT_TRACE_ATTR
@@ -1186,22 +1212,25 @@ void k_trace(SceneDev sc, PathBuf pb, ShadowBuf sb, const uint32_t *equeue, cons
         uint32_t begin = chunk * csize;
         uint32_t total = shadow ? scount : ecount;
         uint32_t end = begin + csize < total ? begin + csize : total;
-        if(threadIdx.x == 0){ s_next = begin; s_nlong = 0u; }
+        // closest-hit rays past iteration 0 are set aside as records at `begin` + rank (trace_chunk): their count starts there
+        const bool records = !shadow && !PRIMARY && !COUNT;      // (a counting launch is never split)
+        const uint32_t lbase = records ? begin : 0u;
+        if(threadIdx.x == 0){ s_next = begin; s_nlong = lbase; }
         __syncthreads();
         uint32_t *deep_lane = RESUME ? deep + (size_t) blockIdx.x * kBlock + threadIdx.x : nullptr;
         const uint32_t deep_stride = gridDim.x * kBlock;
         if(shadow) trace_chunk<true, COUNT, RESUME, TOP, false>(sc, pb, sb, squeue, end, s_dyn_stack + threadIdx.x, &s_next, refill_min, node_min, wc,
-                                                                lq.budget, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
+                                                                lq.budget, lq.rec, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
         else trace_chunk<false, COUNT, RESUME, TOP, PRIMARY>(sc, pb, sb, equeue, end, s_dyn_stack + threadIdx.x, &s_next, refill_min, node_min, wc,
-                                                             lq.budget, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
+                                                             lq.budget, lq.rec, s_long, &s_nlong, s_top, pg, deep_lane, deep_stride);
         __syncthreads();
         if(!RESUME && lq.budget != 0u){
-            uint32_t n = s_nlong;
+            uint32_t n = s_nlong - lbase;
             if(n != 0u){
                 if(threadIdx.x == 0) s_gbase = atomicAdd(shadow ? lq.scount : lq.ecount, n);
                 __syncthreads();
                 uint32_t *dst = (shadow ? lq.squeue : lq.equeue) + s_gbase;
-                for(uint32_t i = threadIdx.x; i < n; i += kBlock) dst[i] = s_long[i];
+                for(uint32_t i = threadIdx.x; i < n; i += kBlock) dst[i] = records ? begin + i : s_long[i];
             }
         }
         __syncthreads();
@@ -1366,7 +1395,7 @@ void launch_trace(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBuf sb, c
     LongQueues lq{};
     if(split && split->budget > 0 && !count){
         lq.equeue = split->equeue; lq.ecount = split->ecount; lq.squeue = split->squeue; lq.scount = split->scount;
-        lq.budget = (uint32_t) split->budget;
+        lq.budget = (uint32_t) split->budget; lq.rec = split->rec;
         // a ray of this launch is set aside after `budget` node steps, so its stack never grows past that many entries
         if(stack_levels > split->budget) stack_words = (split->budget + 1) * kBlock;
     }
@@ -1399,6 +1428,7 @@ void launch_trace_resume(hipStream_t s, const SceneDev &sc, PathBuf pb, ShadowBu
     uint32_t g2 = g < kResumeMaxGroups ? (uint32_t) (g < 1u ? 1u : g) : kResumeMaxGroups;
     if(max_groups != 0u && g2 > max_groups) g2 = max_groups;          // blind tail iterations (HPT_FLAG_NO_HOST_WAIT)
     LongQueues none{};
+    none.rec = split.rec;                                             // read here: the rays launch_trace wrote there
     PrimaryGen no_primary{};
     const uint32_t *eq = extend ? split.equeue : nullptr, *ec = extend ? split.ecount : nullptr;
     const uint32_t *sq = shadow ? split.squeue : nullptr, *scn = shadow ? split.scount : nullptr;

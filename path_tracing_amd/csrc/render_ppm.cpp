@@ -102,7 +102,7 @@ struct PpmStep {
                                                 budget(resume_walk_fits(s_->geo.sd) ? kTraceBudget : 0) {}
     // closest-hit rays of the queue in cnt[it] (it = 0: the identity queue), the PT path's split trace step
     void trace(int it, const uint32_t *queue, uint32_t *cnt, uint32_t *lcnt, uint32_t max_items) const {
-        TraceSplit split{ w.lqueue[0].get(), &lcnt[it], w.lqueue[1].get(), no_shadow, budget };
+        TraceSplit split{ w.lqueue[0].get(), &lcnt[it], w.lqueue[1].get(), no_shadow, budget, w.rec.get() };
         launch_trace(st, s->geo.sd, w.pb, w.sb, queue, &cnt[it], max_items, nullptr, nullptr, 0, s->geo.stack_levels, false, nullptr, &split, nullptr, 0u);
         if(budget > 0) launch_trace_resume(st, s->geo.sd, w.pb, w.sb, true, false, max_items, nullptr, split, nullptr, 0u, w.deep_stack.get());
     }

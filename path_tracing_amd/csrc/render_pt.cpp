@@ -14,12 +14,13 @@ using namespace hpt;
 
 namespace {
 
-// device memory per path slot of one pipeline (ensure_pass): path state 80 B, pending shadow ray 48 B, five queues of 4 B
-constexpr double kBytesPerPathSlot = 148.0;
+// device memory per path slot of one pipeline (ensure_pass): path state 80 B, pending shadow ray 48 B, five queues of 4 B,
+// the record of a closest-hit ray set aside for the resume launch 48 B
+constexpr double kBytesPerPathSlot = 196.0;
 
 int ensure_pass(PassBuffers &w, size_t paths, int n_counters){
     const hipError_t e = reserve_all(paths, w.org_eta, w.dir_flags, w.thr, w.col, w.rng, w.hit, w.org_max, w.dir, w.contrib,
-                                     w.queue[0], w.queue[1], w.squeue, w.lqueue[0], w.lqueue[1]);
+                                     w.queue[0], w.queue[1], w.squeue, w.lqueue[0], w.lqueue[1], w.rec);
     w.pb = PathBuf{ w.org_eta.get(), w.dir_flags.get(), w.thr.get(), w.col.get(), w.rng.get(), w.hit.get() };
     w.sb = ShadowBuf{ w.org_max.get(), w.dir.get(), w.contrib.get() };
     if(e != hipSuccess) return fail_hip("path workspace", e);
@@ -91,7 +92,7 @@ int hpt_render_pt_device(hpt_scene *s, const void *camera, int W, int H, int eye
     const bool brute = (flags & HPT_FLAG_BRUTE_FORCE) != 0;      // separate extend/connect kernels (the scan variants)
     const int kflags = (brute ? 1 : 0) | (count ? 2 : 0);
 
-    // Samples in flight per pass: about 128 Mi path slots (19 GiB of path state, queues and shadow records per pipeline:
+    // Samples in flight per pass: about 128 Mi path slots (24.5 GiB of path state, queues, shadow and deferred-ray records per pipeline:
     // little on a 288 GB device).  Fewer, larger passes amortise the low-occupancy tail iterations of every pass
     // (config 3, ms per 256-spp render, one pipeline: 4 Mi slots 291, 16 Mi 219, 64 Mi 146, 128 Mi 142, 256 Mi 139).
     // Two passes are in flight at a time, on two streams with a workspace each: while one pipeline's kernel drains or
@@ -158,7 +159,7 @@ int hpt_render_pt_device(hpt_scene *s, const void *camera, int W, int H, int eye
 
     // one pass in flight on one pipeline
     struct Pass {
-        PathBuf pb; ShadowBuf sb; uint32_t *queue[2], *squeue, *lqueue[2], *deep_stack; uint32_t *counters, *h_count; hipStream_t st;
+        PathBuf pb; ShadowBuf sb; DeferredRay *rec; uint32_t *queue[2], *squeue, *lqueue[2], *deep_stack; uint32_t *counters, *h_count; hipStream_t st;
         int sthis = 0, cur = 0, pending_shadow = -1; uint32_t slots = 0; PrimaryGen primary{};
         uint32_t *qcnt = nullptr, *scnt = nullptr, *lecnt = nullptr, *lscnt = nullptr;
     };
@@ -166,7 +167,7 @@ int hpt_render_pt_device(hpt_scene *s, const void *camera, int W, int H, int eye
     for(int k = 0; k < npipes; ++k){
         const PassBuffers &w = s->ws.pass[k];
         Pass &q = pipe[k];
-        q.pb = w.pb; q.sb = w.sb; q.queue[0] = w.queue[0].get(); q.queue[1] = w.queue[1].get(); q.squeue = w.squeue.get();
+        q.pb = w.pb; q.sb = w.sb; q.rec = w.rec.get(); q.queue[0] = w.queue[0].get(); q.queue[1] = w.queue[1].get(); q.squeue = w.squeue.get();
         q.lqueue[0] = w.lqueue[0].get(); q.lqueue[1] = w.lqueue[1].get();
         q.deep_stack = w.deep_stack.get();
         q.counters = w.counters.get(); q.h_count = w.h_count; q.st = k == 0 ? stream : s->ws.px_stream[k];
@@ -210,7 +211,7 @@ int hpt_render_pt_device(hpt_scene *s, const void *camera, int W, int H, int eye
             launch_extend(q.st, s->geo.sd, q.pb, eq, &q.qcnt[it], q.slots, kflags, wc);
         } else {
             // extension rays of this iteration + shadow rays of the previous one, one launch
-            TraceSplit split{ q.lqueue[0], &q.lecnt[it], q.lqueue[1], &q.lscnt[it], budget };
+            TraceSplit split{ q.lqueue[0], &q.lecnt[it], q.lqueue[1], &q.lscnt[it], budget, q.rec };
             { LaunchTimer t(s, q.st, timek, 0);
               launch_trace(q.st, s->geo.sd, q.pb, q.sb, eq, &q.qcnt[it], q.slots, q.squeue,
                            q.pending_shadow >= 0 ? &q.scnt[q.pending_shadow] : nullptr, q.slots, s->geo.stack_levels, count, wc, &split, primary, cap); }
@@ -255,7 +256,7 @@ int hpt_render_pt_device(hpt_scene *s, const void *camera, int W, int H, int eye
         for(int k = 0; k < npipes; ++k){
             Pass &q = pipe[k];
             if(q.pending_shadow < 0) continue;
-            TraceSplit split{ q.lqueue[0], &q.lecnt[max_iters], q.lqueue[1], &q.lscnt[max_iters], budget };
+            TraceSplit split{ q.lqueue[0], &q.lecnt[max_iters], q.lqueue[1], &q.lscnt[max_iters], budget, q.rec };
             { LaunchTimer t(s, q.st, timek, 2);
               launch_trace(q.st, s->geo.sd, q.pb, q.sb, nullptr, nullptr, 0, q.squeue, &q.scnt[q.pending_shadow], q.slots,
                            s->geo.stack_levels, count, wc, &split, nullptr, blind_groups); }
