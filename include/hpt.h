@@ -353,7 +353,8 @@ void hpt_tonemap_reference(const float *linear_rgb, unsigned char *rgb8, int64_t
  * The reference's GUI renders 8 spp per frame and throws its accumulation away whenever the camera moves
  * (src/main.cpp:406-466); it has no denoiser.  These calls add the standard two steps for such sample counts:
  * cheap noise-free guide images of the first rough surface behind every pixel, and an edge-avoiding a-trous wavelet
- * filter (Dammertz et al. 2010) over the noisy radiance, steered by them.
+ * filter (Dammertz et al. 2010) over the noisy radiance, steered by them.  The position and normal guides also steer
+ * hpt_history ("history across camera moves", below), which keeps the accumulation when the camera moves.
  *
  * hpt_render_guides: for sample s = 0 .. spp-1, photon mapping's eye pass of pass index (low 32 bits of)
  * sample_offset + s -- streams (seed ^ eye key, pixel, pass), jitter, free delta bounces capped at max_delta, all as
@@ -410,6 +411,12 @@ typedef struct hpt_denoise_params {
 int hpt_render_guides(hpt_scene *scene, const void *camera, int W, int H, int spp,
                       const hpt_params *params,
                       float *albedo, float *normal, float *position, float *coverage);
+/* The same call with four DEVICE output images (any may be NULL, not all four): the same bytes, left on the scene's
+ * device; the call returns when they are complete.  A viewer that moves its camera every frame hands them to
+ * hpt_history_advance and never brings 40 bytes per pixel to the host and back. */
+int hpt_render_guides_device(hpt_scene *scene, const void *camera, int W, int H, int spp,
+                             const hpt_params *params,
+                             void *d_albedo, void *d_normal, void *d_position, void *d_coverage);
 
 typedef struct hpt_denoiser hpt_denoiser;
 int hpt_denoiser_create(int W, int H, hpt_denoiser **out);
@@ -443,7 +450,7 @@ int hpt_denoise_host(const float *linear_rgb, const float *albedo, const float *
  *             general-purpose variance: q and m * m are rounded floats of nearly equal size, so below a relative
  *             variance of about 1e-7 (2^-23) their difference is rounding, not signal (a constant frame gives exactly 0).
  *   reset     zeroes the sums on the stream and sets K = 0; the reference's restart when the camera moves
- *             (main.cpp:453-466) is reset followed by add.
+ *             (main.cpp:453-466) is reset followed by add (hpt_history, below, carries the mean over instead).
  * Every call only enqueues on hip_stream, except hpt_accum_read, which waits for the device and copies the sums to
  * the host (for tests; either image may be NULL).  hpt_accum_create allocates on the current device, sums zeroed.
  * W or H below 1 (or W*H above 2^28), an unknown flag, variance (or a sumsq read) without MOMENTS, a NULL handle, a
@@ -490,6 +497,98 @@ int  hpt_display_metrics(hpt_display *d, double *rms_prev, double *rms_other,
                          uint64_t *ssd_prev, uint64_t *ssd_other, int64_t *presented);
 int  hpt_display_reset(hpt_display *d, void *hip_stream);
 void hpt_display_destroy(hpt_display *d);
+
+/* ---- history across camera moves ---------------------------------------------------------------------
+ * The reference's GUI discards its running average whenever the camera moves (src/main.cpp:453-466), and hpt_accum can
+ * only be reset the same way: every pixel starts again from one noisy frame, even where the same surface point was on
+ * screen a frame ago with tens of samples behind it.  hpt_history is a per-pixel running mean that survives the move:
+ * it looks up where each pixel's guide point (hpt_render_guides) was in the previous frame and carries that pixel's
+ * mean and sample count over when the geometry agrees.
+ *
+ * Conventions as for hpt_accum / hpt_display: images are device pointers in the layouts hpt_untile and
+ * hpt_render_guides write (frame, normal, position, mean: W*H*3 floats; coverage: W*H; row-major, row 0 = top);
+ * advance and reset only enqueue on hip_stream; metrics and read wait for the device; create allocates on the current
+ * device (96 bytes per pixel).  Every refusal is made, with a message, before anything touches the device.
+ *
+ * State per pixel: mean (3 floats), history length n (float), and the last frame's guide position, normal and coverage,
+ * held in two sets (a pixel reads its neighbours' previous state, so a moved frame writes the other set).  The object
+ * also keeps the previous camera record and K, the number of advances since create or reset.
+ *
+ * Camera constants.  For a camera (eye, UL, dx, dy) the host computes, in float, evaluated as written, with
+ * dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z left to right and cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x):
+ *   a = UL - eye;  nrm = cross(dx, dy);  an = dot(a, nrm);
+ *   cu = cross(dy, nrm);  gu = cu / dot(dx, cu) per component;   cv = cross(nrm, dx);  gv = cv / dot(dy, cv).
+ * They are all the kernel reads of a camera.  A camera whose constants (eye included) are not all finite, or whose an
+ * is 0, is refused.
+ *   project(cam, X):  d = X - eye;  den = dot(d, nrm);  s = an / den;  r = d * s - a (per component: d.x * s - a.x);
+ *                     u = dot(r, gu);  v = dot(r, gv);  dist2 = dot(d, d).
+ * (u, v) is the continuous pixel coordinate under which the primary ray eye -> UL + u dx + v dy sees X, and s > 0 says
+ * that X lies in front of the camera.
+ *
+ * hpt_history_advance, for pixel p = (x, y) with frame colour c; every comparison below is false for a NaN operand:
+ *   1. K = 0: n_r = 0.
+ *   2. else, the camera's 84 bytes equal the previous advance's: m = mean[p], n_r = n[p].  No test is applied, so a
+ *      still camera is a plain running mean whatever the guides say.
+ *   3. else, the guide pointers are NULL or coverage[p] > 0 is false: n_r = 0.
+ *   4. else X = position[p], N = normal[p]:
+ *      direct view   P = project(this camera, X) must give P.s > 0, |P.u - ((float) x + 0.5f)| <= 1 and
+ *                    |P.v - ((float) y + 0.5f)| <= 1.  A pixel whose guide point lies behind a mirror or glass bounce
+ *                    does not project onto itself: it restarts rather than inherit history from the wrong place.
+ *      range         Q = project(previous camera, X) must give Q.s > 0 and, with up = Q.u - 0.5f, vp = Q.v - 0.5f:
+ *                    up >= -1, up < (float) W, vp >= -1, vp < (float) H -- compared in float BEFORE any conversion to
+ *                    integer, so NaN and infinity fail here and are never converted.  x0 = floorf(up), fx = up - x0,
+ *                    y0 = floorf(vp), fy = vp - y0.
+ *      taps          sum = (0, 0, 0), nsum = 0, wsum = 0; for j = 0, 1 (outer), i = 0, 1 (inner), q = (x0 + i, y0 + j),
+ *                    skipped when q lies outside the image, when coverage_prev[q] > 0 is false, when (plane test on)
+ *                    t = dot(N, position_prev[q] - X) fails t * t <= tol2 * P.dist2 with tol2 = plane_tolerance *
+ *                    plane_tolerance computed on the host, or when (normal test on) dot(N, normal_prev[q]) >= normal_min
+ *                    is false.  Otherwise w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy); sum = sum + mean_prev[q] * w per
+ *                    channel, nsum = nsum + n_prev[q] * w, wsum = wsum + w.
+ *      result        wsum > 0.01f: m = sum / wsum per channel, n_r = nsum / wsum; otherwise n_r = 0 (a history held up
+ *                    by a sliver of one tap is extrapolation, and 1 / wsum amplifies its rounding).
+ *      Either failed test gives n_r = 0.
+ *   5. n_r > 0 is false: mean = c, n = 1.  Otherwise n_c = fminf(n_r, max_history - 1) (the difference computed on the
+ *      host), mean = (m * n_c + c) / (n_c + 1.0f) per channel, n = n_c + 1.0f.
+ *   6. mean, n and this frame's position, normal and coverage become the pixel's previous state; with NULL guides the
+ *      stored guides are kept on an unmoved camera and become coverage 0 otherwise (K = 0 or a moved camera) -- which
+ *      makes a moved sequence without guides exactly the reference's restart.  d_mean_out, when not NULL, receives
+ *      mean; it may be d_frame_rgb itself, any other overlap among the caller's five images is refused.  The camera is
+ *      stored and K incremented when the call is enqueued.
+ *   kept counts the pixels with n_r > 0, restarted those without on a frame with K > 0 (so kept + restarted = W*H on
+ *   every frame but the first, where both are 0).  Both are exact 64-bit integers and do not depend on the grid.
+ * The tap order is part of the definition; everything is IEEE float, evaluated as written.
+ *
+ * p NULL = all defaults.  The guide pointers are given all three or not at all.  hpt_history_metrics returns the counts
+ * of the last advance (any output may be NULL; HPT_ERR_INVALID before the first advance and after a reset);
+ * hpt_history_read copies the current mean (W*H*3) and n (W*H) to the host (either may be NULL) and K.  hpt_history_reset
+ * zeroes the current state on the stream and sets K = 0.  hpt_history_check runs every argument check of an advance on a
+ * W x H history without a handle or a device (a front-end can validate before it allocates; tests).
+ *
+ * Limits.  History is colour only: no second moment, no variance-guided filtering.  The guide position is an average
+ * over jittered samples, so pixels that straddle an edge mostly fail the direct-view or the plane test and restart.
+ * There are no motion vectors: the scene is static in this library.  Once n reaches max_history the mean turns into an
+ * exponential average with weight 1 / max_history for the new frame, which is what lets lighting seen from a new angle
+ * (a highlight, a reflection) converge to its new value instead of keeping the old one forever. */
+typedef struct hpt_history hpt_history;
+typedef struct hpt_history_params {
+    float max_history;      /* cap on a pixel's history length; 0 -> 256; < 1 or NaN: HPT_ERR_INVALID */
+    float plane_tolerance;  /* 0 -> 0.01: a tap is kept while its stored point lies within this fraction of the
+                               eye distance of the pixel's tangent plane; < 0: test off; NaN: HPT_ERR_INVALID */
+    float normal_min;       /* 0 -> 0.9: least dot product of the two guide normals; < -1: test off; NaN: HPT_ERR_INVALID */
+    int32_t flags;          /* must be 0 */
+} hpt_history_params;
+int  hpt_history_create(int W, int H, hpt_history **out);
+int  hpt_history_advance(hpt_history *h, const void *camera, const void *d_frame_rgb,
+                         const void *d_normal, const void *d_position, const void *d_coverage,
+                         const hpt_history_params *p, void *d_mean_out, void *hip_stream);
+int  hpt_history_metrics(hpt_history *h, uint64_t *kept, uint64_t *restarted, int64_t *frames);
+int  hpt_history_read(hpt_history *h, float *mean, float *length, int64_t *frames);
+int  hpt_history_reset(hpt_history *h, void *hip_stream);
+void hpt_history_destroy(hpt_history *h);
+int  hpt_history_check(int W, int H, const void *camera, const void *d_frame_rgb,
+                       const void *d_normal, const void *d_position, const void *d_coverage,
+                       const hpt_history_params *p, const void *d_mean_out);
 
 /* ---- the acceleration structure, exported (tests) -------------------------------------
  * The reference has no acceleration structure (include/geometric.cuh:293-388 scan every primitive); the tree the

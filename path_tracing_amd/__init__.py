@@ -85,6 +85,16 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float), ("flags", C.c_int32)]
 
 
+class HistoryParams(C.Structure):
+    """hpt_history_params (include/hpt.h): zeros select the defaults (max_history 256, plane_tolerance 0.01, normal_min
+    0.9); a negative tolerance or a normal_min below -1 switches its test off."""
+    _fields_ = [("max_history", C.c_float), ("plane_tolerance", C.c_float), ("normal_min", C.c_float), ("flags", C.c_int32)]
+
+
+def make_history_params(max_history=0.0, plane_tolerance=0.0, normal_min=0.0) -> HistoryParams:
+    return HistoryParams(float(max_history), float(plane_tolerance), float(normal_min), 0)
+
+
 def make_denoise_params(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_position=0.0, demodulate=True, time=False) -> DenoiseParams:
     return DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position),
                          (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TIME if time else 0))
@@ -146,7 +156,9 @@ def load_library() -> C.CDLL:
                      "hpt_render_guides", "hpt_denoiser_create", "hpt_denoiser_set_guides", "hpt_denoiser_run",
                      "hpt_denoiser_last_ms", "hpt_denoiser_level_ms", "hpt_denoise_host",
                      "hpt_accum_create", "hpt_accum_add", "hpt_accum_mean", "hpt_accum_variance", "hpt_accum_reset", "hpt_accum_read",
-                     "hpt_display_create", "hpt_display_present", "hpt_display_metrics", "hpt_display_reset"):
+                     "hpt_display_create", "hpt_display_present", "hpt_display_metrics", "hpt_display_reset",
+                     "hpt_render_guides_device", "hpt_history_create", "hpt_history_advance", "hpt_history_metrics",
+                     "hpt_history_read", "hpt_history_reset", "hpt_history_check"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -155,7 +167,7 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "hpt_denoiser_destroy"):
             lib.hpt_denoiser_destroy.restype = None
             lib.hpt_denoiser_destroy.argtypes = [C.c_void_p]
-        for name in ("hpt_accum_destroy", "hpt_display_destroy"):
+        for name in ("hpt_accum_destroy", "hpt_display_destroy", "hpt_history_destroy"):
             if hasattr(lib, name):
                 getattr(lib, name).restype = None
                 getattr(lib, name).argtypes = [C.c_void_p]
@@ -302,6 +314,15 @@ class Scene:
         _check(self._lib.hpt_render_guides(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), _vp(g["albedo"]),
                                            _vp(g["normal"]), _vp(g["position"]), _vp(g["coverage"])))
         return g
+
+    def render_guides_device(self, camera, W, H, spp=4, params: Params | None = None, albedo=None, normal=None, position=None,
+                             coverage=None):
+        """render_guides into DEVICE images (ints or torch tensors, float32, [H, W, 3]; coverage [H, W]; None = not
+        wanted, at least one is): the same bytes, complete when the call returns."""
+        params = params or make_params()
+        cam = np.ascontiguousarray(camera, CAMERA)
+        ptr = [_dptr(x) if x is not None else None for x in (albedo, normal, position, coverage)]
+        _check(self._lib.hpt_render_guides_device(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), *ptr))
 
     def stats(self) -> dict:
         st = Stats()
@@ -532,6 +553,63 @@ class Display:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.hpt_display_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class History:
+    """Per-pixel running mean that survives camera moves (include/hpt.h, hpt_history_*) for W x H images.  advance() takes
+    the frame's camera record, its DEVICE colour image and the three DEVICE guide images of Scene.render_guides_device
+    (all three or none), reprojects the previous state where the geometry agrees and writes the new mean; metrics()
+    waits for the last advance.  Every other call only enqueues on `stream`, except read()."""
+
+    def __init__(self, W, H):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        self.W, self.H = int(W), int(H)
+        _check(self._lib.hpt_history_create(int(W), int(H), C.byref(self._h)))
+
+    def advance(self, camera, frame, normal=None, position=None, coverage=None, params: HistoryParams | None = None, mean_out=None,
+                stream: int = 0):
+        """mean_out (may be `frame` itself) receives the new mean; params None = the defaults."""
+        cam = np.ascontiguousarray(camera, CAMERA)
+        opt = [_dptr(x) if x is not None else None for x in (normal, position, coverage)]
+        _check(self._lib.hpt_history_advance(self._h, _vp(cam.reshape(1)), _dptr(frame), opt[0], opt[1], opt[2],
+                                             C.byref(params) if params is not None else None,
+                                             _dptr(mean_out) if mean_out is not None else None, C.c_void_p(stream)))
+
+    def metrics(self) -> dict:
+        """dict(kept, restarted, frames: int) of the last advance."""
+        k, r = C.c_uint64(), C.c_uint64()
+        n = C.c_int64()
+        _check(self._lib.hpt_history_metrics(self._h, C.byref(k), C.byref(r), C.byref(n)))
+        return dict(kept=int(k.value), restarted=int(r.value), frames=int(n.value))
+
+    def read(self) -> dict:
+        """Waits for the device: dict(mean [H, W, 3] f32, length [H, W] f32, frames int)."""
+        m = np.empty((self.H, self.W, 3), np.float32)
+        n = np.empty((self.H, self.W), np.float32)
+        k = C.c_int64()
+        _check(self._lib.hpt_history_read(self._h, _vp(m), _vp(n), C.byref(k)))
+        return dict(mean=m, length=n, frames=int(k.value))
+
+    def reset(self, stream: int = 0):
+        _check(self._lib.hpt_history_reset(self._h, C.c_void_p(stream)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.hpt_history_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

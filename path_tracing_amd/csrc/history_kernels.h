@@ -1,0 +1,45 @@
+// Launch interface of the temporal-history kernel (history_kernels.hip): the per-pixel running mean that is carried over
+// when the camera moves (include/hpt.h, "history across camera moves").
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace hpt {
+
+// The constants project() reads (include/hpt.h), computed by the host in float from a camera (eye, UL, dx, dy).
+struct HistoryCamera {
+    float eye[3], a[3], nrm[3], gu[3], gv[3];
+    float an;
+};
+
+// One set of per-pixel state: three 16-byte records per pixel, so a tap is three 16-byte loads.
+struct HistorySet {
+    float4 *mean_n;      // mean.rgb, n
+    float4 *pos_cov;     // position.xyz, coverage
+    float4 *nrm;         // normal.xyz, 0
+};
+
+enum HistoryMode : int { kHistoryFirst = 0, kHistoryIdentity = 1, kHistoryMoved = 2 };
+
+struct HistoryArgs {
+    HistorySet prev, next;           // first / identity: the kernel works in place on `next` (prev == next)
+    const float *frame;              // 3 W H
+    const float *normal, *position;  // 3 W H each, or all three guides null
+    const float *coverage;           // W H
+    float *mean_out;                 // 3 W H or null; may be `frame`
+    unsigned long long *metrics;     // [0] += kept, [1] += restarted; zeroed by the caller before the launch
+    HistoryCamera cam, cam_prev;
+    int W, H;
+    int mode;                        // HistoryMode, the same for every lane
+    float max_history_m1;            // max_history - 1
+    float tol2;                      // plane_tolerance * plane_tolerance
+    float normal_min;
+    int plane_on, normal_on;
+};
+// one lane per pixel; the grid depends on W and H only
+void launch_history_advance(hipStream_t s, const HistoryArgs &a);
+
+// out[k] = in[3 k] for k < n: the coverage image out of the three-channel image launch_untile writes
+void launch_take_first_channel(hipStream_t s, const float *in3, float *out, uint32_t n);
+
+} // namespace hpt

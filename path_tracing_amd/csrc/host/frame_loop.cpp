@@ -1,9 +1,11 @@
-// pt_cli --frames (frame_loop.hpp): render, untile, accumulate and present every frame on one stream, read two sums back.
+// pt_cli --frames (frame_loop.hpp): render, untile, accumulate (or, with --reproject, advance the history) and present every
+// frame on one stream, read the sums back.
 #include "frame_loop.hpp"
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
+#include <cstring>
 #include <iostream>
 
 namespace {
@@ -17,11 +19,13 @@ struct DeviceMem {      // one allocation, released with the loop
 struct Loop {
     hpt_accum *accum = nullptr;
     hpt_display *display = nullptr;
+    hpt_history *history = nullptr;
     hipStream_t stream = nullptr;
     FILE *log = nullptr;
     ~Loop(){
         if(log) fclose(log);
         if(stream){ (void) hipStreamSynchronize(stream); (void) hipStreamDestroy(stream); }
+        hpt_history_destroy(history);
         hpt_display_destroy(display);
         hpt_accum_destroy(accum);
     }
@@ -34,7 +38,7 @@ int hip_failed(const char *what, hipError_t e){ std::cerr << "[Error] " << what 
 
 int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                              int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,
-                             const std::string &rms_log){
+                             const std::string &rms_log, const FrameMotion *motion){
     MovedRun run;
     if(!moved_run(mode, run)){ std::cerr << "[Error] --frames: no scene moved to the device" << std::endl; return -1; }
     if(!run.scene){ std::cerr << "[Error] --frames renders on one device" << std::endl; return -1; }
@@ -46,14 +50,22 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     const int64_t n_local = hpt_local_pixels(W, H, &p);
     if(n_local < 0) return hpt_failed("tiling");
 
-    DeviceMem d_local, d_frame, d_mean, d_rgb8;      // released after L has waited for its stream
+    const bool reproject = motion && motion->reproject;
+    if(reproject && motion->guide_spp < 1){ std::cerr << "[Error] --guide-spp must be at least 1" << std::endl; return -1; }
+    DeviceMem d_local, d_frame, d_mean, d_rgb8, d_normal, d_position, d_coverage;      // released after L has waited for its stream
     Loop L;
     if(!d_frame.alloc(values * sizeof(float)) || !d_mean.alloc(values * sizeof(float)) || !d_rgb8.alloc(values) ||
        (!ppm && !d_local.alloc((size_t) n_local * 3 * sizeof(float)))){
         std::cerr << "[Error] --frames: out of device memory" << std::endl; return -1;
     }
     if(hipError_t e = hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking)) return hip_failed("stream", e);
-    if(hpt_accum_create(W, H, 0, &L.accum) != HPT_OK) return hpt_failed("hpt_accum_create");
+    if(reproject){
+        if(!d_normal.alloc(values * sizeof(float)) || !d_position.alloc(values * sizeof(float)) || !d_coverage.alloc(values / 3 * sizeof(float))){
+            std::cerr << "[Error] --reproject: out of device memory" << std::endl; return -1;
+        }
+        if(hpt_history_create(W, H, &L.history) != HPT_OK) return hpt_failed("hpt_history_create");
+    }
+    else if(hpt_accum_create(W, H, 0, &L.accum) != HPT_OK) return hpt_failed("hpt_accum_create");
     if(hpt_display_create(W, H, &L.display) != HPT_OK) return hpt_failed("hpt_display_create");
     if(!rms_log.empty()){
         L.log = fopen(rms_log.c_str(), "w");
@@ -61,29 +73,53 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     }
     std::vector<float> host_frame(ppm ? values : 0);
 
+    unsigned char cam_now[HPT_CAMERA_BYTES], cam_last[HPT_CAMERA_BYTES];
+    memcpy(cam_now, camera, sizeof cam_now);
     int done = 0;
     for(int f = 0; f < frames; ++f){
         p.sample_offset = run.params.sample_offset + f * frame_spp;
         int rc;
+        if(motion && motion->camera_at){ memcpy(cam_last, cam_now, sizeof cam_now); motion->camera_at(f, cam_now); }
+        const bool moved = motion && motion->camera_at && f > 0 && memcmp(cam_now, cam_last, sizeof cam_now) != 0;
+        const bool guides = reproject && (f == 0 || moved);
+        if(guides){      // blocking, on the scene's own stream: before this frame's render is enqueued, after the last frame's metrics
+            hpt_params g{};
+            g.seed = p.seed; g.sample_offset = p.sample_offset; g.max_delta = p.max_delta; g.tile = p.tile;
+            if(hpt_render_guides_device(run.scene, cam_now, W, H, motion->guide_spp, &g, nullptr, d_normal.p, d_position.p, d_coverage.p) != HPT_OK)
+                return hpt_failed("hpt_render_guides_device");
+        }
         if(ppm){
-            rc = hpt_render_ppm(run.scene, camera, W, H, eye_depth, light_depth, frame_spp, run.light_sample, radius, nullptr, nullptr,
+            rc = hpt_render_ppm(run.scene, cam_now, W, H, eye_depth, light_depth, frame_spp, run.light_sample, radius, nullptr, nullptr,
                                 &p, host_frame.data());
             if(rc != HPT_OK) return hpt_failed("hpt_render_ppm");
             if(hipError_t e = hipMemcpyAsync(d_frame.p, host_frame.data(), values * sizeof(float), hipMemcpyHostToDevice, L.stream))
                 return hip_failed("frame upload", e);
         } else {
-            rc = bdpt ? hpt_render_bdpt_device(run.scene, camera, W, H, eye_depth, light_depth, frame_spp, spl, &p, d_local.p, L.stream)
-                      : hpt_render_pt_device(run.scene, camera, W, H, eye_depth, frame_spp, &p, d_local.p, L.stream);
+            rc = bdpt ? hpt_render_bdpt_device(run.scene, cam_now, W, H, eye_depth, light_depth, frame_spp, spl, &p, d_local.p, L.stream)
+                      : hpt_render_pt_device(run.scene, cam_now, W, H, eye_depth, frame_spp, &p, d_local.p, L.stream);
             if(rc != HPT_OK) return hpt_failed("render");
             if(hpt_untile(d_local.p, d_frame.p, W, H, &p, L.stream) != HPT_OK) return hpt_failed("hpt_untile");
         }
-        if(hpt_accum_add(L.accum, d_frame.p, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_accum_add");
+        if(reproject){
+            if(hpt_history_advance(L.history, cam_now, d_frame.p, guides ? d_normal.p : nullptr, guides ? d_position.p : nullptr,
+                                   guides ? d_coverage.p : nullptr, nullptr, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_history_advance");
+        } else {
+            if(moved && hpt_accum_reset(L.accum, L.stream) != HPT_OK) return hpt_failed("hpt_accum_reset");
+            if(hpt_accum_add(L.accum, d_frame.p, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_accum_add");
+        }
         if(hpt_display_present(L.display, d_mean.p, nullptr, d_rgb8.p, 0, 0, 0, L.stream) != HPT_OK) return hpt_failed("hpt_display_present");
         double rms_prev = 0.0;
         if(hpt_display_metrics(L.display, &rms_prev, nullptr, nullptr, nullptr, nullptr) != HPT_OK) return hpt_failed("hpt_display_metrics");
         done = f + 1;
         if(L.log){ fprintf(L.log, "%d %.9g\n", done, rms_prev); fflush(L.log); }
-        std::cout << "[Frame " << done << "] rms " << rms_prev << std::endl;
+        if(reproject){
+            uint64_t kept = 0;
+            if(hpt_history_metrics(L.history, &kept, nullptr, nullptr) != HPT_OK) return hpt_failed("hpt_history_metrics");
+            char share[32];
+            snprintf(share, sizeof share, "%.1f", 100.0 * (double) kept / ((double) W * H));
+            std::cout << "[Frame " << done << "] rms " << rms_prev << " kept " << share << " %" << std::endl;
+        }
+        else std::cout << "[Frame " << done << "] rms " << rms_prev << std::endl;
         if(until_rms >= 0.0 && done >= 2 && rms_prev <= until_rms) break;
     }
     rgb8.resize(values);

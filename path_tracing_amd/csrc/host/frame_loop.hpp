@@ -4,6 +4,7 @@
 #pragma once
 #include "../../../include/hpt.h"
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -22,8 +23,21 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // frame >= 2 whose rms_prev <= until_rms (until_rms < 0: off).  `camera` is a CudaCamera; image (W*H*3 floats) receives
 // the final mean and rgb8 the last presented bytes (RGB, rows top to bottom).  Returns the number of frames rendered,
 // -1 after an error (reported on stderr).  (frame_loop.cpp, part of pt_cli only)
+//
+// With `motion` (--orbit, --reproject) frame f renders from motion->camera_at(f), when set, instead of `camera`; a frame
+// whose camera record differs from the frame's before is a moved frame.  Without reproject the accumulator is reset on
+// every moved frame, which is what the reference's GUI does (src/main.cpp:453-466).  With reproject the loop keeps an
+// hpt_history instead of the hpt_accum: frame 0 and every moved frame render guide_spp guide samples on the device
+// (hpt_render_guides_device, the frame's seed and sample offset) before the frame itself and hand them to
+// hpt_history_advance, the other frames advance without guides; the frame's line on stdout then ends in the share of
+// pixels that kept their history, "[Frame 7] rms 0.0123 kept 95.1 %".  A null `motion` is the loop as it always was.
+struct FrameMotion {
+    std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
+    bool reproject = false;
+    int guide_spp = 4;
+};
 int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                    int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,
-                   const std::string &rms_log);
+                   const std::string &rms_log, const FrameMotion *motion = nullptr);
 
 } // namespace hpt_host

@@ -14,6 +14,12 @@
 //                     f * S, accumulated and presented on the device; --rms-log FILE gets "<frame> <rms>" per frame (the
 //                     reference GUI's RMS history, src/main.cpp:502-530), --until-rms R stops after a frame >= 2 whose rms <= R.
 //                     The PNG holds the last presented bytes.  pt, bdpt and ppm on one device.
+//   --orbit DEG       with --frames: frame f renders from the scene's eye rotated by f * DEG degrees about the look-at point
+//                     around the up vector (rotation in double, rounded to float, then the usual camera).  By itself it does
+//                     what the reference's GUI does when the camera moves: the accumulation restarts on every moved frame.
+//   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
+//                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
+//                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
 // --mode pt, bdpt, ppm and sppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
 // reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
 // averaged, on one device; sppm the same passes into one progressive state whose radius shrinks per pixel.
@@ -23,7 +29,9 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -44,6 +52,8 @@ int main(int argc, char **argv){
     int frames = 0, frame_spp = 0;
     double until_rms = -1.0;
     std::string rms_log;
+    double orbit_deg = 0.0;
+    bool orbit = false, reproject = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -71,6 +81,8 @@ int main(int argc, char **argv){
         else if(arg == "--frame-spp" && i + 1 < argc) frame_spp = std::stoi(argv[++i]);
         else if(arg == "--until-rms" && i + 1 < argc) until_rms = std::stod(argv[++i]);
         else if(arg == "--rms-log" && i + 1 < argc) rms_log = argv[++i];
+        else if(arg == "--orbit" && i + 1 < argc){ orbit_deg = std::stod(argv[++i]); orbit = true; }
+        else if(arg == "--reproject") reproject = true;
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
@@ -95,7 +107,11 @@ int main(int argc, char **argv){
                       << "  --frames <int>    progressive: frames to accumulate and present on the device (pt, bdpt, ppm; one device)\n"
                       << "  --frame-spp <int> samples (ppm: passes) per frame (default: --spp)\n"
                       << "  --until-rms <float>  stop after a frame >= 2 whose RMS against the previous frame is <= this\n"
-                      << "  --rms-log <file>  one line \"<frame> <rms>\" per frame\n";
+                      << "  --rms-log <file>  one line \"<frame> <rms>\" per frame\n"
+                      << "  --orbit <deg>     with --frames: frame f renders from the eye rotated by f * deg degrees about the look-at point\n"
+                      << "                    around the up vector; the accumulation restarts on every moved frame\n"
+                      << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
+                      << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n";
             return 0;
         }
     }
@@ -109,6 +125,8 @@ int main(int argc, char **argv){
     std::cout << "====================================\n";
     if(mode != "pt" && mode != "bdpt" && mode != "ppm" && mode != "sppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm, sppm).\n"; return -1; }
     const bool progressive = frames != 0 || frame_spp != 0 || until_rms >= 0.0 || !rms_log.empty();
+    if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
+    if(orbit && !std::isfinite(orbit_deg)){ std::cerr << "[Error] --orbit needs a finite angle.\n"; return -1; }
     if(progressive){
         if(frames < 1){ std::cerr << "[Error] --frame-spp, --until-rms and --rms-log need --frames N (N >= 1).\n"; return -1; }
         if(mode == "sppm"){ std::cerr << "[Error] --frames does not apply to --mode sppm: it keeps its own progressive state (use --spp for its passes).\n"; return -1; }
@@ -150,8 +168,28 @@ int main(int argc, char **argv){
     auto start_time = std::chrono::steady_clock::now();
     std::vector<unsigned char> presented;
     if(progressive){
+        hpt_host::FrameMotion motion;
+        motion.reproject = reproject; motion.guide_spp = guide_spp;
+        if(orbit) motion.camera_at = [&](int f, void *camera84){
+            // Rodrigues' rotation of eye - look_at about the unit up vector, in double
+            const hpt_host::Camera &c = scene.camera;
+            const double e[3] = { c.eye.x, c.eye.y, c.eye.z }, l[3] = { c.look_at.x, c.look_at.y, c.look_at.z };
+            double k[3] = { c.view_up.x, c.view_up.y, c.view_up.z };
+            const double len = std::sqrt(k[0] * k[0] + k[1] * k[1] + k[2] * k[2]);
+            for(double &x : k) x /= len;
+            const double v[3] = { e[0] - l[0], e[1] - l[1], e[2] - l[2] };
+            const double t = (double) f * orbit_deg * 3.14159265358979323846 / 180.0, cs = std::cos(t), sn = std::sin(t);
+            const double kxv[3] = { k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0] };
+            const double kv = (k[0] * v[0] + k[1] * v[1] + k[2] * v[2]) * (1.0 - cs);
+            hpt_host::Camera moved = c;
+            moved.eye.x = (float) (l[0] + (v[0] * cs + kxv[0] * sn + k[0] * kv));
+            moved.eye.y = (float) (l[1] + (v[1] * cs + kxv[1] * sn + k[1] * kv));
+            moved.eye.z = (float) (l[2] + (v[2] * cs + kxv[2] * sn + k[2] * kv));
+            const CudaCamera cc = hpt_host::make_cuda_camera(moved, F, W, H);
+            memcpy(camera84, &cc, sizeof cc);
+        };
         const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
-                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log);
+                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject ? &motion : nullptr);
         if(n < 0) return -1;
         std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
     }

@@ -2,6 +2,7 @@
 // phases), its workspace and statistics, the one-shot render and the progressive state; and hpt_render_guides, which
 // runs the eye phase alone.
 #include "hpt_host.h"
+#include "history_kernels.h"
 
 #include <new>
 
@@ -260,10 +261,15 @@ int hpt_render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth
     return ppm_collect_stats(s, r, spp);
 }
 
+} // extern "C"
+
+namespace {
+
 // First-hit guide buffers (include/hpt.h): PPM's eye pass per sample, its hit points summed per pixel, the means
-// un-tiled into whichever host images the caller asks for.  Blocking, one device.
-int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
-                      float *albedo, float *normal, float *position, float *coverage){
+// un-tiled into whichever images the caller asks for -- host images (hpt_render_guides) or, with `device`, device
+// images (hpt_render_guides_device).  Blocking, one device.
+int render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
+                  float *albedo, float *normal, float *position, float *coverage, bool device){
     if(!s) return fail(HPT_ERR_INVALID, "null scene");
     if(!camera) return fail(HPT_ERR_INVALID, "null camera");
     if(spp < 1) return fail(HPT_ERR_INVALID, "spp must be >= 1");
@@ -307,6 +313,12 @@ int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, c
     for(int which = 0; which < 4; ++which){
         if(!outs[which]) continue;
         launch_guides_resolve(st, r.n_local, ga, which, s->ws.local_own.get());
+        if(device){      // the three-channel images straight into the caller's; coverage is the first channel of one
+            launch_untile(st, r.tl, s->ws.local_own.get(), which < 3 ? outs[which] : s->ws.image_own.get());
+            if(which == 3) launch_take_first_channel(st, s->ws.image_own.get(), coverage, (uint32_t) npx);
+            HIP_TRY(hipGetLastError());
+            continue;
+        }
         launch_untile(st, r.tl, s->ws.local_own.get(), s->ws.image_own.get());
         HIP_TRY(hipGetLastError());
         if(which < 3){
@@ -320,6 +332,20 @@ int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, c
     HIP_TRY(hipEventRecord(s->tm.ev_stop, st));
     HIP_TRY(hipEventSynchronize(s->tm.ev_stop));
     return ppm_collect_stats(s, r, spp);
+}
+
+} // namespace
+
+extern "C" {
+
+int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
+                      float *albedo, float *normal, float *position, float *coverage){
+    return render_guides(s, camera, W, H, spp, params, albedo, normal, position, coverage, false);
+}
+
+int hpt_render_guides_device(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
+                             void *d_albedo, void *d_normal, void *d_position, void *d_coverage){
+    return render_guides(s, camera, W, H, spp, params, (float *) d_albedo, (float *) d_normal, (float *) d_position, (float *) d_coverage, true);
 }
 
 int hpt_ppm_get_stats(const hpt_scene *s, hpt_ppm_stats *out){
