@@ -565,7 +565,8 @@ void hpt_display_destroy(hpt_display *d);
  * zeroes the current state on the stream and sets K = 0.  hpt_history_check runs every argument check of an advance on a
  * W x H history without a handle or a device (a front-end can validate before it allocates; tests).
  *
- * Limits.  History is colour only: no second moment, no variance-guided filtering.  The guide position is an average
+ * Limits.  History is colour only: no second moment (the variance-guided filter, below, estimates the variance of a moved
+ * frame spatially and divides by hpt_history_length's n).  The guide position is an average
  * over jittered samples, so pixels that straddle an edge mostly fail the direct-view or the plane test and restart.
  * There are no motion vectors: the scene is static in this library.  Once n reaches max_history the mean turns into an
  * exponential average with weight 1 / max_history for the new frame, which is what lets lighting seen from a new angle
@@ -589,6 +590,73 @@ void hpt_history_destroy(hpt_history *h);
 int  hpt_history_check(int W, int H, const void *camera, const void *d_frame_rgb,
                        const void *d_normal, const void *d_position, const void *d_coverage,
                        const hpt_history_params *p, const void *d_mean_out);
+
+/* ---- variance-guided filtering ------------------------------------------------------------------------
+ * hpt_denoiser_run uses one sigma_color for the whole image.  After a camera move under hpt_history converged pixels
+ * (tens of samples) and restarted ones (n = 1) sit side by side, and no single tolerance serves both.  The guided run
+ * takes a per-pixel variance of the image's values and lets it set each pixel's colour tolerance (the variance-guided
+ * a-trous of SVGF, Schied et al. 2017, without its temporal part, which hpt_accum and hpt_history are).  It runs on the
+ * same hpt_denoiser -- the same packed guides and the same two colour buffers, 80 bytes per pixel as before: the variance
+ * is one scalar per pixel and rides in the free fourth word of the colour records.
+ *
+ * Everything is IEEE float, evaluated as written, left to right; no transcendental, no sqrt, no atomic; the tap order is
+ * part of the definition.  valid(p), a(p), the taps h, the falloff e(x), inv_n, inv_p, the skip rules (outside the image,
+ * or invalid) and the rule that a pixel whose 24 other taps are all skipped keeps its value are the plain filter's
+ * ("The filter", above).
+ *
+ * hpt_denoiser_run_guided.  d_variance: W*H*3 floats, the per-channel variance of the image's values -- what
+ * hpt_accum_variance writes, or hpt_denoiser_estimate_variance.  d_variance_out: W*H floats, may be NULL.
+ *   pack      c_0 is the plain filter's.  v_0(p) = fmaxf(vr / (a.x * a.x) + vg / (a.y * a.y) + vb / (a.z * a.z), 0.0f) with
+ *             DEMODULATE on a valid pixel, else fmaxf(vr + vg + vb, 0.0f); a NaN sum gives 0.
+ *   level k   stride 2^k.  sigma_color is NOT halved per level: the variance shrinks from level to level and does the
+ *             narrowing.  s2 = sigma_color * sigma_color, computed on the host.  For a valid p:
+ *     prefilter     always at stride 1, g = {1/4, 1/2, 1/4}: num = 0, den = 0; for j = -1..1 (outer), i = -1..1 (inner),
+ *                   q = (x + i, y + j) skipped when outside the image or invalid: num = num + v_k(q) * (g[j+1] * g[i+1]),
+ *                   den = den + g[j+1] * g[i+1];  vbar = num / den (the centre is always there).
+ *     colour scale  inv_c = fminf(1.0f / (s2 * vbar + 1e-12f), FLT_MAX).
+ *     taps          the plain filter's 25, with xc = (dc.x dc.x + dc.y dc.y + dc.z dc.z) * inv_c and xn, xp, w as there:
+ *                   sum += c_k(q) * w per channel, vsum = vsum + v_k(q) * (w * w), wsum += w.
+ *     result        c_{k+1}(p) = sum / wsum, v_{k+1}(p) = vsum / (wsum * wsum).  A pixel whose 24 other taps are all skipped
+ *                   keeps both c and v, and so does an invalid pixel.
+ *   output    the colour as in the plain filter (re-modulated; an invalid pixel leaves with its input bits).
+ *             d_variance_out[p] = v_n(p), in the filter's WORKING SPACE: demodulated when DEMODULATE is set, never
+ *             multiplied back by the albedo, and a sum over the three channels.
+ * There is no sqrt: the colour term compares a squared difference with a variance, which keeps every operation one a CPU
+ * restatement rounds identically.  Zero variance means inv_c = 1e12, so only (almost) equal colours mix: a pixel that
+ * claims to be converged passes through.  A sigma_color < 0 switches the colour term off (the variance is still carried).
+ *
+ * hpt_denoiser_estimate_variance is SVGF's spatial fallback for frames whose temporal variance is unknown (a moved camera,
+ * or fewer than 4 frames).  d_frame_rgb is the SINGLE NEW FRAME, not the mean.  For a valid p, over the 7 x 7 window at
+ * stride 1, j = -3..3 (outer), i = -3..3 (inner), q skipped when outside the image or invalid; xn and xp are the filter's
+ * (a term switched off is 1.0f):  w = e(xn) * e(xp);  per channel s += c(q) * w, t += (c(q) * c(q)) * w;  ws += w.  Then
+ * m = s / ws, q2 = t / ws, var = fmaxf(q2 - m * m, 0.0f), and with d_length (W*H floats, a pixel's history length, may be
+ * NULL) var = var / fmaxf(len[p], 1.0f), which makes it the variance of the mean.  An invalid pixel gives 0.  Output
+ * W*H*3 floats.  Only sigma_normal, sigma_position and the flags' validity are read from p.  As hpt_accum_variance, this
+ * is good for Monte-Carlo noise and NOT a general-purpose variance (q2 and m * m are rounded floats of nearly equal size);
+ * the weighted estimate is biased low by the factor 1 - sum w^2 / (sum w)^2 (1/49 of the value at equal weights), and
+ * image detail inside the window that the guides do not see counts as noise.
+ *
+ * hpt_history_length writes the current history length n of every pixel (W*H floats), the image read's `length` returns.
+ * hpt_guided_check runs every argument check of a guided run on a W x H image without a handle or a device.
+ * All calls only enqueue on hip_stream.  HPT_ERR_INVALID with a message, before the device is touched: a null handle,
+ * image or variance; d_out overlapping either input; d_variance_out overlapping any other image; a run (or an estimate)
+ * before hpt_denoiser_set_guides; iterations outside [0, 8]; an unknown flag; a NaN sigma; hpt_history_length before the
+ * first advance.  With HPT_DENOISE_TIME hpt_denoiser_last_ms and hpt_denoiser_level_ms report the guided run. */
+typedef struct hpt_guided_params {
+    int32_t iterations;     /* 1..8; 0 -> 5 */
+    float sigma_color;      /* 0 -> 2.0 (in standard deviations of the pixel's own noise); < 0 -> colour term off */
+    float sigma_normal;     /* as hpt_denoise_params */
+    float sigma_position;   /* as hpt_denoise_params */
+    int32_t flags;          /* HPT_DENOISE_DEMODULATE, HPT_DENOISE_TIME; other bits: HPT_ERR_INVALID */
+} hpt_guided_params;
+int hpt_denoiser_run_guided(hpt_denoiser *d, const void *d_linear_rgb, const void *d_variance,
+                            void *d_out, void *d_variance_out,
+                            const hpt_guided_params *p, void *hip_stream);
+int hpt_denoiser_estimate_variance(hpt_denoiser *d, const void *d_frame_rgb, const void *d_length,
+                                   void *d_variance_out, const hpt_guided_params *p, void *hip_stream);
+int hpt_history_length(hpt_history *h, void *d_length_out, void *hip_stream);
+int hpt_guided_check(int W, int H, const void *d_linear_rgb, const void *d_variance, const void *d_out,
+                     const void *d_variance_out, const hpt_guided_params *p);
 
 /* ---- the acceleration structure, exported (tests) -------------------------------------
  * The reference has no acceleration structure (include/geometric.cuh:293-388 scan every primitive); the tree the

@@ -85,6 +85,13 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float), ("flags", C.c_int32)]
 
 
+class GuidedParams(C.Structure):
+    """hpt_guided_params (include/hpt.h): zeros select the defaults (5 levels, sigmas 2.0 / 0.5 / 0.05); sigma_color is in
+    standard deviations of the pixel's own noise and is not halved per level; a negative sigma switches its term off."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("flags", C.c_int32)]
+
+
 class HistoryParams(C.Structure):
     """hpt_history_params (include/hpt.h): zeros select the defaults (max_history 256, plane_tolerance 0.01, normal_min
     0.9); a negative tolerance or a normal_min below -1 switches its test off."""
@@ -98,6 +105,11 @@ def make_history_params(max_history=0.0, plane_tolerance=0.0, normal_min=0.0) ->
 def make_denoise_params(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_position=0.0, demodulate=True, time=False) -> DenoiseParams:
     return DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position),
                          (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TIME if time else 0))
+
+
+def make_guided_params(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_position=0.0, demodulate=True, time=False) -> GuidedParams:
+    return GuidedParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position),
+                        (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TIME if time else 0))
 
 
 class BvhInfo(C.Structure):
@@ -158,7 +170,8 @@ def load_library() -> C.CDLL:
                      "hpt_accum_create", "hpt_accum_add", "hpt_accum_mean", "hpt_accum_variance", "hpt_accum_reset", "hpt_accum_read",
                      "hpt_display_create", "hpt_display_present", "hpt_display_metrics", "hpt_display_reset",
                      "hpt_render_guides_device", "hpt_history_create", "hpt_history_advance", "hpt_history_metrics",
-                     "hpt_history_read", "hpt_history_reset", "hpt_history_check"):
+                     "hpt_history_read", "hpt_history_reset", "hpt_history_check",
+                     "hpt_denoiser_run_guided", "hpt_denoiser_estimate_variance", "hpt_history_length", "hpt_guided_check"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -427,6 +440,20 @@ class Denoiser:
         params = params or make_denoise_params()
         _check(self._lib.hpt_denoiser_run(self._h, _dptr(linear_rgb), _dptr(out), C.byref(params), C.c_void_p(stream)))
 
+    def run_guided(self, linear_rgb, variance, out, variance_out=None, params: GuidedParams | None = None, stream: int = 0):
+        """The variance-guided filter: `variance` is W*H*3 (Accumulator.variance or estimate_variance); variance_out, when
+        given, receives the filtered scalar variance (W*H, in the filter's working space)."""
+        params = params or make_guided_params()
+        _check(self._lib.hpt_denoiser_run_guided(self._h, _dptr(linear_rgb), _dptr(variance), _dptr(out),
+                                                 _dptr(variance_out) if variance_out is not None else None, C.byref(params), C.c_void_p(stream)))
+
+    def estimate_variance(self, frame, variance_out, length=None, params: GuidedParams | None = None, stream: int = 0):
+        """Spatial per-channel variance (W*H*3) of ONE new frame over 7 x 7 windows steered by the guides; with `length`
+        (W*H, History.length) divided by it: the variance of the mean."""
+        params = params or make_guided_params()
+        _check(self._lib.hpt_denoiser_estimate_variance(self._h, _dptr(frame), _dptr(length) if length is not None else None,
+                                                        _dptr(variance_out), C.byref(params), C.c_void_p(stream)))
+
     def last_ms(self) -> dict:
         """Times of the last run with DENOISE_TIME (waits for it): dict(pack, filter, levels [8])."""
         a, b = C.c_double(), C.c_double()
@@ -465,6 +492,14 @@ def denoise(image, guides, iterations=0, sigma_color=0, sigma_normal=0, sigma_po
     p = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_position, demodulate)
     _check(load_library().hpt_denoise_host(_vp(img), _vp(g[0]), _vp(g[1]), _vp(g[2]), _vp(g[3]), _vp(out), W, H, C.byref(p)))
     return out
+
+
+def guided_check(W, H, linear_rgb, variance, out, variance_out=None, params: GuidedParams | None = None) -> None:
+    """Every argument check of Denoiser.run_guided on a W x H image, without a denoiser or a device (hpt_guided_check);
+    raises HptError as the run would."""
+    opt = lambda x: _dptr(x) if x is not None else None
+    _check(load_library().hpt_guided_check(int(W), int(H), opt(linear_rgb), opt(variance), opt(out), opt(variance_out),
+                                           C.byref(params) if params is not None else None))
 
 
 class Accumulator:
@@ -603,6 +638,10 @@ class History:
         k = C.c_int64()
         _check(self._lib.hpt_history_read(self._h, _vp(m), _vp(n), C.byref(k)))
         return dict(mean=m, length=n, frames=int(k.value))
+
+    def length(self, out, stream: int = 0):
+        """The current history length n of every pixel into the DEVICE image `out` (W*H float32); enqueues only."""
+        _check(self._lib.hpt_history_length(self._h, _dptr(out), C.c_void_p(stream)))
 
     def reset(self, stream: int = 0):
         _check(self._lib.hpt_history_reset(self._h, C.c_void_p(stream)))

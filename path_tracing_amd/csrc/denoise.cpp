@@ -1,6 +1,9 @@
 // The denoiser's host side (include/hpt.h, hpt_denoiser_* and hpt_denoise_host): the object with its packed guides and
-// ping-pong colour buffers, the argument checks, the per-level constants and the optional HIP-event timing.
+// ping-pong colour buffers, the argument checks, the per-level constants and the optional HIP-event timing; and, on the
+// same object, the variance-guided filter and the spatial variance estimate (hpt_denoiser_run_guided,
+// hpt_denoiser_estimate_variance, hpt_guided_check).
 #include "hpt_host.h"
+#include "guided_kernels.h"
 
 #include <cfloat>
 #include <cmath>
@@ -9,6 +12,7 @@
 using namespace hpt;
 
 static_assert(sizeof(hpt_denoise_params) == 20, "ABI record: keep path_tracing_amd/__init__.py (DenoiseParams) in step");
+static_assert(sizeof(hpt_guided_params) == 20, "ABI record: keep path_tracing_amd/__init__.py (GuidedParams) in step");
 
 namespace {
 
@@ -60,6 +64,47 @@ float inv_sq(float s){ return fminf(1.0f / (s * s), FLT_MAX); }
 bool overlap(const void *a, const void *b, size_t bytes){
     const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
     return x < y + bytes && y < x + bytes;
+}
+bool overlap2(const void *a, size_t na, const void *b, size_t nb){
+    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+    return x < y + nb && y < x + na;
+}
+
+// *p (zeros for null) with the defaults filled in; `filter` false (the estimator) reads the flags and the two guide sigmas only
+int take_guided_params(const hpt_guided_params *p, hpt_guided_params &D, bool filter){
+    memset(&D, 0, sizeof D);
+    if(p) D = *p;
+    if(D.flags & ~kDenoiseFlags) return fail(HPT_ERR_INVALID, "hpt_guided_params.flags: HPT_DENOISE_DEMODULATE and HPT_DENOISE_TIME only");
+    if(filter){
+        if(D.iterations < 0 || D.iterations > kMaxLevels) return fail(HPT_ERR_INVALID, "hpt_guided_params.iterations must be in [0, 8]");
+        if(D.iterations == 0) D.iterations = 5;
+        if(D.sigma_color != D.sigma_color) return fail(HPT_ERR_INVALID, "hpt_guided_params: a sigma is NaN");
+        if(D.sigma_color == 0.0f) D.sigma_color = 2.0f;
+    }
+    if(D.sigma_normal != D.sigma_normal || D.sigma_position != D.sigma_position) return fail(HPT_ERR_INVALID, "hpt_guided_params: a sigma is NaN");
+    if(D.sigma_normal == 0.0f) D.sigma_normal = 0.5f;
+    if(D.sigma_position == 0.0f) D.sigma_position = 0.05f;
+    return HPT_OK;
+}
+
+int check_image_size(int W, int H){
+    if(W <= 0 || H <= 0) return fail(HPT_ERR_INVALID, "image size must be positive");
+    if((long long) W * H > (1ll << 28)) return fail(HPT_ERR_INVALID, "image too large for the denoiser (at most 2^28 pixels)");
+    return HPT_OK;
+}
+
+// every check of a guided run that needs no handle; fills the resolved parameters
+int check_guided(int W, int H, const void *rgb, const void *variance, const void *out, const void *variance_out,
+                 const hpt_guided_params *p, hpt_guided_params &D){
+    if(int rc = check_image_size(W, H)) return rc;
+    if(!rgb || !out) return fail(HPT_ERR_INVALID, "null image");
+    if(!variance) return fail(HPT_ERR_INVALID, "null variance image");
+    const size_t npx = (size_t) W * H, b3 = npx * 3 * sizeof(float), b1 = npx * sizeof(float);
+    if(overlap2(out, b3, rgb, b3) || overlap2(out, b3, variance, b3))
+        return fail(HPT_ERR_INVALID, "hpt_denoiser_run_guided: d_out must not overlap d_linear_rgb or d_variance");
+    if(variance_out && (overlap2(variance_out, b1, rgb, b3) || overlap2(variance_out, b1, variance, b3) || overlap2(variance_out, b1, out, b3)))
+        return fail(HPT_ERR_INVALID, "hpt_denoiser_run_guided: d_variance_out must not overlap another image");
+    return take_guided_params(p, D, true);
 }
 
 } // namespace
@@ -131,9 +176,71 @@ int hpt_denoiser_run(hpt_denoiser *d, const void *d_linear_rgb, void *d_out, con
     return HPT_OK;
 }
 
+int hpt_guided_check(int W, int H, const void *d_linear_rgb, const void *d_variance, const void *d_out, const void *d_variance_out,
+                     const hpt_guided_params *p){
+    hpt_guided_params D;
+    return check_guided(W, H, d_linear_rgb, d_variance, d_out, d_variance_out, p, D);
+}
+
+int hpt_denoiser_run_guided(hpt_denoiser *d, const void *d_linear_rgb, const void *d_variance, void *d_out, void *d_variance_out,
+                            const hpt_guided_params *p, void *hip_stream){
+    if(!d) return fail(HPT_ERR_INVALID, "null denoiser");
+    hpt_guided_params D;
+    if(int rc = check_guided(d->W, d->H, d_linear_rgb, d_variance, d_out, d_variance_out, p, D)) return rc;
+    if(!d->guides_set) return fail(HPT_ERR_INVALID, "hpt_denoiser_run_guided before hpt_denoiser_set_guides");
+    if(int rc = on_denoiser_device(d)) return rc;
+    hipStream_t st = (hipStream_t) hip_stream;
+    const bool timed = (D.flags & HPT_DENOISE_TIME) != 0;
+    const int demod = (D.flags & HPT_DENOISE_DEMODULATE) ? 1 : 0;
+    d->timed_levels = 0;
+    if(timed) for(int k = 0; k < D.iterations + 2; ++k) if(!d->ev[k]) HIP_TRY(hipEventCreate(&d->ev[k]));
+
+    if(timed) HIP_TRY(hipEventRecord(d->ev[0], st));
+    launch_guided_pack(st, (const float *) d_linear_rgb, (const float *) d_variance, d->g, d->ping[0].get(), d->npx, demod);
+    if(timed) HIP_TRY(hipEventRecord(d->ev[1], st));
+    GuidedLevel L{};
+    L.W = d->W; L.H = d->H; L.demod = demod;
+    L.use_c = D.sigma_color > 0.0f; L.use_n = D.sigma_normal > 0.0f; L.use_p = D.sigma_position > 0.0f;
+    L.s2 = L.use_c ? D.sigma_color * D.sigma_color : 0.0f;      // not halved per level: the shrinking variance narrows it
+    L.inv_n = L.use_n ? inv_sq(D.sigma_normal) : 0.0f;
+    L.inv_p = L.use_p ? inv_sq(D.sigma_position) : 0.0f;
+    for(int k = 0; k < D.iterations; ++k){
+        L.stride = 1 << k;
+        const int last = k + 1 == D.iterations;
+        launch_atrous_guided(st, L, d->g, d->ping[k & 1].get(), d->ping[(k + 1) & 1].get(), (float *) d_out, (float *) d_variance_out, last);
+        if(timed) HIP_TRY(hipEventRecord(d->ev[k + 2], st));
+    }
+    HIP_TRY(hipGetLastError());
+    if(timed) d->timed_levels = D.iterations;
+    return HPT_OK;
+}
+
+int hpt_denoiser_estimate_variance(hpt_denoiser *d, const void *d_frame_rgb, const void *d_length, void *d_variance_out,
+                                   const hpt_guided_params *p, void *hip_stream){
+    if(!d) return fail(HPT_ERR_INVALID, "null denoiser");
+    if(!d_frame_rgb) return fail(HPT_ERR_INVALID, "null frame");
+    if(!d_variance_out) return fail(HPT_ERR_INVALID, "null variance image");
+    const size_t b3 = d->npx * 3 * sizeof(float), b1 = d->npx * sizeof(float);
+    if(overlap2(d_variance_out, b3, d_frame_rgb, b3) || (d_length && overlap2(d_variance_out, b3, d_length, b1)))
+        return fail(HPT_ERR_INVALID, "hpt_denoiser_estimate_variance: d_variance_out must not overlap d_frame_rgb or d_length");
+    hpt_guided_params D;
+    if(int rc = take_guided_params(p, D, false)) return rc;
+    if(!d->guides_set) return fail(HPT_ERR_INVALID, "hpt_denoiser_estimate_variance before hpt_denoiser_set_guides");
+    if(int rc = on_denoiser_device(d)) return rc;
+    VarianceArgs A{};
+    A.W = d->W; A.H = d->H;
+    A.use_n = D.sigma_normal > 0.0f; A.use_p = D.sigma_position > 0.0f;
+    A.inv_n = A.use_n ? inv_sq(D.sigma_normal) : 0.0f;
+    A.inv_p = A.use_p ? inv_sq(D.sigma_position) : 0.0f;
+    A.frame = (const float *) d_frame_rgb; A.length = (const float *) d_length; A.out = (float *) d_variance_out;
+    launch_variance_spatial((hipStream_t) hip_stream, A, d->g);
+    HIP_TRY(hipGetLastError());
+    return HPT_OK;
+}
+
 int hpt_denoiser_level_ms(const hpt_denoiser *d, double *ms_levels, int cap){
     if(!d || !ms_levels || cap < 0) return fail(HPT_ERR_INVALID, "null argument");
-    if(d->timed_levels == 0) return fail(HPT_ERR_INVALID, "the last hpt_denoiser_run was not timed (HPT_DENOISE_TIME)");
+    if(d->timed_levels == 0) return fail(HPT_ERR_INVALID, "the last hpt_denoiser_run or hpt_denoiser_run_guided was not timed (HPT_DENOISE_TIME)");
     if(int rc = on_denoiser_device(d)) return rc;
     HIP_TRY(hipEventSynchronize(d->ev[d->timed_levels + 1]));
     for(int k = 0; k < cap; ++k){
@@ -146,7 +253,7 @@ int hpt_denoiser_level_ms(const hpt_denoiser *d, double *ms_levels, int cap){
 
 int hpt_denoiser_last_ms(const hpt_denoiser *d, double *ms_pack, double *ms_filter){
     if(!d) return fail(HPT_ERR_INVALID, "null denoiser");
-    if(d->timed_levels == 0) return fail(HPT_ERR_INVALID, "the last hpt_denoiser_run was not timed (HPT_DENOISE_TIME)");
+    if(d->timed_levels == 0) return fail(HPT_ERR_INVALID, "the last hpt_denoiser_run or hpt_denoiser_run_guided was not timed (HPT_DENOISE_TIME)");
     if(int rc = on_denoiser_device(d)) return rc;
     HIP_TRY(hipEventSynchronize(d->ev[d->timed_levels + 1]));
     float a = 0.0f, b = 0.0f;

@@ -3,6 +3,7 @@
 // constants the kernel reads, and the argument checks, all made before anything touches the device.
 #include "hpt_host.h"
 #include "history_kernels.h"
+#include "guided_kernels.h"
 
 #include <cmath>
 #include <new>
@@ -208,6 +209,16 @@ int hpt_history_read(hpt_history *h, float *mean, float *length, int64_t *frames
         }
     }
     if(frames) *frames = h->frames;
+    return HPT_OK;
+}
+
+int hpt_history_length(hpt_history *h, void *d_length_out, void *hip_stream){
+    if(!h) return fail(HPT_ERR_INVALID, "null history");
+    if(!d_length_out) return fail(HPT_ERR_INVALID, "null length image");
+    if(h->frames < 1) return fail(HPT_ERR_INVALID, "hpt_history_length before the first hpt_history_advance");
+    if(int rc = on_device(h->device)) return rc;
+    launch_take_fourth_word((hipStream_t) hip_stream, h->mean_n[h->cur].get(), (float *) d_length_out, h->npx);
+    HIP_TRY(hipGetLastError());
     return HPT_OK;
 }
 

@@ -1,5 +1,5 @@
-// pt_cli --frames (frame_loop.hpp): render, untile, accumulate (or, with --reproject, advance the history) and present every
-// frame on one stream, read the sums back.
+// pt_cli --frames (frame_loop.hpp): render, untile, accumulate (or, with --reproject, advance the history), with --guided
+// filter the mean under its variance, and present every frame on one stream, read the sums back.
 #include "frame_loop.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -20,11 +20,13 @@ struct Loop {
     hpt_accum *accum = nullptr;
     hpt_display *display = nullptr;
     hpt_history *history = nullptr;
+    hpt_denoiser *denoiser = nullptr;
     hipStream_t stream = nullptr;
     FILE *log = nullptr;
     ~Loop(){
         if(log) fclose(log);
         if(stream){ (void) hipStreamSynchronize(stream); (void) hipStreamDestroy(stream); }
+        hpt_denoiser_destroy(denoiser);
         hpt_history_destroy(history);
         hpt_display_destroy(display);
         hpt_accum_destroy(accum);
@@ -51,27 +53,42 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     if(n_local < 0) return hpt_failed("tiling");
 
     const bool reproject = motion && motion->reproject;
-    if(reproject && motion->guide_spp < 1){ std::cerr << "[Error] --guide-spp must be at least 1" << std::endl; return -1; }
+    const bool guided = motion && motion->guided;
+    if((reproject || guided) && motion->guide_spp < 1){ std::cerr << "[Error] --guide-spp must be at least 1" << std::endl; return -1; }
     DeviceMem d_local, d_frame, d_mean, d_rgb8, d_normal, d_position, d_coverage;      // released after L has waited for its stream
+    DeviceMem d_albedo, d_variance, d_length, d_filtered;                              // --guided
     Loop L;
     if(!d_frame.alloc(values * sizeof(float)) || !d_mean.alloc(values * sizeof(float)) || !d_rgb8.alloc(values) ||
        (!ppm && !d_local.alloc((size_t) n_local * 3 * sizeof(float)))){
         std::cerr << "[Error] --frames: out of device memory" << std::endl; return -1;
     }
     if(hipError_t e = hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking)) return hip_failed("stream", e);
-    if(reproject){
+    if(reproject || guided){
         if(!d_normal.alloc(values * sizeof(float)) || !d_position.alloc(values * sizeof(float)) || !d_coverage.alloc(values / 3 * sizeof(float))){
-            std::cerr << "[Error] --reproject: out of device memory" << std::endl; return -1;
+            std::cerr << "[Error] --reproject, --guided: out of device memory" << std::endl; return -1;
         }
+    }
+    if(guided){
+        if(!d_albedo.alloc(values * sizeof(float)) || !d_variance.alloc(values * sizeof(float)) || !d_length.alloc(values / 3 * sizeof(float)) ||
+           !d_filtered.alloc(values * sizeof(float))){
+            std::cerr << "[Error] --guided: out of device memory" << std::endl; return -1;
+        }
+        if(hpt_denoiser_create(W, H, &L.denoiser) != HPT_OK) return hpt_failed("hpt_denoiser_create");
+    }
+    if(reproject){
         if(hpt_history_create(W, H, &L.history) != HPT_OK) return hpt_failed("hpt_history_create");
     }
-    else if(hpt_accum_create(W, H, 0, &L.accum) != HPT_OK) return hpt_failed("hpt_accum_create");
+    else if(hpt_accum_create(W, H, guided ? HPT_ACCUM_MOMENTS : 0, &L.accum) != HPT_OK) return hpt_failed("hpt_accum_create");
     if(hpt_display_create(W, H, &L.display) != HPT_OK) return hpt_failed("hpt_display_create");
     if(!rms_log.empty()){
         L.log = fopen(rms_log.c_str(), "w");
         if(!L.log){ std::cerr << "[Error] cannot open " << rms_log << std::endl; return -1; }
     }
     std::vector<float> host_frame(ppm ? values : 0);
+    std::vector<float> host_length[3];              // --guided without --reproject: the frame count K = 1, 2, 3 as a length image
+    if(guided && !reproject) for(int k = 0; k < 3; ++k) host_length[k].assign(values / 3, (float) (k + 1));
+    hpt_guided_params gp{};
+    gp.flags = HPT_DENOISE_DEMODULATE;
 
     unsigned char cam_now[HPT_CAMERA_BYTES], cam_last[HPT_CAMERA_BYTES];
     memcpy(cam_now, camera, sizeof cam_now);
@@ -81,12 +98,14 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         int rc;
         if(motion && motion->camera_at){ memcpy(cam_last, cam_now, sizeof cam_now); motion->camera_at(f, cam_now); }
         const bool moved = motion && motion->camera_at && f > 0 && memcmp(cam_now, cam_last, sizeof cam_now) != 0;
-        const bool guides = reproject && (f == 0 || moved);
+        const bool guides = (reproject || guided) && (f == 0 || moved);
         if(guides){      // blocking, on the scene's own stream: before this frame's render is enqueued, after the last frame's metrics
             hpt_params g{};
             g.seed = p.seed; g.sample_offset = p.sample_offset; g.max_delta = p.max_delta; g.tile = p.tile;
-            if(hpt_render_guides_device(run.scene, cam_now, W, H, motion->guide_spp, &g, nullptr, d_normal.p, d_position.p, d_coverage.p) != HPT_OK)
+            if(hpt_render_guides_device(run.scene, cam_now, W, H, motion->guide_spp, &g, d_albedo.p, d_normal.p, d_position.p, d_coverage.p) != HPT_OK)
                 return hpt_failed("hpt_render_guides_device");
+            if(guided && hpt_denoiser_set_guides(L.denoiser, d_albedo.p, d_normal.p, d_position.p, d_coverage.p, L.stream) != HPT_OK)
+                return hpt_failed("hpt_denoiser_set_guides");
         }
         if(ppm){
             rc = hpt_render_ppm(run.scene, cam_now, W, H, eye_depth, light_depth, frame_spp, run.light_sample, radius, nullptr, nullptr,
@@ -103,11 +122,30 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         if(reproject){
             if(hpt_history_advance(L.history, cam_now, d_frame.p, guides ? d_normal.p : nullptr, guides ? d_position.p : nullptr,
                                    guides ? d_coverage.p : nullptr, nullptr, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_history_advance");
+            if(guided && hpt_history_length(L.history, d_length.p, L.stream) != HPT_OK) return hpt_failed("hpt_history_length");
         } else {
             if(moved && hpt_accum_reset(L.accum, L.stream) != HPT_OK) return hpt_failed("hpt_accum_reset");
             if(hpt_accum_add(L.accum, d_frame.p, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_accum_add");
         }
-        if(hpt_display_present(L.display, d_mean.p, nullptr, d_rgb8.p, 0, 0, 0, L.stream) != HPT_OK) return hpt_failed("hpt_display_present");
+        if(guided){
+            // the variance of the mean: the accumulator's own from four frames on; before that, and under --reproject, the
+            // spatial estimate of this frame divided by the frame count or by each pixel's history length
+            const int64_t K = reproject ? 0 : hpt_accum_count(L.accum);
+            if(!reproject && K >= 4){
+                if(hpt_accum_variance(L.accum, d_variance.p, L.stream) != HPT_OK) return hpt_failed("hpt_accum_variance");
+            } else {
+                if(!reproject){
+                    if(hipError_t e = hipMemcpyAsync(d_length.p, host_length[K - 1].data(), values / 3 * sizeof(float), hipMemcpyHostToDevice, L.stream))
+                        return hip_failed("length upload", e);
+                }
+                if(hpt_denoiser_estimate_variance(L.denoiser, d_frame.p, d_length.p, d_variance.p, &gp, L.stream) != HPT_OK)
+                    return hpt_failed("hpt_denoiser_estimate_variance");
+            }
+            if(hpt_denoiser_run_guided(L.denoiser, d_mean.p, d_variance.p, d_filtered.p, nullptr, &gp, L.stream) != HPT_OK)
+                return hpt_failed("hpt_denoiser_run_guided");
+        }
+        void *shown = guided ? d_filtered.p : d_mean.p;
+        if(hpt_display_present(L.display, shown, nullptr, d_rgb8.p, 0, 0, 0, L.stream) != HPT_OK) return hpt_failed("hpt_display_present");
         double rms_prev = 0.0;
         if(hpt_display_metrics(L.display, &rms_prev, nullptr, nullptr, nullptr, nullptr) != HPT_OK) return hpt_failed("hpt_display_metrics");
         done = f + 1;
@@ -124,7 +162,7 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     }
     rgb8.resize(values);
     hipError_t e = hipStreamSynchronize(L.stream);
-    if(e == hipSuccess) e = hipMemcpy(image, d_mean.p, values * sizeof(float), hipMemcpyDeviceToHost);
+    if(e == hipSuccess) e = hipMemcpy(image, guided ? d_filtered.p : d_mean.p, values * sizeof(float), hipMemcpyDeviceToHost);
     if(e == hipSuccess) e = hipMemcpy(rgb8.data(), d_rgb8.p, values, hipMemcpyDeviceToHost);
     if(e != hipSuccess) return hip_failed("download", e);
     return done;

@@ -31,10 +31,18 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // (hpt_render_guides_device, the frame's seed and sample offset) before the frame itself and hand them to
 // hpt_history_advance, the other frames advance without guides; the frame's line on stdout then ends in the share of
 // pixels that kept their history, "[Frame 7] rms 0.0123 kept 95.1 %".  A null `motion` is the loop as it always was.
+//
+// With `guided` every frame presents (and `image` receives) the variance-guided filter of the mean instead of the mean
+// (hpt_denoiser_run_guided, defaults, demodulated) on a denoiser that lives with the loop.  Guides, now with albedo, are
+// rendered on frame 0 and on every moved frame as under reproject.  The variance of the mean: without reproject the
+// accumulator keeps moments and from its fourth frame on hpt_accum_variance is used, before that
+// hpt_denoiser_estimate_variance of the frame with a length image filled with the frame count; with reproject the
+// estimate of the frame with hpt_history_length.  Without `guided` the loop, its launches and its output are unchanged.
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
     bool reproject = false;
     int guide_spp = 4;
+    bool guided = false;
 };
 int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                    int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,

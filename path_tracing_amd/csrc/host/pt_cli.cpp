@@ -20,6 +20,10 @@
 //   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
 //                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
 //                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
+//   --guided          with --frames: present the variance-guided filter of the accumulated mean (hpt_denoiser_run_guided)
+//                     instead of the mean: guides with albedo on frame 0 and every moved frame (--guide-spp >= 1), the
+//                     variance from the accumulator's moments or, in the first frames and under --reproject, from the
+//                     spatial estimate of the new frame divided by the history length.
 // --mode pt, bdpt, ppm and sppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
 // reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
 // averaged, on one device; sppm the same passes into one progressive state whose radius shrinks per pixel.
@@ -53,7 +57,7 @@ int main(int argc, char **argv){
     double until_rms = -1.0;
     std::string rms_log;
     double orbit_deg = 0.0;
-    bool orbit = false, reproject = false;
+    bool orbit = false, reproject = false, guided = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -83,6 +87,7 @@ int main(int argc, char **argv){
         else if(arg == "--rms-log" && i + 1 < argc) rms_log = argv[++i];
         else if(arg == "--orbit" && i + 1 < argc){ orbit_deg = std::stod(argv[++i]); orbit = true; }
         else if(arg == "--reproject") reproject = true;
+        else if(arg == "--guided") guided = true;
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
@@ -111,7 +116,8 @@ int main(int argc, char **argv){
                       << "  --orbit <deg>     with --frames: frame f renders from the eye rotated by f * deg degrees about the look-at point\n"
                       << "                    around the up vector; the accumulation restarts on every moved frame\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
-                      << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n";
+                      << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
+                      << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n";
             return 0;
         }
     }
@@ -126,6 +132,8 @@ int main(int argc, char **argv){
     if(mode != "pt" && mode != "bdpt" && mode != "ppm" && mode != "sppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm, sppm).\n"; return -1; }
     const bool progressive = frames != 0 || frame_spp != 0 || until_rms >= 0.0 || !rms_log.empty();
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
+    if(guided && frames < 1){ std::cerr << "[Error] --guided needs --frames N (N >= 1).\n"; return -1; }
+    if(guided && guide_spp < 1){ std::cerr << "[Error] --frames --guided needs --guide-spp of at least 1.\n"; return -1; }
     if(orbit && !std::isfinite(orbit_deg)){ std::cerr << "[Error] --orbit needs a finite angle.\n"; return -1; }
     if(progressive){
         if(frames < 1){ std::cerr << "[Error] --frame-spp, --until-rms and --rms-log need --frames N (N >= 1).\n"; return -1; }
@@ -169,7 +177,7 @@ int main(int argc, char **argv){
     std::vector<unsigned char> presented;
     if(progressive){
         hpt_host::FrameMotion motion;
-        motion.reproject = reproject; motion.guide_spp = guide_spp;
+        motion.reproject = reproject; motion.guide_spp = guide_spp; motion.guided = guided;
         if(orbit) motion.camera_at = [&](int f, void *camera84){
             // Rodrigues' rotation of eye - look_at about the unit up vector, in double
             const hpt_host::Camera &c = scene.camera;
@@ -189,7 +197,7 @@ int main(int argc, char **argv){
             memcpy(camera84, &cc, sizeof cc);
         };
         const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
-                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject ? &motion : nullptr);
+                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject || guided ? &motion : nullptr);
         if(n < 0) return -1;
         std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
     }
