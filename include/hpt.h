@@ -508,7 +508,7 @@ void hpt_display_destroy(hpt_display *d);
  * Conventions as for hpt_accum / hpt_display: images are device pointers in the layouts hpt_untile and
  * hpt_render_guides write (frame, normal, position, mean: W*H*3 floats; coverage: W*H; row-major, row 0 = top);
  * advance and reset only enqueue on hip_stream; metrics and read wait for the device; create allocates on the current
- * device (96 bytes per pixel).  Every refusal is made, with a message, before anything touches the device.
+ * device (96 bytes per pixel, 128 with HPT_HISTORY_MOMENTS).  Every refusal is made, with a message, before anything touches the device.
  *
  * State per pixel: mean (3 floats), history length n (float), and the last frame's guide position, normal and coverage,
  * held in two sets (a pixel reads its neighbours' previous state, so a moved frame writes the other set).  The object
@@ -565,8 +565,9 @@ void hpt_display_destroy(hpt_display *d);
  * zeroes the current state on the stream and sets K = 0.  hpt_history_check runs every argument check of an advance on a
  * W x H history without a handle or a device (a front-end can validate before it allocates; tests).
  *
- * Limits.  History is colour only: no second moment (the variance-guided filter, below, estimates the variance of a moved
- * frame spatially and divides by hpt_history_length's n).  The guide position is an average
+ * Limits.  A history from hpt_history_create is colour only; hpt_history_create_flags with HPT_HISTORY_MOMENTS adds the
+ * second moment ("temporal variance", below).  Without it the variance-guided filter estimates the variance of every
+ * frame spatially and divides by hpt_history_length's n.  The guide position is an average
  * over jittered samples, so pixels that straddle an edge mostly fail the direct-view or the plane test and restart.
  * There are no motion vectors: the scene is static in this library.  Once n reaches max_history the mean turns into an
  * exponential average with weight 1 / max_history for the new frame, which is what lets lighting seen from a new angle
@@ -591,11 +592,58 @@ int  hpt_history_check(int W, int H, const void *camera, const void *d_frame_rgb
                        const void *d_normal, const void *d_position, const void *d_coverage,
                        const hpt_history_params *p, const void *d_mean_out);
 
+/* ---- temporal variance ----------------------------------------------------------------------------------
+ * The spatial estimate (hpt_denoiser_estimate_variance, below) looks at the newest frame alone.  A path tracer's noise is
+ * not stationary: bright samples are rare, and a pixel whose mean still carries the remnant of one sits in a window where
+ * the newest frame has none.  Its estimated variance is small, its colour tolerance tight, and the remnant passes the
+ * filter as a speckle.  A history that also carries the running mean of the SQUARED frame values knows each pixel's own
+ * variance over time (SVGF's temporal half, Schied et al. 2017).
+ *
+ * hpt_history_create_flags(W, H, flags, out).  flags = 0 is hpt_history_create; any bit but HPT_HISTORY_MOMENTS returns
+ * HPT_ERR_INVALID.  With HPT_HISTORY_MOMENTS each of the two sets holds a fourth 16-byte record per pixel, q.rgb | 0, zeroed
+ * by create and by hpt_history_reset like the others: 128 bytes per pixel instead of 96.
+ *
+ * hpt_history_advance on such a history computes mean, n, kept, restarted and the stored guides exactly as above -- the
+ * same bits as a history without the flag -- and carries q through the same steps, per channel, IEEE float, evaluated as
+ * written:
+ *   2. (unmoved camera)  q_r = q[p].
+ *   4. (taps)            qsum = (0, 0, 0) beside sum; a tap that is taken also gives qsum = qsum + q_prev[tap] * w, with the
+ *                        same four taps, the same skips, the same w and the same order.  Where m is taken
+ *                        (wsum > 0.01f): q_r = qsum / wsum.
+ *   5.                   n_r > 0 is false: q = c * c.  Otherwise q = (q_r * n_c + c * c) / (n_c + 1.0f) with the n_c of
+ *                        the mean.  (NULL guides on a first or moved frame have n_r = 0, so q = c * c.)
+ *
+ * hpt_history_variance(h, d_fallback, min_length, d_variance_out, stream): one launch, a map over pixels, enqueues only.
+ * L = min_length == 0 ? 4 : min_length; L < 2 or NaN returns HPT_ERR_INVALID, so n - 1 >= 1 wherever the moments are used.
+ * For pixel p with the current m, q, n:
+ *   n >= L     per channel d = q - m * m; out = fmaxf(d, 0.0f) / (n - 1.0f).  A NaN d (inf - inf) gives 0.
+ *   otherwise  out = d_fallback[p] per channel (W*H*3 floats); 0 when d_fallback is NULL.
+ * d_fallback may be d_variance_out itself -- the spatial estimate is patched where the history knows better -- any other
+ * overlap of the two is refused.  The result is the variance of the MEAN, in the layout hpt_denoiser_run_guided takes.
+ *
+ * Caveats.  As hpt_accum_variance, this is good for Monte-Carlo noise and NOT a general-purpose variance: q and m * m are
+ * rounded floats of nearly equal size, so below a relative variance of about 1e-7 their difference is rounding, not
+ * signal.  Past max_history the weights are exponential, not equal, so (q - m * m) / (n - 1) is an approximation of the
+ * mean's variance.  After a move q_r - m_r * m_r also contains the spread between the taps' means (the four taps are
+ * mixed as if they were one population), which errs on the high side: a pixel is filtered a little more, never less.
+ *
+ * hpt_history_read_moments copies the current q (W*H*3 floats) to the host and waits for the device (for tests).
+ * hpt_history_variance_check runs every argument check of hpt_history_variance on a W x H history created with
+ * create_flags, without a handle or a device.  HPT_ERR_INVALID with a message, before anything touches the device: a null
+ * handle or output; a history created without HPT_HISTORY_MOMENTS (variance, read_moments); a call before the first
+ * advance or after a reset (variance); a bad min_length; a partial overlap; another current device than the history's. */
+#define HPT_HISTORY_MOMENTS 1        /* also carry the per-channel running mean of the squared frame values */
+int  hpt_history_create_flags(int W, int H, int32_t flags, hpt_history **out);
+int  hpt_history_variance(hpt_history *h, const void *d_fallback, float min_length, void *d_variance_out, void *hip_stream);
+int  hpt_history_read_moments(hpt_history *h, float *q);
+int  hpt_history_variance_check(int W, int H, int32_t create_flags, const void *d_fallback, float min_length,
+                                const void *d_variance_out);
+
 /* ---- variance-guided filtering ------------------------------------------------------------------------
  * hpt_denoiser_run uses one sigma_color for the whole image.  After a camera move under hpt_history converged pixels
  * (tens of samples) and restarted ones (n = 1) sit side by side, and no single tolerance serves both.  The guided run
  * takes a per-pixel variance of the image's values and lets it set each pixel's colour tolerance (the variance-guided
- * a-trous of SVGF, Schied et al. 2017, without its temporal part, which hpt_accum and hpt_history are).  It runs on the
+ * a-trous of SVGF, Schied et al. 2017; its temporal part is hpt_accum, hpt_history and hpt_history_variance).  It runs on the
  * same hpt_denoiser -- the same packed guides and the same two colour buffers, 80 bytes per pixel as before: the variance
  * is one scalar per pixel and rides in the free fourth word of the colour records.
  *

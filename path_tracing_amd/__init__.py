@@ -34,6 +34,7 @@ DENOISE_TIME = 2
 ACCUM_MOMENTS = 1
 DISPLAY_BGR = 1
 DISPLAY_FLIP_Y = 2
+HISTORY_MOMENTS = 1
 
 
 class HptError(RuntimeError):
@@ -171,7 +172,8 @@ def load_library() -> C.CDLL:
                      "hpt_display_create", "hpt_display_present", "hpt_display_metrics", "hpt_display_reset",
                      "hpt_render_guides_device", "hpt_history_create", "hpt_history_advance", "hpt_history_metrics",
                      "hpt_history_read", "hpt_history_reset", "hpt_history_check",
-                     "hpt_denoiser_run_guided", "hpt_denoiser_estimate_variance", "hpt_history_length", "hpt_guided_check"):
+                     "hpt_denoiser_run_guided", "hpt_denoiser_estimate_variance", "hpt_history_length", "hpt_guided_check",
+                     "hpt_history_create_flags", "hpt_history_variance", "hpt_history_read_moments", "hpt_history_variance_check"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -502,6 +504,14 @@ def guided_check(W, H, linear_rgb, variance, out, variance_out=None, params: Gui
                                            C.byref(params) if params is not None else None))
 
 
+def history_variance_check(W, H, out, fallback=None, min_length=0.0, moments=True) -> None:
+    """Every argument check of History.variance on a W x H history, without a history or a device
+    (hpt_history_variance_check); raises HptError as the call would."""
+    opt = lambda x: _dptr(x) if x is not None else None
+    _check(load_library().hpt_history_variance_check(int(W), int(H), C.c_int32(HISTORY_MOMENTS if moments else 0), opt(fallback),
+                                                     C.c_float(min_length), opt(out)))
+
+
 class Accumulator:
     """Running sum over frames on the device (include/hpt.h, hpt_accum_*) for W x H images: float32 adds in frame order,
     with moments=True also the sum of squares.  Frames and outputs are DEVICE buffers (ints or torch tensors, float32,
@@ -607,13 +617,17 @@ class History:
     """Per-pixel running mean that survives camera moves (include/hpt.h, hpt_history_*) for W x H images.  advance() takes
     the frame's camera record, its DEVICE colour image and the three DEVICE guide images of Scene.render_guides_device
     (all three or none), reprojects the previous state where the geometry agrees and writes the new mean; metrics()
-    waits for the last advance.  Every other call only enqueues on `stream`, except read()."""
+    waits for the last advance.  Every other call only enqueues on `stream`, except read().  With moments=True the history
+    also carries the running mean of the squared frame values, and variance() gives the temporal variance of the mean."""
 
-    def __init__(self, W, H):
+    def __init__(self, W, H, moments=False):
         self._lib = load_library()
         self._h = C.c_void_p()
-        self.W, self.H = int(W), int(H)
-        _check(self._lib.hpt_history_create(int(W), int(H), C.byref(self._h)))
+        self.W, self.H, self.moments = int(W), int(H), bool(moments)
+        if moments:
+            _check(self._lib.hpt_history_create_flags(int(W), int(H), C.c_int32(HISTORY_MOMENTS), C.byref(self._h)))
+        else:
+            _check(self._lib.hpt_history_create(int(W), int(H), C.byref(self._h)))
 
     def advance(self, camera, frame, normal=None, position=None, coverage=None, params: HistoryParams | None = None, mean_out=None,
                 stream: int = 0):
@@ -632,12 +646,24 @@ class History:
         return dict(kept=int(k.value), restarted=int(r.value), frames=int(n.value))
 
     def read(self) -> dict:
-        """Waits for the device: dict(mean [H, W, 3] f32, length [H, W] f32, frames int)."""
+        """Waits for the device: dict(mean [H, W, 3] f32, length [H, W] f32, frames int), and q [H, W, 3] f32 on a moments
+        history."""
         m = np.empty((self.H, self.W, 3), np.float32)
         n = np.empty((self.H, self.W), np.float32)
         k = C.c_int64()
         _check(self._lib.hpt_history_read(self._h, _vp(m), _vp(n), C.byref(k)))
-        return dict(mean=m, length=n, frames=int(k.value))
+        out = dict(mean=m, length=n, frames=int(k.value))
+        if self.moments:
+            q = np.empty((self.H, self.W, 3), np.float32)
+            _check(self._lib.hpt_history_read_moments(self._h, _vp(q)))
+            out["q"] = q
+        return out
+
+    def variance(self, out, fallback=None, min_length=0.0, stream: int = 0):
+        """The temporal variance of the mean into the DEVICE image `out` (W*H*3 float32) where a pixel's history length is
+        at least min_length (0 -> 4), `fallback` (W*H*3, may be `out` itself; None -> 0) elsewhere; enqueues only."""
+        _check(self._lib.hpt_history_variance(self._h, _dptr(fallback) if fallback is not None else None, C.c_float(min_length),
+                                              _dptr(out) if out is not None else None, C.c_void_p(stream)))
 
     def length(self, out, stream: int = 0):
         """The current history length n of every pixel into the DEVICE image `out` (W*H float32); enqueues only."""

@@ -100,6 +100,21 @@ int check_advance(int W, int H, const void *camera, const void *frame, const voi
     return HPT_OK;
 }
 
+// every check of a variance call that needs no handle; fills the resolved minimum length
+int check_variance(int W, int H, int32_t create_flags, const void *fallback, float min_length, const void *out, float &L){
+    if(int rc = check_size(W, H)) return rc;
+    if(create_flags & ~HPT_HISTORY_MOMENTS) return fail(HPT_ERR_INVALID, "hpt_history_create_flags: unknown flag");
+    if(!(create_flags & HPT_HISTORY_MOMENTS))
+        return fail(HPT_ERR_INVALID, "hpt_history_variance: the history was created without HPT_HISTORY_MOMENTS");
+    if(!out) return fail(HPT_ERR_INVALID, "null variance image");
+    L = min_length == 0.0f ? 4.0f : min_length;
+    if(!(L >= 2.0f)) return fail(HPT_ERR_INVALID, "hpt_history_variance: min_length must be at least 2 (0 selects 4)");
+    const size_t bytes = (size_t) W * H * 12;
+    if(fallback && fallback != out && overlap(fallback, bytes, out, bytes))
+        return fail(HPT_ERR_INVALID, "hpt_history_variance: the images must not overlap (d_fallback may be d_variance_out itself)");
+    return HPT_OK;
+}
+
 } // namespace
 
 struct hpt_history {
@@ -109,10 +124,12 @@ struct hpt_history {
     int cur = 0;                     // the set that holds the previous state
     unsigned char camera[HPT_CAMERA_BYTES] = {};
     HistoryCamera cam_prev{};
-    DevBuf<float4> mean_n[2], pos_cov[2], nrm[2];
+    int32_t flags = 0;               // HPT_HISTORY_MOMENTS
+    DevBuf<float4> mean_n[2], pos_cov[2], nrm[2], sq[2];   // sq: allocated with HPT_HISTORY_MOMENTS only
     DevBuf<unsigned long long> metrics;      // kept, restarted of the advance in flight
     unsigned long long *h_metrics = nullptr; // pinned copy, valid once `done` has passed
     hipEvent_t done = nullptr;
+    bool moments() const { return (flags & HPT_HISTORY_MOMENTS) != 0; }
     HistorySet set(int k) const { return HistorySet{ mean_n[k].get(), pos_cov[k].get(), nrm[k].get() }; }
     ~hpt_history(){
         if(done) hipEventDestroy(done);
@@ -128,13 +145,21 @@ int hpt_history_check(int W, int H, const void *camera, const void *d_frame_rgb,
     return check_advance(W, H, camera, d_frame_rgb, d_normal, d_position, d_coverage, p, d_mean_out, cam, res);
 }
 
-int hpt_history_create(int W, int H, hpt_history **out){
+int hpt_history_variance_check(int W, int H, int32_t create_flags, const void *d_fallback, float min_length, const void *d_variance_out){
+    float L;
+    return check_variance(W, H, create_flags, d_fallback, min_length, d_variance_out, L);
+}
+
+int hpt_history_create(int W, int H, hpt_history **out){ return hpt_history_create_flags(W, H, 0, out); }
+
+int hpt_history_create_flags(int W, int H, int32_t flags, hpt_history **out){
     if(!out) return fail(HPT_ERR_INVALID, "null out");
     *out = nullptr;
     if(int rc = check_size(W, H)) return rc;
+    if(flags & ~HPT_HISTORY_MOMENTS) return fail(HPT_ERR_INVALID, "hpt_history_create_flags: unknown flag");
     hpt_history *h = new (std::nothrow) hpt_history;
     if(!h) return fail(HPT_ERR_NOMEM, "out of host memory");
-    h->W = W; h->H = H; h->npx = (uint32_t) W * (uint32_t) H;
+    h->W = W; h->H = H; h->npx = (uint32_t) W * (uint32_t) H; h->flags = flags;
     hipError_t e = hipGetDevice(&h->device);
     for(int k = 0; k < 2; ++k){
         if(e == hipSuccess) e = h->mean_n[k].reserve(h->npx);
@@ -143,6 +168,8 @@ int hpt_history_create(int W, int H, hpt_history **out){
         if(e == hipSuccess) e = hipMemset(h->mean_n[k].get(), 0, (size_t) h->npx * sizeof(float4));
         if(e == hipSuccess) e = hipMemset(h->pos_cov[k].get(), 0, (size_t) h->npx * sizeof(float4));
         if(e == hipSuccess) e = hipMemset(h->nrm[k].get(), 0, (size_t) h->npx * sizeof(float4));
+        if(e == hipSuccess && h->moments()) e = h->sq[k].reserve(h->npx);
+        if(e == hipSuccess && h->moments()) e = hipMemset(h->sq[k].get(), 0, (size_t) h->npx * sizeof(float4));
     }
     if(e == hipSuccess) e = h->metrics.reserve(2);
     if(e == hipSuccess) e = hipHostMalloc((void **) &h->h_metrics, 2 * sizeof(unsigned long long), hipHostMallocDefault);
@@ -166,6 +193,7 @@ int hpt_history_advance(hpt_history *h, const void *camera, const void *d_frame_
     a.mode = h->frames == 0 ? kHistoryFirst : memcmp(camera, h->camera, HPT_CAMERA_BYTES) == 0 ? kHistoryIdentity : kHistoryMoved;
     const int next = a.mode == kHistoryMoved ? h->cur ^ 1 : h->cur;       // only a moved frame reads its neighbours
     a.prev = h->set(h->cur); a.next = h->set(next);
+    if(h->moments()){ a.sq_prev = h->sq[h->cur].get(); a.sq_next = h->sq[next].get(); }
     a.frame = (const float *) d_frame_rgb; a.normal = (const float *) d_normal; a.position = (const float *) d_position;
     a.coverage = (const float *) d_coverage; a.mean_out = (float *) d_mean_out;
     a.metrics = h->metrics.get();
@@ -212,6 +240,30 @@ int hpt_history_read(hpt_history *h, float *mean, float *length, int64_t *frames
     return HPT_OK;
 }
 
+int hpt_history_read_moments(hpt_history *h, float *q){
+    if(!h) return fail(HPT_ERR_INVALID, "null history");
+    if(!h->moments()) return fail(HPT_ERR_INVALID, "hpt_history_read_moments: the history was created without HPT_HISTORY_MOMENTS");
+    if(!q) return fail(HPT_ERR_INVALID, "null moments image");
+    if(int rc = on_device(h->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<float4> rec(h->npx);
+    HIP_TRY(hipMemcpy(rec.data(), h->sq[h->cur].get(), (size_t) h->npx * sizeof(float4), hipMemcpyDeviceToHost));
+    for(size_t k = 0; k < rec.size(); ++k){ q[3 * k] = rec[k].x; q[3 * k + 1] = rec[k].y; q[3 * k + 2] = rec[k].z; }
+    return HPT_OK;
+}
+
+int hpt_history_variance(hpt_history *h, const void *d_fallback, float min_length, void *d_variance_out, void *hip_stream){
+    if(!h) return fail(HPT_ERR_INVALID, "null history");
+    float L;
+    if(int rc = check_variance(h->W, h->H, h->flags, d_fallback, min_length, d_variance_out, L)) return rc;
+    if(h->frames < 1) return fail(HPT_ERR_INVALID, "hpt_history_variance before the first hpt_history_advance");
+    if(int rc = on_device(h->device)) return rc;
+    launch_history_variance((hipStream_t) hip_stream, h->mean_n[h->cur].get(), h->sq[h->cur].get(), (const float *) d_fallback,
+                            (float *) d_variance_out, h->npx, L);
+    HIP_TRY(hipGetLastError());
+    return HPT_OK;
+}
+
 int hpt_history_length(hpt_history *h, void *d_length_out, void *hip_stream){
     if(!h) return fail(HPT_ERR_INVALID, "null history");
     if(!d_length_out) return fail(HPT_ERR_INVALID, "null length image");
@@ -229,6 +281,7 @@ int hpt_history_reset(hpt_history *h, void *hip_stream){
     HIP_TRY(hipMemsetAsync(h->mean_n[h->cur].get(), 0, (size_t) h->npx * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(h->pos_cov[h->cur].get(), 0, (size_t) h->npx * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(h->nrm[h->cur].get(), 0, (size_t) h->npx * sizeof(float4), st));
+    if(h->moments()) HIP_TRY(hipMemsetAsync(h->sq[h->cur].get(), 0, (size_t) h->npx * sizeof(float4), st));
     h->frames = 0;
     return HPT_OK;
 }

@@ -12,7 +12,8 @@ struct HistoryCamera {
     float an;
 };
 
-// One set of per-pixel state: three 16-byte records per pixel, so a tap is three 16-byte loads.
+// One set of per-pixel state: three 16-byte records per pixel, so a tap is three 16-byte loads.  (A history that keeps
+// second moments has a fourth record per set, HistoryArgs::sq_prev / sq_next, and a tap is four loads.)
 struct HistorySet {
     float4 *mean_n;      // mean.rgb, n
     float4 *pos_cov;     // position.xyz, coverage
@@ -35,9 +36,18 @@ struct HistoryArgs {
     float tol2;                      // plane_tolerance * plane_tolerance
     float normal_min;
     int plane_on, normal_on;
+    // q.rgb, 0 of the two sets: the running mean of the squared frame values; both null without HPT_HISTORY_MOMENTS.  Kept
+    // behind everything else, so the kernels without moments read the arguments they always read from where they always were.
+    const float4 *sq_prev;
+    float4 *sq_next;
 };
-// one lane per pixel; the grid depends on W and H only
+// one lane per pixel; the grid depends on W and H only.  sq_next selects the kernels that carry the second moment.
 void launch_history_advance(hipStream_t s, const HistoryArgs &a);
+
+// out[3 p + c] = n[p] >= min_length ? fmaxf(q - m * m, 0) / (n - 1) : fallback ? fallback[3 p + c] : 0, one lane per pixel;
+// `out` may be `fallback`
+void launch_history_variance(hipStream_t s, const float4 *mean_n, const float4 *sq, const float *fallback, float *out, uint32_t npx,
+                             float min_length);
 
 // out[k] = in[3 k] for k < n: the coverage image out of the three-channel image launch_untile writes
 void launch_take_first_channel(hipStream_t s, const float *in3, float *out, uint32_t n);

@@ -4,7 +4,11 @@
 //                      create or reset and a frame from an unmoved camera touch the pixel's own records only and work in
 //                      place; a frame from a moved camera projects the pixel's guide point into the previous camera, reads
 //                      up to four neighbours' records from the previous set (three 16-byte loads per tap) and writes the
-//                      other set.
+//                      other set.  MOMENTS (a history created with HPT_HISTORY_MOMENTS) carries the running mean of the
+//                      squared frame values through the same steps with the same taps and weights: a fourth 16-byte record
+//                      per pixel and a fourth load per tap.
+//   k_history_variance one lane per pixel, a pure map: the variance of the mean from mean, second moment and length where
+//                      the history is long enough, the caller's fallback elsewhere.
 //
 // IEEE float evaluated as written (-ffp-contract=off, correctly rounded divide), no float atomic; the two counters are
 // integer sums, reduced in the workgroup and added with one 64-bit atomic each, so their order does not show
@@ -38,7 +42,7 @@ __device__ __forceinline__ Projected project(const HistoryCamera &c, V3 X){
 
 // Lanes past the image take part in the ballots and the barrier with both flags false.  A lane reads its frame colour
 // before it writes the mean, so mean_out may be the frame.
-template <int MODE, bool GUIDES>
+template <int MODE, bool GUIDES, bool MOMENTS>
 __global__ __launch_bounds__(kBlock)
 void k_history_advance(HistoryArgs a){
     __shared__ uint32_t s_part[2][kBlock / 64];
@@ -47,7 +51,7 @@ void k_history_advance(HistoryArgs a){
     bool kept = false, restarted = false;
     if(p < npx){
         const V3 c = ld3(a.frame + 3u * p);
-        V3 m{ 0.0f, 0.0f, 0.0f };
+        V3 m{ 0.0f, 0.0f, 0.0f }, m2{ 0.0f, 0.0f, 0.0f };       // m2: the reprojected second moment q_r
         float n_r = 0.0f;
         V3 X{ 0.0f, 0.0f, 0.0f }, N{ 0.0f, 0.0f, 0.0f };
         float cov = 0.0f;
@@ -55,6 +59,7 @@ void k_history_advance(HistoryArgs a){
         if(MODE == kHistoryIdentity){
             const float4 mp = a.prev.mean_n[p];
             m = V3{ mp.x, mp.y, mp.z }; n_r = mp.w;
+            if(MOMENTS){ const float4 sp = a.sq_prev[p]; m2 = V3{ sp.x, sp.y, sp.z }; }
         }
         if(MODE == kHistoryMoved && GUIDES && cov > 0.0f){
             const uint32_t y = p / (uint32_t) a.W, x = p - y * (uint32_t) a.W;
@@ -68,7 +73,7 @@ void k_history_advance(HistoryArgs a){
                 const float fx = up - fx0, fy = vp - fy0;
                 const int x0 = (int) fx0, y0 = (int) fy0;
                 const float lim = a.tol2 * now.dist2;
-                V3 sum{ 0.0f, 0.0f, 0.0f };
+                V3 sum{ 0.0f, 0.0f, 0.0f }, qsum{ 0.0f, 0.0f, 0.0f };
                 float nsum = 0.0f, wsum = 0.0f;
 #pragma unroll
                 for(int j = 0; j < 2; ++j){
@@ -90,26 +95,34 @@ void k_history_advance(HistoryArgs a){
                         const float4 mq = a.prev.mean_n[q];
                         const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
                         sum.x = sum.x + mq.x * w; sum.y = sum.y + mq.y * w; sum.z = sum.z + mq.z * w;
+                        if(MOMENTS){
+                            const float4 sq = a.sq_prev[q];
+                            qsum.x = qsum.x + sq.x * w; qsum.y = qsum.y + sq.y * w; qsum.z = qsum.z + sq.z * w;
+                        }
                         nsum = nsum + mq.w * w;
                         wsum = wsum + w;
                     }
                 }
                 if(wsum > 0.01f){
                     m = V3{ sum.x / wsum, sum.y / wsum, sum.z / wsum };
+                    if(MOMENTS) m2 = V3{ qsum.x / wsum, qsum.y / wsum, qsum.z / wsum };
                     n_r = nsum / wsum;
                 }
             }
         }
-        V3 mean = c;
+        V3 mean = c, msq{ 0.0f, 0.0f, 0.0f };
+        if(MOMENTS) msq = V3{ c.x * c.x, c.y * c.y, c.z * c.z };
         float n = 1.0f;
         if(n_r > 0.0f){
             const float n_c = fminf(n_r, a.max_history_m1);
             const float n1 = n_c + 1.0f;
             mean = V3{ (m.x * n_c + c.x) / n1, (m.y * n_c + c.y) / n1, (m.z * n_c + c.z) / n1 };
+            if(MOMENTS) msq = V3{ (m2.x * n_c + c.x * c.x) / n1, (m2.y * n_c + c.y * c.y) / n1, (m2.z * n_c + c.z * c.z) / n1 };
             n = n1;
             kept = true;
         } else restarted = MODE != kHistoryFirst;
         a.next.mean_n[p] = make_float4(mean.x, mean.y, mean.z, n);
+        if(MOMENTS) a.sq_next[p] = make_float4(msq.x, msq.y, msq.z, 0.0f);
         if(GUIDES){
             a.next.pos_cov[p] = make_float4(X.x, X.y, X.z, cov);
             a.next.nrm[p] = make_float4(N.x, N.y, N.z, 0.0f);
@@ -131,10 +144,41 @@ void k_history_advance(HistoryArgs a){
     }
 }
 
+// A lane reads its fallback values before it writes, so `out` may be `fallback`.
+__global__ __launch_bounds__(kBlock)
+void k_history_variance(const float4 *mean_n, const float4 *sq, const float *fallback, float *out, uint32_t npx, float min_length){
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if(p >= npx) return;
+    const float4 mn = mean_n[p];
+    V3 v{ 0.0f, 0.0f, 0.0f };
+    if(mn.w >= min_length){
+        const float4 q = sq[p];
+        const float nm1 = mn.w - 1.0f;
+        v = V3{ fmaxf(q.x - mn.x * mn.x, 0.0f) / nm1, fmaxf(q.y - mn.y * mn.y, 0.0f) / nm1, fmaxf(q.z - mn.z * mn.z, 0.0f) / nm1 };
+    } else if(fallback) v = ld3(fallback + 3u * p);
+    float *o = out + 3u * p;
+    o[0] = v.x; o[1] = v.y; o[2] = v.z;
+}
+
 __global__ __launch_bounds__(kBlock)
 void k_take_first_channel(const float *in3, float *out, uint32_t n){
     const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
     if(k < n) out[k] = in3[3u * k];
+}
+
+template <bool MOMENTS>
+void launch_advance(hipStream_t s, const dim3 &grid, const dim3 &block, const HistoryArgs &a){
+    const bool g = a.position != nullptr;
+    if(a.mode == kHistoryFirst){
+        if(g) hipLaunchKernelGGL((k_history_advance<kHistoryFirst, true, MOMENTS>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_history_advance<kHistoryFirst, false, MOMENTS>), grid, block, 0, s, a);
+    } else if(a.mode == kHistoryIdentity){
+        if(g) hipLaunchKernelGGL((k_history_advance<kHistoryIdentity, true, MOMENTS>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_history_advance<kHistoryIdentity, false, MOMENTS>), grid, block, 0, s, a);
+    } else {
+        if(g) hipLaunchKernelGGL((k_history_advance<kHistoryMoved, true, MOMENTS>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_history_advance<kHistoryMoved, false, MOMENTS>), grid, block, 0, s, a);
+    }
 }
 
 } // namespace
@@ -142,17 +186,13 @@ void k_take_first_channel(const float *in3, float *out, uint32_t n){
 void launch_history_advance(hipStream_t s, const HistoryArgs &a){
     const uint32_t npx = (uint32_t) a.W * (uint32_t) a.H;
     const dim3 grid((npx + kBlock - 1) / kBlock), block(kBlock);
-    const bool g = a.position != nullptr;
-    if(a.mode == kHistoryFirst){
-        if(g) hipLaunchKernelGGL((k_history_advance<kHistoryFirst, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_history_advance<kHistoryFirst, false>), grid, block, 0, s, a);
-    } else if(a.mode == kHistoryIdentity){
-        if(g) hipLaunchKernelGGL((k_history_advance<kHistoryIdentity, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_history_advance<kHistoryIdentity, false>), grid, block, 0, s, a);
-    } else {
-        if(g) hipLaunchKernelGGL((k_history_advance<kHistoryMoved, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_history_advance<kHistoryMoved, false>), grid, block, 0, s, a);
-    }
+    if(a.sq_next) launch_advance<true>(s, grid, block, a);
+    else launch_advance<false>(s, grid, block, a);
+}
+
+void launch_history_variance(hipStream_t s, const float4 *mean_n, const float4 *sq, const float *fallback, float *out, uint32_t npx,
+                             float min_length){
+    hipLaunchKernelGGL(k_history_variance, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, s, mean_n, sq, fallback, out, npx, min_length);
 }
 
 void launch_take_first_channel(hipStream_t s, const float *in3, float *out, uint32_t n){

@@ -1,5 +1,6 @@
 // pt_cli --frames (frame_loop.hpp): render, untile, accumulate (or, with --reproject, advance the history), with --guided
-// filter the mean under its variance, and present every frame on one stream, read the sums back.
+// filter the mean under its variance (with --temporal-variance the history's own where it is long enough), and present
+// every frame on one stream, read the sums back.
 #include "frame_loop.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -54,6 +55,8 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
 
     const bool reproject = motion && motion->reproject;
     const bool guided = motion && motion->guided;
+    const bool temporal = motion && motion->temporal_variance;
+    if(temporal && !(reproject && guided)){ std::cerr << "[Error] --temporal-variance needs --reproject and --guided" << std::endl; return -1; }
     if((reproject || guided) && motion->guide_spp < 1){ std::cerr << "[Error] --guide-spp must be at least 1" << std::endl; return -1; }
     DeviceMem d_local, d_frame, d_mean, d_rgb8, d_normal, d_position, d_coverage;      // released after L has waited for its stream
     DeviceMem d_albedo, d_variance, d_length, d_filtered;                              // --guided
@@ -76,7 +79,7 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         if(hpt_denoiser_create(W, H, &L.denoiser) != HPT_OK) return hpt_failed("hpt_denoiser_create");
     }
     if(reproject){
-        if(hpt_history_create(W, H, &L.history) != HPT_OK) return hpt_failed("hpt_history_create");
+        if(hpt_history_create_flags(W, H, temporal ? HPT_HISTORY_MOMENTS : 0, &L.history) != HPT_OK) return hpt_failed("hpt_history_create");
     }
     else if(hpt_accum_create(W, H, guided ? HPT_ACCUM_MOMENTS : 0, &L.accum) != HPT_OK) return hpt_failed("hpt_accum_create");
     if(hpt_display_create(W, H, &L.display) != HPT_OK) return hpt_failed("hpt_display_create");
@@ -140,6 +143,9 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
                 }
                 if(hpt_denoiser_estimate_variance(L.denoiser, d_frame.p, d_length.p, d_variance.p, &gp, L.stream) != HPT_OK)
                     return hpt_failed("hpt_denoiser_estimate_variance");
+                // the history's own variance over time where it is long enough, patched into the estimate
+                if(temporal && hpt_history_variance(L.history, d_variance.p, 0.0f, d_variance.p, L.stream) != HPT_OK)
+                    return hpt_failed("hpt_history_variance");
             }
             if(hpt_denoiser_run_guided(L.denoiser, d_mean.p, d_variance.p, d_filtered.p, nullptr, &gp, L.stream) != HPT_OK)
                 return hpt_failed("hpt_denoiser_run_guided");

@@ -38,11 +38,17 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // accumulator keeps moments and from its fourth frame on hpt_accum_variance is used, before that
 // hpt_denoiser_estimate_variance of the frame with a length image filled with the frame count; with reproject the
 // estimate of the frame with hpt_history_length.  Without `guided` the loop, its launches and its output are unchanged.
+//
+// With `temporal_variance` (needs reproject and guided; refused otherwise) the history is created with
+// HPT_HISTORY_MOMENTS, and after hpt_history_length and hpt_denoiser_estimate_variance the loop calls hpt_history_variance
+// in place on the estimate: a pixel whose history is at least four frames long gets its own variance over time, the
+// others keep the spatial estimate.  Without it the loop, its launches and its output are unchanged.
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
     bool reproject = false;
     int guide_spp = 4;
     bool guided = false;
+    bool temporal_variance = false;
 };
 int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                    int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,

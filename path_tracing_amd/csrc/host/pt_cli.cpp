@@ -24,6 +24,9 @@
 //                     instead of the mean: guides with albedo on frame 0 and every moved frame (--guide-spp >= 1), the
 //                     variance from the accumulator's moments or, in the first frames and under --reproject, from the
 //                     spatial estimate of the new frame divided by the history length.
+//   --temporal-variance   with --frames --reproject --guided: the history also carries each pixel's second moment
+//                     (HPT_HISTORY_MOMENTS), and where a pixel's history is at least four frames long its own variance
+//                     over time (hpt_history_variance) replaces the spatial estimate.
 // --mode pt, bdpt, ppm and sppm are built; bdpt renders the reference's CPU estimator (run_cpu_bdpt) on the GPU, ppm the
 // reference's photon mapping (ppm_cu.cu) with a gather in a fixed order: --spp passes of --spl photons per light,
 // averaged, on one device; sppm the same passes into one progressive state whose radius shrinks per pixel.
@@ -57,7 +60,7 @@ int main(int argc, char **argv){
     double until_rms = -1.0;
     std::string rms_log;
     double orbit_deg = 0.0;
-    bool orbit = false, reproject = false, guided = false;
+    bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -88,6 +91,7 @@ int main(int argc, char **argv){
         else if(arg == "--orbit" && i + 1 < argc){ orbit_deg = std::stod(argv[++i]); orbit = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
+        else if(arg == "--temporal-variance") temporal_variance = true;
         else if(arg == "--help" || arg == "-h"){
             std::cout << "Usage: pt_cli [options]\n"
                       << "Options:\n"
@@ -117,7 +121,9 @@ int main(int argc, char **argv){
                       << "                    around the up vector; the accumulation restarts on every moved frame\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
                       << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
-                      << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n";
+                      << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n"
+                      << "  --temporal-variance  with --frames --reproject --guided: carry second moments through the history and use each\n"
+                      << "                    pixel's variance over time where its history is at least four frames long\n";
             return 0;
         }
     }
@@ -131,6 +137,9 @@ int main(int argc, char **argv){
     std::cout << "====================================\n";
     if(mode != "pt" && mode != "bdpt" && mode != "ppm" && mode != "sppm"){ std::cerr << "[Error] unknown mode " << mode << " (pt, bdpt, ppm, sppm).\n"; return -1; }
     const bool progressive = frames != 0 || frame_spp != 0 || until_rms >= 0.0 || !rms_log.empty();
+    if(temporal_variance && (frames < 1 || !reproject || !guided)){
+        std::cerr << "[Error] --temporal-variance needs --frames N (N >= 1), --reproject and --guided.\n"; return -1;
+    }
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
     if(guided && frames < 1){ std::cerr << "[Error] --guided needs --frames N (N >= 1).\n"; return -1; }
     if(guided && guide_spp < 1){ std::cerr << "[Error] --frames --guided needs --guide-spp of at least 1.\n"; return -1; }
@@ -177,7 +186,7 @@ int main(int argc, char **argv){
     std::vector<unsigned char> presented;
     if(progressive){
         hpt_host::FrameMotion motion;
-        motion.reproject = reproject; motion.guide_spp = guide_spp; motion.guided = guided;
+        motion.reproject = reproject; motion.guide_spp = guide_spp; motion.guided = guided; motion.temporal_variance = temporal_variance;
         if(orbit) motion.camera_at = [&](int f, void *camera84){
             // Rodrigues' rotation of eye - look_at about the unit up vector, in double
             const hpt_host::Camera &c = scene.camera;
