@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes front-end of the CPU oracle (oracle/liboracle.so).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this
-package.  PARITY STATUS: parity unpinned (see oracle/ref_math.hpp).
+package.  PARITY STATUS: pinned bit for bit to the reference's own code built for the host -- functions, scans, PT kernel,
+cpu_bdpt (oracle/ref_probe.py, tests/golden/ref_*.npz); the CUDA BDPT and PPM kernels are not.
 """
 from __future__ import annotations
 
@@ -20,13 +21,14 @@ class PtOpts(C.Structure):
                 ("sample_offset", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int),
                 ("threads", C.c_int), ("glass_shadow_opaque", C.c_int), ("max_delta", C.c_int),
                 ("output_sum", C.c_int), ("russian_roulette", C.c_int), ("ball_draw_reversed", C.c_int),
-                ("rcp_nudge_ulps", C.c_int), ("rcp_nudge_mask", C.c_int)]
+                ("rcp_nudge_ulps", C.c_int), ("rcp_nudge_mask", C.c_int), ("bsdf_draw_reversed", C.c_int)]
 
 
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "closest_rays", "shadow_rays", "bounces",
                                           "delta_bounces", "tri_tests", "sphere_tests",
-                                          "boxes_closest", "tris_closest", "boxes_shadow", "tris_shadow")]
+                                          "boxes_closest", "tris_closest", "boxes_shadow", "tris_shadow",
+                                          "max_delta_run")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -63,14 +65,17 @@ def _p(a):
 
 def pt_render(lights, spheres, tris, camera, W, H, max_depth, spp, *, seed=1, rng_mode=0, trig_mode=0,
               sample_offset=0, window=None, threads=0, glass_shadow_opaque=0, max_delta=64, output_sum=False, ball_draw_reversed=False, russian_roulette=False,
-              bvh=None, rcp_nudge=(0, 0)):
+              bvh=None, rcp_nudge=(0, 0), bsdf_draw_reversed=False):
     """Unidirectional PT + NEE (restates src/pt_cu.cu:20-250).  Returns (image[H,W,3] f32, stats dict).
     Pixels outside `window` = (x0, y0, x1, y1) stay zero.  bvh: the dict path_tracing_amd.export_bvh_host /
     Scene.export_bvh return -- triangles are then found by walking that tree on the host (same image as the scan) and
     stats carry boxes_* / tris_*: the independent count behind the bench's algorithmic bytes.
     rcp_nudge = (ulps, sign_mask), with bvh only: the walk's three reciprocals are moved `ulps` float neighbours before
     use, up where the axis bit of sign_mask (1 x, 2 y, 4 z) is set and down otherwise -- a reciprocal that is not
-    correctly rounded.  Triangle tests and the scan are untouched, so a conservative tree still gives the scan's image."""
+    correctly rounded.  Triangle tests and the scan are untouched, so a conservative tree still gives the scan's image.
+    Replaying the reference's kernel as g++ compiles it (tests/golden/ref_pt_kernel.npz) takes rng_mode=1, trig_mode=1,
+    glass_shadow_opaque=1 and both ball_draw_reversed and bsdf_draw_reversed: g++ evaluates call arguments right to left.
+    stats["max_delta_run"] is the most free delta bounces one sample took (the reference has no cap; max_delta is ours)."""
     img = np.zeros((H, W, 3), np.float32)
     o = PtOpts()
     o.seed, o.rng_mode, o.trig_mode, o.sample_offset = int(seed), rng_mode, trig_mode, sample_offset
@@ -79,6 +84,7 @@ def pt_render(lights, spheres, tris, camera, W, H, max_depth, spp, *, seed=1, rn
     o.ball_draw_reversed = int(ball_draw_reversed)
     o.russian_roulette = int(russian_roulette)
     o.rcp_nudge_ulps, o.rcp_nudge_mask = int(rcp_nudge[0]), int(rcp_nudge[1])
+    o.bsdf_draw_reversed = int(bsdf_draw_reversed)
     st = PtStats()
     cam = np.ascontiguousarray(camera)
     lights = np.ascontiguousarray(lights)
@@ -136,11 +142,12 @@ def bsdf_sample(mat6, wo, n, u3, cur_eta=1.0, trig_mode=0):
     return dict(wi=out[0:3].copy(), f=out[3:6].copy(), pdf=float(out[6]), is_delta=bool(out[7]), new_eta=float(out[8]))
 
 
-def function_kats(records):
-    """[n, 24] float32 records -> [n, 40] results of the restated reference functions (layout: oracle_function_kats)."""
+def function_kats(records, trig_mode=0):
+    """[n, 24] float32 records -> [n, 40] results of the restated reference functions (layout: oracle_function_kats).
+    trig_mode=1: libm sinf / cosf where the reference calls them -- the table tests/golden/ref_functions.npz pins."""
     rec = np.ascontiguousarray(records, np.float32).reshape(-1, 24)
     out = np.zeros((len(rec), 40), np.float32)
-    lib().oracle_function_kats(_p(rec), len(rec), _p(out))
+    lib().oracle_function_kats_mode(_p(rec), len(rec), _p(out), int(trig_mode))
     return out
 
 

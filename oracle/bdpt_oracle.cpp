@@ -4,9 +4,12 @@
 // one-level group boxes).  It is the checker / CPU baseline for the BDPT-estimator rows of
 // SURVEY.md section 8; nothing in path_tracing_amd/ links or calls it.
 //
-// PARITY STATUS: parity unpinned (see ref_math.hpp).  Advisory: in replay mode (one
-// std::mt19937 stream per pass, seeds 1337 / 9999, one thread) it is compared with an image the
-// survey stage produced from the reference's own cpu_bdpt.cpp (tests/golden/README.md).
+// PARITY STATUS: PINNED to the reference's own run_cpu_bdpt built for the host (oracle/Makefile
+// target `ref`): in replay mode (one std::mt19937 stream per pass, seeds 1337 / 9999, one thread)
+// it reproduces tests/golden/ref_cpu_bdpt.npz (input.txt and mis_test.txt, 32 x 32) and the image the
+// survey stage produced from the same sources bit for bit (tests/test_reference_pin_cpu.py,
+// tests/test_bdpt_oracle.py).  The reference's CUDA BDPT kernels are NOT built and stay parity
+// unpinned: the device path is held to this estimator, not to them.
 //
 // Host arithmetic notes: the reference's CPU model uses glm: normalize(v) = v * (1/sqrt(dot)),
 // while its float3 helpers divide by the length (ref_math.hpp); each is kept where the

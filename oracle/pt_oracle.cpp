@@ -5,7 +5,12 @@
 // reference's brute-force scene scans (include/geometric.cuh:293-388).  It is the
 // checker for the HIP kernels; nothing in path_tracing_amd/ links or calls it.
 //
-// PARITY STATUS: parity unpinned (see ref_math.hpp header and tests/golden/README.md).
+// PARITY STATUS: PINNED, bit for bit, to the reference's own code built for the host (oracle/Makefile target `ref`,
+// fixtures tests/golden/ref_*.npz, tests/test_reference_pin_cpu.py): the scans (find_closest_hit's t and scan ordinal,
+// check_visibility under both settings of mtl_old) on nine hostile scenes, and cuda_path_trace_kernel through
+// pt_render_wrapper's own launch on eight small renders, against the replay mode (rng_mode 1, libm trig, zeroed mtl_old,
+// both argument orders reversed as g++ evaluates them).  Not pinned: the counter mode's streams and polynomial trig are
+// this project's definitions, and the host walk of the exported tree has no counterpart there.
 //
 // Behaviour the reference leaves undefined, defined here exactly as in DESIGN.md:
 //  * shadow rays (check_visibility reads uninitialised mtl_old, geometric.cuh:310-311,
@@ -41,6 +46,9 @@ struct OraclePtOpts {
                             //    order of make_float3(u(),u(),u()) is unspecified, geometric.cuh:410)
     int rcp_nudge_ulps;     // host walk only: each per-axis reciprocal is moved this many float neighbours before use,
     int rcp_nudge_mask;     //    up where the axis bit (1 = x, 2 = y, 4 = z) is set, down otherwise (0 ulps = exact division)
+    int bsdf_draw_reversed; // 1 (replay only): the three uniforms of a bsdf_sample call are drawn u2, u1, u_rr -- the order
+                            //    g++ evaluates the call's arguments in (pt_cu.cu:210-212 leaves it unspecified); the
+                            //    counter mode keeps DESIGN section 2's u_rr, u1, u2
 };
 
 struct OraclePtStats {
@@ -48,6 +56,9 @@ struct OraclePtStats {
     // host walk of the library's exported tree (oracle_pt_render_bvh only): child boxes slab-tested (2 per inner-node
     // visit) and triangle tests, by closest-hit and by shadow rays -- what hpt_stats.boxes_* / tris_* must equal
     uint64_t boxes_closest, tris_closest, boxes_shadow, tris_shadow;
+    // the most free delta bounces any one sample took: the reference does not cap them (pt_cu.cu:228), opts.max_delta does,
+    // so a render whose max_delta_run stays below max_delta is one the cap never touched
+    uint64_t max_delta_run;
 };
 
 // The tree libhpt.so built for the scene (include/hpt.h, hpt_bvh_info / hpt_bvh_export_host): the reference has no
@@ -397,6 +408,7 @@ V3 trace_sample(const Scene &sc, const RCamera &cam, int px, int py, int max_dep
         // BSDF sampling, pt_cu.cu:204-241
         V3 wi, bsdf_val; float pdf_omega, new_eta; bool is_delta;
         float u_rr = rng.next(), u1 = rng.next(), u2 = rng.next();
+        if(o.bsdf_draw_reversed){ float tmp = u_rr; u_rr = u2; u2 = tmp; }
         bsdf_sample(o.trig_mode, hit.mtl, wo, hit.normal, u_rr, u1, u2, ray_eta, wi, bsdf_val, pdf_omega, is_delta, new_eta);
         if(pdf_omega <= 0.0f) break;        // non-delta: pt_cu.cu:214; delta: the TIR return (defined: terminate)
         st.bounces++;
@@ -409,7 +421,9 @@ V3 trace_sample(const Scene &sc, const RCamera &cam, int px, int py, int max_dep
             last_is_delta = true;
             if(!is_valid_color(throughput)) break;
             st.delta_bounces++;
-            if(++delta_count > o.max_delta) break;
+            ++delta_count;
+            if((uint64_t) delta_count > st.max_delta_run) st.max_delta_run = (uint64_t) delta_count;
+            if(delta_count > o.max_delta) break;
             depth--;
             continue;
         }
@@ -498,6 +512,7 @@ int oracle_pt_render_bvh(const void *lights, int nl, const void *spheres, int ns
             t.sphere_tests += s.sphere_tests;
             t.boxes_closest += s.boxes_closest; t.tris_closest += s.tris_closest;
             t.boxes_shadow += s.boxes_shadow; t.tris_shadow += s.tris_shadow;
+            t.max_delta_run = std::max(t.max_delta_run, s.max_delta_run);
         }
         *stats_out = t;
     }
@@ -529,7 +544,9 @@ void oracle_bsdf_sample(int trig_mode, const float *mat7, const float *wo, const
 // Function-level known-answer table: the restated reference functions (ref_math.hpp: separate bsdf_evaluate / bsdf_pdf /
 // bsdf_sample, each rebuilding its own frame like geometric.cuh:419-562) on n records.  Same record layout as the
 // device probe k_probe_functions (24 floats in, 40 floats out).
-void oracle_function_kats(const float *in, int n, float *out){
+// trig_mode 1: libm sinf / cosf wherever the reference calls them (bsdf_sample, the visible-normal sample, columns 20 / 21):
+// the table tests/golden/ref_functions.npz holds from the reference's own functions.
+void oracle_function_kats_mode(const float *in, int n, float *out, int trig_mode){
 #pragma omp parallel for schedule(static)
     for(int i = 0; i < n; ++i){
         const float *r = in + (size_t) i * 24;
@@ -539,7 +556,7 @@ void oracle_function_kats(const float *in, int n, float *out){
         V3 f = bsdf_evaluate(m, wo_w, wi_w, N);
         o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = bsdf_pdf(m, wo_w, wi_w, N);
         V3 swi, sf; float spdf, ne; bool d;
-        bsdf_sample(0, m, wo_w, N, r[15], r[16], r[17], r[18], swi, sf, spdf, d, ne);
+        bsdf_sample(trig_mode, m, wo_w, N, r[15], r[16], r[17], r[18], swi, sf, spdf, d, ne);
         o[4] = swi.x; o[5] = swi.y; o[6] = swi.z; o[7] = sf.x; o[8] = sf.y; o[9] = sf.z; o[10] = spdf; o[11] = d ? 1.0f : 0.0f; o[12] = ne;
         o[13] = fr_dielectric(r[19], r[20], r[21]);
         V3 sch = fr_schlick(r[19], m.base_color);
@@ -548,9 +565,9 @@ void oracle_function_kats(const float *in, int n, float *out){
         V3 wo_l = world_to_local(wo_w, T, B, N), wi_l = world_to_local(wi_w, T, B, N);
         const float alpha = roughness_to_alpha(m.roughness);
         o[17] = tr_D(wi_l, alpha); o[18] = tr_lambda(wi_l, alpha); o[19] = tr_G(wo_l, wi_l, alpha);
-        float sn, cs; sincos_2pi_poly(r[17], sn, cs);
+        float sn, cs; sincos_phi(trig_mode, r[17], sn, cs);
         o[20] = sn; o[21] = cs;
-        V3 vn = sample_vndf(0, wo_l.z > 0 ? wo_l : wo_l * -1.0f, alpha, r[16], r[17]);
+        V3 vn = sample_vndf(trig_mode, wo_l.z > 0 ? wo_l : wo_l * -1.0f, alpha, r[16], r[17]);
         o[22] = vn.x; o[23] = vn.y; o[24] = vn.z;
         o[25] = is_valid_color(f) ? 1.0f : 0.0f;
         V3 cl = clamp_radiance(f * 20.0f, 15.0f);
@@ -560,6 +577,7 @@ void oracle_function_kats(const float *in, int n, float *out){
         o[38] = 0.0f; o[39] = 0.0f;
     }
 }
+void oracle_function_kats(const float *in, int n, float *out){ oracle_function_kats_mode(in, n, out, 0); }
 // brute-force closest hit for a batch of rays: out t (1e20 = miss) and prim ordinal (-1 = miss)
 void oracle_closest_hits(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt,
                          const float *ro, const float *rd, int nrays, float *t_out, int *prim_out){

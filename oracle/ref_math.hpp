@@ -5,10 +5,13 @@
 // bench.py's cpu_baseline leg may build, link or call anything under oracle/.
 // The product (path_tracing_amd/) never includes this header.
 //
-// PARITY STATUS: *parity unpinned*.  The reference ships no tests, golden
-// vectors or fixtures for this path, and its sources cannot be compiled in this
-// image (they need glm and <curand_kernel.h>, which are absent; no stand-in
-// headers are written).  Advisory cross-checks only: see tests/golden/README.md.
+// PARITY STATUS: PINNED.  The reference ships no tests, golden vectors or
+// fixtures for this path, but its own sources compile for the host against the
+// stand-in headers of oracle/shim/ (oracle/Makefile, target `ref`), and what they
+// compute is recorded in tests/golden/ref_functions.npz: every function below,
+// with trig_mode 1, reproduces it bit for bit on all 1280 records and 40 columns
+// (tests/test_reference_pin_cpu.py).  Not pinned by construction: sincos_2pi_poly
+// and the Pcg streams, which are this project's definitions, not the reference's.
 //
 // Arithmetic contract (shared, by construction, with the HIP kernels):
 //  * IEEE binary32, every expression evaluated exactly in the order written,

@@ -1,0 +1,4 @@
+// TEST INFRASTRUCTURE ONLY -- host stand-in for <glm/gtc/matrix_transform.hpp>: the reference includes it but the pinned
+// sources use nothing from it.
+#pragma once
+#include <glm/glm.hpp>

@@ -19,8 +19,8 @@ def _input(sio, oracle_mod, raw_light_dirs):
 def test_advisory_replay_of_survey_cpu_bdpt_image(oracle_mod, sio):
     """ADVISORY pin.  survey_cpu_bdpt_input_256x256_4spp_spl8_rows0-63.f32 holds the first 64 rows
     of the image the survey stage got from the reference's own run_cpu_bdpt (input.txt, 256x256,
-    4 spp, spl 8, depth 4/4, OMP_NUM_THREADS=1; built there with stand-in glm/CUDA headers, which
-    this round may not do -- see tests/golden/README.md).  Replaying the reference's two
+    4 spp, spl 8, depth 4/4, OMP_NUM_THREADS=1; built there with stand-in glm/CUDA headers -- see
+    tests/golden/README.md; oracle/_ref/ rebuilt from the same sources gives the same rows).  Replaying the reference's two
     std::mt19937 streams (1337 / 9999) on one thread must reproduce it bit for bit; the whole
     256x256 image was checked once the same way (max-abs 0, mean 0.16336238 = SURVEY Appendix C)."""
     sc, L, sp, tr, order = _input(sio, oracle_mod, raw_light_dirs=True)
