@@ -569,7 +569,8 @@ void hpt_display_destroy(hpt_display *d);
  * second moment ("temporal variance", below).  Without it the variance-guided filter estimates the variance of every
  * frame spatially and divides by hpt_history_length's n.  The guide position is an average
  * over jittered samples, so pixels that straddle an edge mostly fail the direct-view or the plane test and restart.
- * There are no motion vectors: the scene is static in this library.  Once n reaches max_history the mean turns into an
+ * There are no motion vectors: geometry that moves ("scene updates", below) is not followed -- reset the history after an
+ * update.  Once n reaches max_history the mean turns into an
  * exponential average with weight 1 / max_history for the new frame, which is what lets lighting seen from a new angle
  * (a highlight, a reflection) converge to its new value instead of keeping the old one forever. */
 typedef struct hpt_history hpt_history;
@@ -740,6 +741,61 @@ int hpt_trace_closest(hpt_scene *scene, const float *origins, const float *dirs,
  * when no opaque primitive blocks the segment. */
 int hpt_trace_visibility(hpt_scene *scene, const float *p1, const float *p2, int n,
                          int flags, int32_t *visible_out);
+
+/* ---- scene updates -----------------------------------------------------------------------------------
+ * A live scene's geometry moved in place: the handle, its workspaces and the tree's topology stay, and everything that
+ * is a function of the vertex positions -- the leaf records, every node box, the 16-bit grid, both quantised trees and
+ * the per-triangle frames -- is recomputed on the device (a refit), to the bytes the host restatement gives
+ * (hpt_bvh_refit_host).  The image does not depend on the tree's quality: closest hits break ties by scan ordinal and
+ * occlusion is a boolean, so a refitted tree renders what a rebuilt one renders; what a refit costs is traversal work,
+ * since boxes refitted to vertices that moved far overlap more than the builder would have let them.
+ *
+ * hpt_scene_update_triangles takes num_triangles records of HPT_TRIANGLE_BYTES as hpt_scene_create does.  The count
+ * must be the scene's, and the 84 bytes of every record behind its three vertices (old material, material, id) must
+ * equal the record the scene was created from: an update moves geometry, it does not re-intern materials.  The call is
+ * blocking and runs on the null stream, like every blocking entry point: the caller has waited for earlier work on
+ * other streams.  Afterwards every integrator on the handle renders the new scene -- PT, BDPT (groups set earlier are
+ * kept), photon mapping, the guides and the probes.  Workspaces, the statistics that describe the scene's shape
+ * (bvh_nodes, bvh_depth, n_tris, n_materials) and ms_bvh_build are untouched.  Triangles with a non-finite edge are
+ * dead, as at creation (no ray hits them, no box holds them), and may come back to life in a later update.
+ *
+ * hpt_scene_update_rounds replaces the spheres and the lights, which are scanned, not in the tree: the counts must be
+ * the scene's and the 84 bytes of every sphere record behind centre and radius must be unchanged; any field of a light
+ * may change.
+ *
+ * Both calls replace the records the handle keeps and invalidate what is derived from them lazily (the bidirectional
+ * scene, the photon-mapping bounds).  They return HPT_ERR_INVALID, with a message, before anything touches the device
+ * for: a null scene, or a null array with a non-zero count; a count that is not the scene's; changed bytes other than
+ * positions (the message names the first record); a current device other than the scene's.  A scene of zero triangles
+ * accepts an update of zero triangles.  hpt_scene_update_check makes the refusals of hpt_scene_update_triangles and
+ * nothing else: no device work.  After HPT_ERR_DEVICE from an update the scene must be destroyed.
+ *
+ * What the caller keeps in step: an hpt_sppm state created before an update still holds the old scene's bounds and
+ * statistics -- reset or recreate it (not checked).  hpt_history and hpt_accum have no motion vectors for moving
+ * geometry: with a still camera they would average two scenes, so reset them after an update.
+ *
+ * hpt_scene_get_update_info describes the last hpt_scene_update_triangles (zeros before the first): how many have been
+ * made, how many triangles were live and dead, and the milliseconds of packing the vertices (36 bytes per triangle),
+ * of uploading them (the first update also allocates the scratch) and of the device part (HIP events around it).
+ *
+ * hpt_bvh_refit_host is the definition, on the host alone (no device): it builds from `triangles`, refits to
+ * `new_triangles` (same count, same non-vertex bytes) and exports as hpt_bvh_export_host does.  Refitting a tree to the
+ * vertices it was built from reproduces the builder's bytes.
+ *
+ * Out of scope: vertices handed over as a device pointer; topology changes and automatic rebuilds (a caller whose
+ * geometry has moved far destroys and creates); hpt_multi_* and the scene the one-shot wrappers keep, which compare
+ * bytes and rebuild as before; pt_cli, whose loop has no notion of a scene over time. */
+typedef struct hpt_update_info {
+    uint64_t updates, live_tris, dead_tris;
+    double ms_pack, ms_upload, ms_refit;
+} hpt_update_info;
+int hpt_scene_update_triangles(hpt_scene *scene, const void *triangles, int num_triangles);
+int hpt_scene_update_rounds(hpt_scene *scene, const void *lights, int num_lights, const void *spheres, int num_spheres);
+int hpt_scene_update_check(const hpt_scene *scene, const void *triangles, int num_triangles);
+int hpt_scene_get_update_info(const hpt_scene *scene, hpt_update_info *out);
+int hpt_bvh_refit_host(const void *lights, int num_lights, const void *spheres, int num_spheres, const void *triangles,
+                       const void *new_triangles, int num_triangles, hpt_bvh_info *info,
+                       void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,11 @@ class BvhInfo(C.Structure):
                 ("qorigin", C.c_float * 3), ("qscale", C.c_float * 3)]
 
 
+class UpdateInfo(C.Structure):
+    _fields_ = [("updates", C.c_uint64), ("live_tris", C.c_uint64), ("dead_tris", C.c_uint64),
+                ("ms_pack", C.c_double), ("ms_upload", C.c_double), ("ms_refit", C.c_double)]
+
+
 # exported tree (include/hpt.h, hpt_bvh_info): 32-B quantised nodes as 8 uint32 words, 48-B triangles as 12 words
 QNODE_WORDS = 8
 TRI_WORDS = 12
@@ -173,7 +178,9 @@ def load_library() -> C.CDLL:
                      "hpt_render_guides_device", "hpt_history_create", "hpt_history_advance", "hpt_history_metrics",
                      "hpt_history_read", "hpt_history_reset", "hpt_history_check",
                      "hpt_denoiser_run_guided", "hpt_denoiser_estimate_variance", "hpt_history_length", "hpt_guided_check",
-                     "hpt_history_create_flags", "hpt_history_variance", "hpt_history_read_moments", "hpt_history_variance_check"):
+                     "hpt_history_create_flags", "hpt_history_variance", "hpt_history_read_moments", "hpt_history_variance_check",
+                     "hpt_scene_update_triangles", "hpt_scene_update_rounds", "hpt_scene_update_check", "hpt_scene_get_update_info",
+                     "hpt_bvh_refit_host"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -348,6 +355,29 @@ class Scene:
         """The tree this scene's device holds (include/hpt.h, hpt_scene_export_bvh): dict(info, qnodes [n, 8] uint32,
         tris [m, 12] uint32 words of the 48-B leaf-order records)."""
         return _export_bvh(lambda info, qn, qcap, tr, tcap: self._lib.hpt_scene_export_bvh(self._h, info, qn, qcap, tr, tcap))
+
+    # -- scene updates (include/hpt.h) -----------------------------------------------------
+    def update_triangles(self, triangles):
+        """Moves the scene's triangles in place: the same number of records, only their vertices changed.  The tree is
+        refitted on the device; every integrator renders the new scene afterwards.  Blocking."""
+        tr = np.ascontiguousarray(triangles, TRIANGLE)
+        _check(self._lib.hpt_scene_update_triangles(self._h, _vp(tr), len(tr)))
+
+    def update_rounds(self, lights, spheres):
+        """Replaces the lights and the spheres (same counts; sphere materials unchanged, any light field may change)."""
+        L = np.ascontiguousarray(lights, LIGHT)
+        sp = np.ascontiguousarray(spheres, SPHERE)
+        _check(self._lib.hpt_scene_update_rounds(self._h, _vp(L), len(L), _vp(sp), len(sp)))
+
+    def update_check(self, triangles):
+        """Raises HptError where update_triangles would refuse these records; no device work."""
+        update_check(self, triangles)
+
+    def update_info(self) -> dict:
+        """The last update_triangles: dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
+        info = UpdateInfo()
+        _check(self._lib.hpt_scene_get_update_info(self._h, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in info._fields_}
 
     # -- ray probes (tests) ---------------------------------------------------------------
     def trace_closest(self, origins, dirs, brute_force=False):
@@ -771,6 +801,28 @@ def export_bvh_host(lights, spheres, triangles) -> dict:
     triangles = np.ascontiguousarray(triangles, TRIANGLE)
     return _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_export_host(
         _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), len(triangles), info, qn, qcap, tr, tcap))
+
+
+def refit_bvh_host(lights, spheres, triangles, new_triangles) -> dict:
+    """The tree a scene created from `triangles` holds after update_triangles(new_triangles), computed on the host (no
+    device needed): the definition the device's refit is held to.  The keys of export_bvh_host."""
+    lib = load_library()
+    lights = np.ascontiguousarray(lights, LIGHT)
+    spheres = np.ascontiguousarray(spheres, SPHERE)
+    triangles = np.ascontiguousarray(triangles, TRIANGLE)
+    new_triangles = np.ascontiguousarray(new_triangles, TRIANGLE)
+    if len(new_triangles) != len(triangles):
+        raise HptError("hpt error 1: an update keeps the triangle count: %d triangles, %d were handed over" % (len(triangles), len(new_triangles)))
+    return _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_refit_host(
+        _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), _vp(new_triangles), len(triangles), info, qn, qcap, tr, tcap))
+
+
+def update_check(scene, triangles, num_triangles=None) -> None:
+    """hpt_scene_update_check: raises HptError for what Scene.update_triangles would refuse (scene may be None,
+    triangles may be None with a count given); touches no device."""
+    tr = np.ascontiguousarray(triangles, TRIANGLE) if triangles is not None else None
+    n = len(tr) if num_triangles is None else int(num_triangles)
+    _check(load_library().hpt_scene_update_check(scene._h if scene is not None else None, _vp(tr) if tr is not None else None, n))
 
 
 def probe_functions(records) -> np.ndarray:

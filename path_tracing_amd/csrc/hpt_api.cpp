@@ -267,7 +267,26 @@ int scene_upload(const HostScene &hs, const void *lights, int nl, const void *sp
     s->tm.stats.n_tris = (uint32_t) nt; s->tm.stats.n_materials = (uint32_t) hs.materials.size();
     s->tm.stats.ms_bvh_build = hs.ms_bvh_build;
     s->tm.stats.ms_upload = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    // what a refit needs (scene_update.cpp); it goes to the device with the first update
+    s->up.level_begin = hs.level_begin; s->up.wide_src = hs.wide_src; s->up.num_wide = (uint32_t) hs.wnodes.size();
+    s->up.sphere_material.resize((size_t) ns);
+    for(int i = 0; i < ns; ++i) s->up.sphere_material[(size_t) i] = hs.rounds[(size_t) i].material;
     *out = s;
+    return HPT_OK;
+}
+
+int export_host_tree(const HostScene &hs, hpt_bvh_info *info, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap){
+    info->num_nodes = (int32_t) hs.qnodes.size(); info->num_tris = (int32_t) hs.tris.size();
+    info->bvh_depth = hs.bvh_depth; info->num_rounds = hs.num_spheres + hs.num_lights;
+    for(int a = 0; a < 3; ++a){ info->qorigin[a] = hs.qorigin[a]; info->qscale[a] = hs.qscale[a]; }
+    if(qnodes_out){
+        if(qnodes_cap < hs.qnodes.size() * sizeof(QBvhNode)) return fail(HPT_ERR_INVALID, "qnodes_out too small");
+        memcpy(qnodes_out, hs.qnodes.data(), hs.qnodes.size() * sizeof(QBvhNode));
+    }
+    if(tris_out){
+        if(tris_cap < hs.tris.size() * sizeof(DevTriangle)) return fail(HPT_ERR_INVALID, "tris_out too small");
+        memcpy(tris_out, hs.tris.data(), hs.tris.size() * sizeof(DevTriangle));
+    }
     return HPT_OK;
 }
 
@@ -303,6 +322,8 @@ void hpt_scene_destroy(hpt_scene *s){
         if(s->ws.px_stream[k]) hipStreamDestroy(s->ws.px_stream[k]);
     }
     for(hipEvent_t e : s->pm.marks) hipEventDestroy(e);
+    if(s->up.ev_a) hipEventDestroy(s->up.ev_a);
+    if(s->up.ev_b) hipEventDestroy(s->up.ev_b);
     if(s->tm.ev_start) hipEventDestroy(s->tm.ev_start);
     if(s->tm.ev_stop) hipEventDestroy(s->tm.ev_stop);
     for(hipEvent_t e : s->tm.event_pool) hipEventDestroy(e);
@@ -519,18 +540,7 @@ int hpt_bvh_export_host(const void *lights, int nl, const void *spheres, int ns,
     HostScene hs;
     const char *err = build_host_scene(lights, nl, spheres, ns, tris, nt, hs);
     if(err && *err) return fail(HPT_ERR_INVALID, err);
-    info->num_nodes = (int32_t) hs.qnodes.size(); info->num_tris = (int32_t) hs.tris.size();
-    info->bvh_depth = hs.bvh_depth; info->num_rounds = ns + nl;
-    for(int a = 0; a < 3; ++a){ info->qorigin[a] = hs.qorigin[a]; info->qscale[a] = hs.qscale[a]; }
-    if(qnodes_out){
-        if(qnodes_cap < hs.qnodes.size() * sizeof(QBvhNode)) return fail(HPT_ERR_INVALID, "qnodes_out too small");
-        memcpy(qnodes_out, hs.qnodes.data(), hs.qnodes.size() * sizeof(QBvhNode));
-    }
-    if(tris_out){
-        if(tris_cap < hs.tris.size() * sizeof(DevTriangle)) return fail(HPT_ERR_INVALID, "tris_out too small");
-        memcpy(tris_out, hs.tris.data(), hs.tris.size() * sizeof(DevTriangle));
-    }
-    return HPT_OK;
+    return export_host_tree(hs, info, qnodes_out, qnodes_cap, tris_out, tris_cap);
 }
 
 int hpt_scene_export_bvh(const hpt_scene *s, hpt_bvh_info *info, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap){

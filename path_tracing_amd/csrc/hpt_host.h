@@ -1,5 +1,5 @@
 // Host side of libhpt.so, shared by its translation units (hpt_api.cpp, render_pt.cpp, render_bdpt.cpp, render_ppm.cpp,
-// denoise.cpp, hpt_multi.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
+// denoise.cpp, hpt_multi.cpp, scene_update.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
 // Internal and host only; compiled as HIP because it includes the launch interfaces.
 #pragma once
 #include "../../include/hpt.h"
@@ -8,6 +8,7 @@
 #include "bdpt_kernels.h"
 #include "ppm_kernels.h"
 #include "denoise_kernels.h"
+#include "refit_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -149,6 +150,21 @@ struct hpt_scene {
         hpt_ppm_stats stats{};
     } pm;
 
+    // scene updates (scene_update.cpp): what the build left for a refit, kept on the host until the first update, and
+    // the refit's scratch on the device, allocated by the first update and kept
+    struct Update {
+        std::vector<uint32_t> level_begin;           // levels of the breadth-first binary tree (HostScene::level_begin)
+        hpt::pod_vector<uint32_t> wide_src;          // four per wide node (HostScene::wide_src)
+        std::vector<uint32_t> sphere_material;       // material number of every sphere (the update does not re-intern)
+        uint32_t num_wide = 0;
+        bool ready = false;                          // d_wide_src holds wide_src
+        hpt::DevBuf<uint4> d_wide_src;
+        hpt::DevBuf<float> verts, slot_box, exact, partial, result;      // 9 / slot 6 / node 6 / block 6 floats; 6 floats + the dead count
+        std::vector<float> h_verts;
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;
+        hpt_update_info info{};
+    } up;
+
     // timing and statistics of the last render
     struct Timing {
         hipEvent_t ev_start = nullptr, ev_stop = nullptr;
@@ -226,6 +242,9 @@ struct LaunchTimer {        // brackets one launch with events when TIME_KERNELS
 inline bool same_bytes(const std::vector<unsigned char> &kept, const void *given, size_t bytes){
     return kept.size() == bytes && (bytes == 0 || memcmp(kept.data(), given, bytes) == 0);
 }
+
+// the arrays and the description hpt_bvh_export_host hands out, of a scene built (or refitted) on the host (hpt_api.cpp)
+int export_host_tree(const HostScene &hs, hpt_bvh_info *info, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);
 
 // hpt_multi.cpp: the fan-out kept by the one-shot wrappers is reused for byte-identical arrays
 bool multi_matches(const hpt_multi *m, int n_devices, const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt);

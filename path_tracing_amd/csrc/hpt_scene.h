@@ -101,6 +101,11 @@ struct HostScene {
     pod_vector<QBvhNode> qnodes;       // same tree, quantised boxes
     pod_vector<WideNode> wnodes;       // four-wide collapse of it (the resume launch's tree)
     int wide_depth = 0;
+    // what a refit needs besides the arrays (scene updates, include/hpt.h): per wide node and child the binary child its box
+    // is taken from (node * 2 + side, kEmptyChild for an absent child), and where each level of the breadth-first binary
+    // tree begins (level_begin[l] .. level_begin[l + 1]; the last entry is the node count)
+    pod_vector<uint32_t> wide_src;
+    std::vector<uint32_t> level_begin;
     float qorigin[3] = {0, 0, 0}, qscale[3] = {1, 1, 1};   // grid: coordinate = qorigin + q * qscale
     pod_vector<DevTriangle> tris;      // leaf order
     std::vector<DevRound> rounds;      // spheres, then light balls
@@ -144,6 +149,28 @@ const char *build_bdpt_host_scene(const void *lights, int nl, const void *sphere
 // Returns an empty string on success, an error message otherwise.
 const char *build_host_scene(const void *lights, int nl, const void *spheres, int ns,
                              const void *tris, int nt, HostScene &out);
+
+// ---- scene updates: the tree's topology is kept and everything that is a function of the vertex positions is recomputed ----
+
+// Spheres then light balls, and the light records, of a scene (build_host_scene and hpt_scene_update_rounds run these lines);
+// sphere_material[i] is the material number of sphere i.
+const char *flatten_rounds_host(const void *lights, int nl, const void *spheres, int ns, const uint32_t *sphere_material,
+                                std::vector<DevRound> &rounds, std::vector<DevLight> &lights_out);
+
+// The refusals of an update: "" when `tris` (nt records) may replace `kept` (kept_nt records) -- the same count and, in every
+// record, the same 84 bytes behind the vertices -- else the message (a literal or `msg`).  Likewise for the spheres' 84 bytes.
+const char *check_triangle_update(const void *kept, int kept_nt, const void *tris, int nt, char *msg, size_t msg_cap);
+const char *check_rounds_update(const void *kept_spheres, int kept_ns, int kept_nl, const void *lights, int nl, const void *spheres, int ns,
+                                char *msg, size_t msg_cap);
+
+// The definition of a refit: hs (built by build_host_scene from records that differ from `tris` in the vertices only) gets the
+// leaf records, node boxes, grid and both quantised trees of the new vertices; child codes, counts and depths stay.  The
+// device's refit (refit_kernels.hip) is held to these bytes.  dead_out: the number of triangles no ray can hit.
+const char *refit_host_scene(HostScene &hs, const void *tris, int nt, uint64_t *dead_out = nullptr);
+
+// the builder's lines the device's refit needs on the host between its launches
+float box_padding_of(const float scene_min[3], const float scene_max[3], int nt);                      // pad_abs of a scene box
+void grid_of_box(const float lo[3], const float hi[3], float qorigin[3], float qscale[3]);         // the 16-bit grid over a box
 
 } // namespace hpt
 

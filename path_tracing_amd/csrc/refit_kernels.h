@@ -1,0 +1,39 @@
+// Launch interface of the refit kernels (refit_kernels.hip): a live scene's tree refitted to new vertex positions on the
+// device (include/hpt.h, "scene updates").  The topology -- child codes, leaf slots, node and level counts -- is the
+// build's; everything that is a function of the vertices is recomputed, to the bytes of refit_host_scene
+// (scene_build.cpp), which is the definition.  All launches are one lane per element, plain streaming code.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace hpt {
+
+// the 16-bit grid of the quantised trees: coordinate = qorigin + q * qscale
+struct RefitGrid { float qorigin[3], qscale[3]; };
+
+constexpr int kRefitBlock = 256;
+inline uint32_t refit_blocks(uint32_t n){ return (n + (uint32_t) kRefitBlock - 1u) / (uint32_t) kRefitBlock; }
+
+// One lane per leaf slot: tris[slot] (3 x float4) gets v0, e1, e2 of input triangle `ordinal - num_rounds` out of verts (nine
+// floats per triangle, input order); ordinal, material and flags stay.  slot_box[slot] (6 floats: min, max) gets the
+// triangle's box, or an inverted box for a dead triangle (an edge component that is not finite).  partial[6 * block] gets
+// the block's live box; *dead_count grows by the block's dead triangles (one integer atomic per block; zeroed by the caller).
+void launch_refit_tris(hipStream_t s, const float *verts, float4 *tris, uint32_t num_tris, uint32_t num_rounds, float *slot_box,
+                       float *partial, uint32_t *dead_count);
+// one block: out6 = the union of `blocks` partial boxes (launch_refit_tris)
+void launch_refit_reduce(hipStream_t s, const float *partial, uint32_t blocks, float *out6);
+
+// One lane per node of [first, first + count), a level of the breadth-first tree whose deeper levels are done: the exact box
+// of a leaf child is the union of its slots' boxes (a dead slot is the point dead_at), of an inner child exact[child]; the
+// node stores each padded (pad_abs, then two float neighbours each way) and exact[node] (6 floats) gets their union.
+void launch_refit_level(hipStream_t s, float4 *nodes, uint32_t num_nodes, uint32_t first, uint32_t count, const float *slot_box,
+                        uint32_t num_tris, float *exact, float pad_abs, float dead_x, float dead_y, float dead_z);
+
+// one lane per binary node: qnodes[node] (2 x uint4) from the stored boxes of nodes[node] on the grid
+void launch_refit_quantise(hipStream_t s, const float4 *nodes, uint4 *qnodes, uint32_t num_nodes, RefitGrid grid);
+// one lane per four-wide node: words 0-11 from the stored boxes of the binary children wide_src[wide node] names
+// (node * 2 + side, 0xFFFFFFFF: absent); the child codes in words 12-15 stay
+void launch_refit_wide(hipStream_t s, const float4 *nodes, uint32_t num_nodes, uint4 *wnodes, const uint4 *wide_src, uint32_t num_wide,
+                       RefitGrid grid);
+
+} // namespace hpt

@@ -1,0 +1,237 @@
+// Refit kernels (refit_kernels.h): the builder's arithmetic on new vertex positions, to the bytes of refit_host_scene
+// (scene_build.cpp).  Every float expression is evaluated as written (-ffp-contract=off); min / max are the comparisons of
+// std::min / std::max, and the float neighbours are taken on the bit pattern, so nothing depends on a math library.
+#include "refit_kernels.h"
+
+#include <cmath>
+
+namespace hpt {
+namespace {
+
+constexpr uint32_t kLeaf = 0x80000000u, kEmpty = 0xFFFFFFFFu;
+
+__device__ __forceinline__ float min_f(float a, float b){ return b < a ? b : a; }      // std::min(a, b)
+__device__ __forceinline__ float max_f(float a, float b){ return a < b ? b : a; }      // std::max(a, b)
+
+// std::nextafter(x, -INFINITY) and (x, +INFINITY)
+__device__ __forceinline__ float next_down(float x){
+    if(x != x) return x;
+    if(x == 0.0f) return __uint_as_float(0x80000001u);
+    const uint32_t u = __float_as_uint(x);
+    if(u == 0xFF800000u) return x;
+    return __uint_as_float(x > 0.0f ? u - 1u : u + 1u);
+}
+__device__ __forceinline__ float next_up(float x){
+    if(x != x) return x;
+    if(x == 0.0f) return __uint_as_float(0x00000001u);
+    const uint32_t u = __float_as_uint(x);
+    if(u == 0x7F800000u) return x;
+    return __uint_as_float(x > 0.0f ? u + 1u : u - 1u);
+}
+
+__device__ __forceinline__ bool finite_f(float x){ return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+// a - b with the host's NaN: the builder's edges are computed by x86 SSE, where a NaN operand comes back quieted (the first
+// one when both are) and inf - inf is the negative default NaN; the device's subtraction is an addition of -b and would hand
+// out other sign bits.  Only the bytes of dead triangles' records depend on it (no ray hits one: hit_triangle rejects a NaN).
+__device__ __forceinline__ float sub_as_host(float a, float b){
+    if(a != a) return __uint_as_float(__float_as_uint(a) | 0x00400000u);
+    if(b != b) return __uint_as_float(__float_as_uint(b) | 0x00400000u);
+    const float r = a - b;
+    return r != r ? __uint_as_float(0xFFC00000u) : r;
+}
+
+struct DBox { float mn[3], mx[3]; };
+__device__ __forceinline__ void reset(DBox &b){ for(int a = 0; a < 3; ++a){ b.mn[a] = INFINITY; b.mx[a] = -INFINITY; } }
+__device__ __forceinline__ void grow(DBox &b, const DBox &o){ for(int a = 0; a < 3; ++a){ b.mn[a] = min_f(b.mn[a], o.mn[a]); b.mx[a] = max_f(b.mx[a], o.mx[a]); } }
+__device__ __forceinline__ void grow(DBox &b, float x, float y, float z){
+    b.mn[0] = min_f(b.mn[0], x); b.mx[0] = max_f(b.mx[0], x);
+    b.mn[1] = min_f(b.mn[1], y); b.mx[1] = max_f(b.mx[1], y);
+    b.mn[2] = min_f(b.mn[2], z); b.mx[2] = max_f(b.mx[2], z);
+}
+__device__ __forceinline__ DBox load_box(const float *p){
+    const float2 a = ((const float2 *) p)[0], b = ((const float2 *) p)[1], c = ((const float2 *) p)[2];
+    DBox r; r.mn[0] = a.x; r.mn[1] = a.y; r.mn[2] = b.x; r.mx[0] = b.y; r.mx[1] = c.x; r.mx[2] = c.y;
+    return r;
+}
+__device__ __forceinline__ void store_box(float *p, const DBox &b){
+    ((float2 *) p)[0] = make_float2(b.mn[0], b.mn[1]); ((float2 *) p)[1] = make_float2(b.mn[2], b.mx[0]); ((float2 *) p)[2] = make_float2(b.mx[1], b.mx[2]);
+}
+
+// the union of the block's boxes in lane 0's `b` (every lane of the block calls this)
+__device__ void block_union(DBox &b){
+    __shared__ float red[6][kRefitBlock];
+    const int t = (int) threadIdx.x;
+    for(int a = 0; a < 3; ++a){ red[a][t] = b.mn[a]; red[3 + a][t] = b.mx[a]; }
+    __syncthreads();
+    for(int w = kRefitBlock / 2; w > 0; w >>= 1){
+        if(t < w) for(int a = 0; a < 3; ++a){ red[a][t] = min_f(red[a][t], red[a][t + w]); red[3 + a][t] = max_f(red[3 + a][t], red[3 + a][t + w]); }
+        __syncthreads();
+    }
+    for(int a = 0; a < 3; ++a){ b.mn[a] = red[a][0]; b.mx[a] = red[3 + a][0]; }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kRefitBlock) void k_refit_tris(const float *__restrict__ verts, float4 *__restrict__ tris, uint32_t num_tris,
+                                                             uint32_t num_rounds, float *__restrict__ slot_box, float *__restrict__ partial,
+                                                             uint32_t *__restrict__ dead_count){
+    const uint32_t s = blockIdx.x * (uint32_t) kRefitBlock + threadIdx.x;
+    DBox box; reset(box);
+    int dead = 0;
+    if(s < num_tris){
+        const float4 r0 = tris[(size_t) s * 3], r1 = tris[(size_t) s * 3 + 1], r2 = tris[(size_t) s * 3 + 2];
+        const uint32_t idx = __float_as_uint(r0.w) - num_rounds;
+        bool live = idx < num_tris;           // (a slot's ordinal names an input triangle: anything else is not read)
+        float v[9];
+        if(live){
+            const float *p = verts + (size_t) idx * 9;
+            for(int k = 0; k < 9; ++k) v[k] = p[k];
+        } else for(int k = 0; k < 9; ++k) v[k] = NAN;
+        float e1[3], e2[3];
+        for(int a = 0; a < 3; ++a){ e1[a] = sub_as_host(v[3 + a], v[a]); e2[a] = sub_as_host(v[6 + a], v[a]); }
+        for(int a = 0; a < 3; ++a) live = live && finite_f(e1[a]) && finite_f(e2[a]);
+        tris[(size_t) s * 3] = make_float4(v[0], v[1], v[2], r0.w);
+        tris[(size_t) s * 3 + 1] = make_float4(e1[0], e1[1], e1[2], r1.w);
+        tris[(size_t) s * 3 + 2] = make_float4(e2[0], e2[1], e2[2], r2.w);
+        if(live){ grow(box, v[0], v[1], v[2]); grow(box, v[3], v[4], v[5]); grow(box, v[6], v[7], v[8]); }
+        else dead = 1;
+        store_box(slot_box + (size_t) s * 6, box);         // dead: inverted
+    }
+    const int block_dead = __syncthreads_count(dead);
+    block_union(box);
+    if(threadIdx.x == 0){
+        store_box(partial + (size_t) blockIdx.x * 6, box);
+        if(block_dead > 0) atomicAdd(dead_count, (uint32_t) block_dead);
+    }
+}
+
+__global__ __launch_bounds__(kRefitBlock) void k_refit_reduce(const float *__restrict__ partial, uint32_t blocks, float *__restrict__ out6){
+    DBox box; reset(box);
+    for(uint32_t i = threadIdx.x; i < blocks; i += (uint32_t) kRefitBlock) grow(box, load_box(partial + (size_t) i * 6));
+    block_union(box);
+    if(threadIdx.x == 0) store_box(out6, box);
+}
+
+__device__ __forceinline__ void padded(const DBox &b, float pad_abs, float4 &mn, float4 &mx){
+    float lo[3], hi[3];
+    for(int a = 0; a < 3; ++a){
+        lo[a] = next_down(next_down(b.mn[a] - pad_abs));
+        hi[a] = next_up(next_up(b.mx[a] + pad_abs));
+    }
+    mn.x = lo[0]; mn.y = lo[1]; mn.z = lo[2]; mx.x = hi[0]; mx.y = hi[1]; mx.z = hi[2];
+}
+
+__global__ __launch_bounds__(kRefitBlock) void k_refit_level(float4 *__restrict__ nodes, uint32_t num_nodes, uint32_t first, uint32_t count,
+                                                              const float *__restrict__ slot_box, uint32_t num_tris, float *__restrict__ exact,
+                                                              float pad_abs, float dead_x, float dead_y, float dead_z){
+    const uint32_t k = blockIdx.x * (uint32_t) kRefitBlock + threadIdx.x;
+    if(k >= count || first + k >= num_nodes) return;
+    const uint32_t i = first + k;
+    float4 n[4];
+    for(int q = 0; q < 4; ++q) n[q] = nodes[(size_t) i * 4 + q];
+    DBox both; reset(both);
+    for(int side = 0; side < 2; ++side){
+        const uint32_t code = __float_as_uint(side ? n[1].w : n[0].w);
+        if(code == kEmpty) continue;                       // keeps its inverted box
+        DBox cb;
+        if(code & kLeaf){
+            reset(cb);
+            const uint32_t s0 = (code & ~kLeaf) >> 3, c = (code & 7u) + 1u;
+            for(uint32_t s = s0; s < s0 + c && s < num_tris; ++s){
+                DBox sb = load_box(slot_box + (size_t) s * 6);
+                if(!(sb.mn[0] <= sb.mx[0])){ sb.mn[0] = sb.mx[0] = dead_x; sb.mn[1] = sb.mx[1] = dead_y; sb.mn[2] = sb.mx[2] = dead_z; }
+                grow(cb, sb);
+            }
+        } else {
+            if(code >= num_nodes) continue;
+            cb = load_box(exact + (size_t) code * 6);
+        }
+        padded(cb, pad_abs, n[side * 2], n[side * 2 + 1]);
+        grow(both, cb);
+    }
+    for(int q = 0; q < 4; ++q) nodes[(size_t) i * 4 + q] = n[q];
+    store_box(exact + (size_t) i * 6, both);
+}
+
+// the host's qlo / qhi (scene_build.cpp, grid_lo / grid_hi): the same comparisons, so a NaN lands on 0 here too
+__device__ __forceinline__ uint32_t grid_lo(float v, float origin, float scale){
+    const double q = floor(((double) v - (double) origin) / (double) scale) - 1.0;
+    const double m = 0.0 < q ? q : 0.0;
+    return (uint32_t) (m < 65535.0 ? m : 65535.0);
+}
+__device__ __forceinline__ uint32_t grid_hi(float v, float origin, float scale){
+    const double q = ceil(((double) v - (double) origin) / (double) scale) + 1.0;
+    const double m = 0.0 < q ? q : 0.0;
+    return (uint32_t) (m < 65535.0 ? m : 65535.0);
+}
+
+__global__ __launch_bounds__(kRefitBlock) void k_refit_quantise(const float4 *__restrict__ nodes, uint4 *__restrict__ qnodes, uint32_t num_nodes,
+                                                                 RefitGrid g){
+    const uint32_t i = blockIdx.x * (uint32_t) kRefitBlock + threadIdx.x;
+    if(i >= num_nodes) return;
+    float4 n[4];
+    for(int q = 0; q < 4; ++q) n[q] = nodes[(size_t) i * 4 + q];
+    const uint32_t left = __float_as_uint(n[0].w), right = __float_as_uint(n[1].w);
+    const float lmin[3] = { n[0].x, n[0].y, n[0].z }, lmax[3] = { n[1].x, n[1].y, n[1].z };
+    const float rmin[3] = { n[2].x, n[2].y, n[2].z }, rmax[3] = { n[3].x, n[3].y, n[3].z };
+    uint32_t w[6];
+    for(int a = 0; a < 3; ++a){
+        uint32_t ll = 65535u, lh = 0u, rl = 65535u, rh = 0u;
+        if(left != kEmpty){ ll = grid_lo(lmin[a], g.qorigin[a], g.qscale[a]); lh = grid_hi(lmax[a], g.qorigin[a], g.qscale[a]); }
+        if(right != kEmpty){ rl = grid_lo(rmin[a], g.qorigin[a], g.qscale[a]); rh = grid_hi(rmax[a], g.qorigin[a], g.qscale[a]); }
+        w[2 * a] = ll | (rl << 16); w[2 * a + 1] = lh | (rh << 16);
+    }
+    qnodes[(size_t) i * 2] = make_uint4(w[0], w[1], w[2], w[3]);
+    qnodes[(size_t) i * 2 + 1] = make_uint4(w[4], w[5], left, right);
+}
+
+__global__ __launch_bounds__(kRefitBlock) void k_refit_wide(const float4 *__restrict__ nodes, uint32_t num_nodes, uint4 *__restrict__ wnodes,
+                                                             const uint4 *__restrict__ wide_src, uint32_t num_wide, RefitGrid g){
+    const uint32_t i = blockIdx.x * (uint32_t) kRefitBlock + threadIdx.x;
+    if(i >= num_wide) return;
+    const uint4 s4 = wide_src[i];
+    const uint32_t src[4] = { s4.x, s4.y, s4.z, s4.w };
+    uint32_t lo[3][4], hi[3][4];
+    for(int k = 0; k < 4; ++k){
+        if(src[k] != kEmpty && (src[k] >> 1) < num_nodes){
+            const size_t at = (size_t) (src[k] >> 1) * 4 + (size_t) (src[k] & 1u) * 2;
+            const float4 mn = nodes[at], mx = nodes[at + 1];
+            const float fmn[3] = { mn.x, mn.y, mn.z }, fmx[3] = { mx.x, mx.y, mx.z };
+            for(int a = 0; a < 3; ++a){ lo[a][k] = grid_lo(fmn[a], g.qorigin[a], g.qscale[a]); hi[a][k] = grid_hi(fmx[a], g.qorigin[a], g.qscale[a]); }
+        } else { for(int a = 0; a < 3; ++a){ lo[a][k] = 65535u; hi[a][k] = 0u; } }
+    }
+    for(int a = 0; a < 3; ++a)
+        wnodes[(size_t) i * 4 + a] = make_uint4(lo[a][0] | (lo[a][1] << 16), lo[a][2] | (lo[a][3] << 16), hi[a][0] | (hi[a][1] << 16), hi[a][2] | (hi[a][3] << 16));
+}
+
+} // namespace
+
+void launch_refit_tris(hipStream_t s, const float *verts, float4 *tris, uint32_t num_tris, uint32_t num_rounds, float *slot_box,
+                       float *partial, uint32_t *dead_count){
+    if(num_tris == 0) return;
+    hipLaunchKernelGGL(k_refit_tris, dim3(refit_blocks(num_tris)), dim3(kRefitBlock), 0, s, verts, tris, num_tris, num_rounds, slot_box, partial, dead_count);
+}
+
+void launch_refit_reduce(hipStream_t s, const float *partial, uint32_t blocks, float *out6){
+    hipLaunchKernelGGL(k_refit_reduce, dim3(1), dim3(kRefitBlock), 0, s, partial, blocks, out6);
+}
+
+void launch_refit_level(hipStream_t s, float4 *nodes, uint32_t num_nodes, uint32_t first, uint32_t count, const float *slot_box,
+                        uint32_t num_tris, float *exact, float pad_abs, float dead_x, float dead_y, float dead_z){
+    if(count == 0) return;
+    hipLaunchKernelGGL(k_refit_level, dim3(refit_blocks(count)), dim3(kRefitBlock), 0, s, nodes, num_nodes, first, count, slot_box, num_tris, exact,
+                       pad_abs, dead_x, dead_y, dead_z);
+}
+
+void launch_refit_quantise(hipStream_t s, const float4 *nodes, uint4 *qnodes, uint32_t num_nodes, RefitGrid grid){
+    if(num_nodes == 0) return;
+    hipLaunchKernelGGL(k_refit_quantise, dim3(refit_blocks(num_nodes)), dim3(kRefitBlock), 0, s, nodes, qnodes, num_nodes, grid);
+}
+
+void launch_refit_wide(hipStream_t s, const float4 *nodes, uint32_t num_nodes, uint4 *wnodes, const uint4 *wide_src, uint32_t num_wide,
+                       RefitGrid grid){
+    if(num_wide == 0) return;
+    hipLaunchKernelGGL(k_refit_wide, dim3(refit_blocks(num_wide)), dim3(kRefitBlock), 0, s, nodes, num_nodes, wnodes, wide_src, num_wide, grid);
+}
+
+} // namespace hpt

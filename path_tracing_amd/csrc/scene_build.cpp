@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -139,6 +140,17 @@ void parallel_chunks(size_t n, F fn){
     while(job->done.load(std::memory_order_acquire) < kChunks) std::this_thread::yield();
 }
 
+// What a node stores for a child whose triangles span `b`: padded by an absolute slack plus two ulps so that rounding in the
+// slab test and in Moeller-Trumbore can never cull a hit the brute-force scan accepts
+void write_padded_box(float *mn, float *mx, const Box &b, float pad_abs){
+    for(int a = 0; a < 3; ++a){
+        float lo = b.mn[a] - pad_abs, hi = b.mx[a] + pad_abs;
+        lo = std::nextafter(std::nextafter(lo, -INFINITY), -INFINITY);
+        hi = std::nextafter(std::nextafter(hi, INFINITY), INFINITY);
+        mn[a] = lo; mx[a] = hi;
+    }
+}
+
 struct Builder {
     pod_vector<Prim> prims;
     pod_vector<BvhNode> nodes;        // pre-sized by the caller; slots are handed out by next_node
@@ -162,16 +174,7 @@ struct Builder {
     static int parallel_levels(){ int l = 0; while((2 << l) <= usable_cpus() && l < 6) ++l; return l; }     // 2^levels subtree threads at most
     static constexpr size_t kBigNode = 131072;        // nodes this large bin and partition their range on several threads
 
-    void write_box(float *mn, float *mx, const Box &b) const {
-        // pad by an absolute slack plus two ulps so that rounding in the slab test and in
-        // Moeller-Trumbore can never cull a hit the brute-force scan accepts
-        for(int a = 0; a < 3; ++a){
-            float lo = b.mn[a] - pad_abs, hi = b.mx[a] + pad_abs;
-            lo = std::nextafter(std::nextafter(lo, -INFINITY), -INFINITY);
-            hi = std::nextafter(std::nextafter(hi, INFINITY), INFINITY);
-            mn[a] = lo; mx[a] = hi;
-        }
-    }
+    void write_box(float *mn, float *mx, const Box &b) const { write_padded_box(mn, mx, b, pad_abs); }
 
     uint32_t make_leaf(int first, int count){
         // canonical leaf order: by input index (a leaf holds 8 triangles at most: insertion sort)
@@ -396,29 +399,161 @@ void normalize3(const float *v, float s, float *out){
     out[0] = x / len; out[1] = y / len; out[2] = z / len;
 }
 
+// ---- the steps of a build that are functions of the vertex positions alone: the builder and the refit run these lines ----
+
+// Dead triangles.  A record whose edge v1 - v0 or v2 - v0 has a component that is not finite -- a NaN or infinite
+// coordinate, or two finite ones whose difference overflows -- is hit by no ray: in hit_triangle (pt_device_math.h; the
+// reference's geometric.cuh:261-291) the determinant a = dot(e1, cross(rd, e2)) is then infinite or NaN, f = 1 / a is 0 or
+// NaN, and t = f * (...) is 0 or NaN, which `t > kEps` rejects.  Such a record keeps its leaf slot (the slots are a
+// permutation of the input; the scan kernels index them) but must not reach a box, pad_abs or the grid, where one
+// infinity makes every plane NaN and every ray visit every node: it enters the build as a point at the low corner of the
+// live triangles' box (the origin when there is none).
+// set(i, box, live) is called once for every input triangle (from several threads), and once more for every dead one when
+// its point is known; scene_box comes back as the box of what was set last.  Returns the number of dead triangles.
+template <typename Set>
+size_t triangle_boxes(const RefTriangle *tris, int nt, Box &scene_box, Set set){
+    scene_box.reset();
+    std::vector<Box> part((size_t) kChunks);
+    std::vector<std::vector<uint32_t>> dead((size_t) kChunks);          // input indices of the dead triangles, per chunk
+    for(Box &b : part) b.reset();
+    parallel_chunks((size_t) nt, [&](int c, size_t b0, size_t e0){
+        for(size_t i = b0; i < e0; ++i){
+            const RefTriangle &t = tris[i];
+            bool live = true;
+            for(int a = 0; a < 3; ++a) live = live && std::isfinite(t.v1[a] - t.v0[a]) && std::isfinite(t.v2[a] - t.v0[a]);
+            Box box;
+            if(!live){
+                // placed below, once the live triangles' box is known
+                for(int a = 0; a < 3; ++a) box.mn[a] = box.mx[a] = 0.0f;
+                set(i, box, false);
+                dead[(size_t) c].push_back((uint32_t) i);
+                continue;
+            }
+            box.reset();
+            box.grow(t.v0); box.grow(t.v1); box.grow(t.v2);
+            set(i, box, true);
+            part[(size_t) c].grow(box);
+        }
+    });
+    for(const Box &b : part) scene_box.grow(b);
+    size_t ndead = 0; for(const std::vector<uint32_t> &d : dead) ndead += d.size();
+    if(ndead > 0){
+        Box at;
+        for(int a = 0; a < 3; ++a) at.mn[a] = at.mx[a] = ndead < (size_t) nt ? scene_box.mn[a] : 0.0f;
+        for(const std::vector<uint32_t> &d : dead) for(uint32_t i : d) set(i, at, false);
+        scene_box.grow(at.mn);
+    }
+    return ndead;
+}
+
+// the absolute slack of every stored box (write_padded_box)
+float box_padding(const Box &scene_box, int nt){
+    float extent = 0.0f;
+    if(nt > 0) for(int a = 0; a < 3; ++a){
+        extent = std::max(extent, scene_box.mx[a] - scene_box.mn[a]);
+        extent = std::max(extent, std::max(std::fabs(scene_box.mn[a]), std::fabs(scene_box.mx[a])));
+    }
+    return 2e-6f * extent;
+}
+
+inline void triangle_geometry(DevTriangle &d, const RefTriangle &t){
+    for(int a = 0; a < 3; ++a){
+        d.v0[a] = t.v0[a];
+        d.e1[a] = t.v1[a] - t.v0[a];          // geometric.cuh:266-267
+        d.e2[a] = t.v2[a] - t.v0[a];
+    }
+}
+
+// grid coordinates of a stored plane (double precision; a NaN lands on 0)
+inline uint32_t grid_lo(float v, float origin, float scale){ double q = std::floor(((double) v - (double) origin) / (double) scale) - 1.0; return (uint32_t) std::min(65535.0, std::max(0.0, q)); }
+inline uint32_t grid_hi(float v, float origin, float scale){ double q = std::ceil(((double) v - (double) origin) / (double) scale) + 1.0; return (uint32_t) std::min(65535.0, std::max(0.0, q)); }
+
+// quantised twin: 16-bit grid over the union of the (padded) node boxes of hs.nodes; fills qorigin, qscale and qnodes
+void quantise_tree(HostScene &hs){
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    {   std::vector<Box> part((size_t) kChunks);
+        for(Box &b : part) b.reset();
+        parallel_chunks(hs.nodes.size(), [&](int c, size_t b0, size_t e0){
+            Box &pb = part[(size_t) c];
+            for(size_t i = b0; i < e0; ++i){
+                const BvhNode &n = hs.nodes[i];
+                if(n.left != kEmptyChild){ pb.grow(n.lmin); pb.grow(n.lmax); }
+                if(n.right != kEmptyChild){ pb.grow(n.rmin); pb.grow(n.rmax); }
+            }
+        });
+        for(const Box &b : part) for(int a = 0; a < 3; ++a){ lo[a] = std::min(lo[a], b.mn[a]); hi[a] = std::max(hi[a], b.mx[a]); }
+    }
+    grid_of_box(lo, hi, hs.qorigin, hs.qscale);
+    hs.qnodes.resize(hs.nodes.size());
+    parallel_chunks(hs.nodes.size(), [&](int, size_t b0, size_t e0){
+        for(size_t i = b0; i < e0; ++i){
+            const BvhNode &n = hs.nodes[i]; QBvhNode &q = hs.qnodes[i];
+            for(int a = 0; a < 3; ++a){
+                const float o = hs.qorigin[a], sc = hs.qscale[a];
+                if(n.left != kEmptyChild){ q.plane[a][0][0] = (uint16_t) grid_lo(n.lmin[a], o, sc); q.plane[a][1][0] = (uint16_t) grid_hi(n.lmax[a], o, sc); } else { q.plane[a][0][0] = 65535; q.plane[a][1][0] = 0; }
+                if(n.right != kEmptyChild){ q.plane[a][0][1] = (uint16_t) grid_lo(n.rmin[a], o, sc); q.plane[a][1][1] = (uint16_t) grid_hi(n.rmax[a], o, sc); } else { q.plane[a][0][1] = 65535; q.plane[a][1][1] = 0; }
+            }
+            q.left = n.left; q.right = n.right;
+        }
+    });
+}
+
+// four-wide twin, boxes: words 0-11 of every wide node from the stored box of the binary child each of its four children was
+// collapsed from (hs.wide_src, recorded by the build), on the grid of quantise_tree; the child codes (words 12-15) are the build's
+void pack_wide_boxes(HostScene &hs){
+    parallel_chunks(hs.wnodes.size(), [&](int, size_t b0, size_t e0){
+        for(size_t qi = b0; qi < e0; ++qi){
+            WideNode &w = hs.wnodes[qi];
+            uint32_t lo[3][4], hi[3][4];
+            for(int k = 0; k < 4; ++k){
+                const uint32_t src = hs.wide_src[qi * 4 + (size_t) k];
+                if(src != kEmptyChild){
+                    const BvhNode &b = hs.nodes[src >> 1];
+                    const float *mn = (src & 1u) ? b.rmin : b.lmin, *mx = (src & 1u) ? b.rmax : b.lmax;
+                    for(int a = 0; a < 3; ++a){ lo[a][k] = grid_lo(mn[a], hs.qorigin[a], hs.qscale[a]); hi[a][k] = grid_hi(mx[a], hs.qorigin[a], hs.qscale[a]); }
+                }
+                else { for(int a = 0; a < 3; ++a){ lo[a][k] = 65535u; hi[a][k] = 0u; } }
+            }
+            for(int a = 0; a < 3; ++a){
+                w.w[a * 4 + 0] = lo[a][0] | (lo[a][1] << 16); w.w[a * 4 + 1] = lo[a][2] | (lo[a][3] << 16);
+                w.w[a * 4 + 2] = hi[a][0] | (hi[a][1] << 16); w.w[a * 4 + 3] = hi[a][2] | (hi[a][3] << 16);
+            }
+        }
+    });
+}
+
 } // namespace
 
-const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v, int ns,
-                             const void *tris_v, int nt, HostScene &hs){
-    if(nl < 0 || ns < 0 || nt < 0) return "negative primitive count";
-    if((nl > 0 && !lights_v) || (ns > 0 && !spheres_v) || (nt > 0 && !tris_v)) return "null primitive array";
-    if((uint64_t) nt >= (1ull << 28)) return "too many triangles (limit 2^28)";
+void grid_of_box(const float lo_in[3], const float hi_in[3], float qorigin[3], float qscale[3]){
+    for(int a = 0; a < 3; ++a){
+        float lo = lo_in[a], hi = hi_in[a];
+        if(!(lo <= hi)){ lo = 0.0f; hi = 1.0f; }
+        qorigin[a] = lo;
+        float ext = hi - lo;
+        qscale[a] = ext > 0.0f ? ext / 65535.0f : 1.0f;
+        qscale[a] = std::nextafter(qscale[a], INFINITY);          // never shorter than the box
+    }
+}
+
+float box_padding_of(const float scene_min[3], const float scene_max[3], int nt){
+    Box b; for(int a = 0; a < 3; ++a){ b.mn[a] = scene_min[a]; b.mx[a] = scene_max[a]; }
+    return box_padding(b, nt);
+}
+
+const char *flatten_rounds_host(const void *lights_v, int nl, const void *spheres_v, int ns, const uint32_t *sphere_material,
+                                std::vector<DevRound> &rounds, std::vector<DevLight> &lights_out){
+    if(nl < 0 || ns < 0) return "negative primitive count";
+    if((nl > 0 && !lights_v) || (ns > 0 && (!spheres_v || !sphere_material))) return "null primitive array";
     const RefLight *lights = (const RefLight *) lights_v;
     const RefSphere *spheres = (const RefSphere *) spheres_v;
-    const RefTriangle *tris = (const RefTriangle *) tris_v;
-
-    hs = HostScene();
-    hs.num_spheres = ns; hs.num_lights = nl; hs.num_tris = nt;
-    std::map<MatKey, uint32_t> mat_table;
-
     // spheres then light balls: the reference's closest-hit scan order (geometric.cuh:340-368)
-    hs.rounds.reserve((size_t) ns + nl);
+    rounds.clear(); rounds.reserve((size_t) ns + nl);
     for(int i = 0; i < ns; ++i){
         DevRound r; memset(&r, 0, sizeof r);
         r.c[0] = spheres[i].c[0]; r.c[1] = spheres[i].c[1]; r.c[2] = spheres[i].c[2]; r.r = spheres[i].r;
-        r.material = intern_material(spheres[i].m, mat_table, hs.materials);
+        r.material = sphere_material[i];
         r.flags = (spheres[i].m.eta <= 0.0f) ? 1u : 0u;
-        hs.rounds.push_back(r);
+        rounds.push_back(r);
     }
     for(int i = 0; i < nl; ++i){
         DevRound r; memset(&r, 0, sizeof r);
@@ -426,9 +561,9 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
         r.c[0] = b.c[0]; r.c[1] = b.c[1]; r.c[2] = b.c[2]; r.r = b.r;
         r.material = (uint32_t) i;
         r.flags = 2u;
-        hs.rounds.push_back(r);
+        rounds.push_back(r);
     }
-    hs.lights.reserve(nl);
+    lights_out.clear(); lights_out.reserve(nl);
     for(int i = 0; i < nl; ++i){
         const RefLight &L = lights[i];
         DevLight d; memset(&d, 0, sizeof d);
@@ -444,7 +579,103 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
         d.area = 4.0f * kPi * L.ball.r * L.ball.r;    // pt_cu.cu:70,179
         d.is_parallel = L.is_parallel ? 1u : 0u;
         d.cone_ratio = (1.0f - d.cos_cutoff) / 2.0f;  // pt_cu.cu:73
-        hs.lights.push_back(d);
+        lights_out.push_back(d);
+    }
+    return "";
+}
+
+const char *check_triangle_update(const void *kept_v, int kept_nt, const void *tris_v, int nt, char *msg, size_t msg_cap){
+    if(nt < 0) return "negative triangle count";
+    if(nt != kept_nt){ snprintf(msg, msg_cap, "an update keeps the triangle count: the scene has %d triangles, %d were handed over", kept_nt, nt); return msg; }
+    if(nt > 0 && !tris_v) return "null triangle array";
+    const RefTriangle *kept = (const RefTriangle *) kept_v, *tris = (const RefTriangle *) tris_v;
+    for(int i = 0; i < nt; ++i)
+        if(memcmp(&kept[i].o, &tris[i].o, sizeof(RefTriangle) - offsetof(RefTriangle, o)) != 0){
+            snprintf(msg, msg_cap, "an update moves vertices only: material or id bytes of triangle %d differ from the record the scene was created from", i);
+            return msg;
+        }
+    return "";
+}
+
+const char *check_rounds_update(const void *kept_spheres_v, int kept_ns, int kept_nl, const void *lights_v, int nl, const void *spheres_v, int ns,
+                                char *msg, size_t msg_cap){
+    if(nl < 0 || ns < 0) return "negative primitive count";
+    if(nl != kept_nl || ns != kept_ns){ snprintf(msg, msg_cap, "an update keeps the counts: the scene has %d lights and %d spheres, %d and %d were handed over", kept_nl, kept_ns, nl, ns); return msg; }
+    if((nl > 0 && !lights_v) || (ns > 0 && !spheres_v)) return "null primitive array";
+    const RefSphere *kept = (const RefSphere *) kept_spheres_v, *spheres = (const RefSphere *) spheres_v;
+    for(int i = 0; i < ns; ++i)
+        if(memcmp(&kept[i].o, &spheres[i].o, sizeof(RefSphere) - offsetof(RefSphere, o)) != 0){
+            snprintf(msg, msg_cap, "an update moves spheres only: material or id bytes of sphere %d differ from the record the scene was created from", i);
+            return msg;
+        }
+    return "";
+}
+
+const char *refit_host_scene(HostScene &hs, const void *tris_v, int nt, uint64_t *dead_out){
+    if(nt != hs.num_tris) return "an update keeps the triangle count";
+    if(nt > 0 && !tris_v) return "null triangle array";
+    if(hs.level_begin.size() < 2 || hs.wide_src.size() != hs.wnodes.size() * 4) return "internal error: the scene keeps no refit tables";
+    const RefTriangle *tris = (const RefTriangle *) tris_v;
+    const uint32_t num_rounds = (uint32_t) (hs.num_spheres + hs.num_lights);
+    // 1. liveness and boxes per triangle, input order
+    pod_vector<Box> tb((size_t) nt);
+    Box scene_box;
+    const size_t ndead = triangle_boxes(tris, nt, scene_box, [&](size_t i, const Box &b, bool){ tb[i] = b; });
+    if(dead_out) *dead_out = ndead;
+    const float pad_abs = box_padding(scene_box, nt);
+    // 2. the leaf-order records: a slot keeps its triangle (ordinal, material, flags)
+    parallel_chunks((size_t) nt, [&](int, size_t b0, size_t e0){
+        for(size_t s = b0; s < e0; ++s) triangle_geometry(hs.tris[s], tris[hs.tris[s].ordinal - num_rounds]);
+    });
+    // 3. node boxes, deepest level first (children sit behind their parents): a child's exact box is the union of its
+    // triangles' boxes, what the node stores is that box padded -- never a padded box padded again
+    pod_vector<Box> exact(hs.nodes.size());
+    for(size_t l = hs.level_begin.size() - 1; l-- > 0; ){
+        const size_t first = hs.level_begin[l], cnt = hs.level_begin[l + 1] - first;
+        parallel_chunks(cnt, [&](int, size_t b0, size_t e0){
+            for(size_t i = first + b0; i < first + e0; ++i){
+                BvhNode &n = hs.nodes[i];
+                Box both; both.reset();
+                for(int side = 0; side < 2; ++side){
+                    const uint32_t code = side ? n.right : n.left;
+                    float *mn = side ? n.rmin : n.lmin, *mx = side ? n.rmax : n.lmax;
+                    if(code == kEmptyChild){ set_empty_box(mn, mx); continue; }
+                    Box cb;
+                    if(code & kLeafFlag){
+                        cb.reset();
+                        const uint32_t s0 = (code & ~kLeafFlag) >> 3, c = (code & 7u) + 1u;
+                        for(uint32_t s = s0; s < s0 + c; ++s) cb.grow(tb[hs.tris[s].ordinal - num_rounds]);
+                    } else cb = exact[code];
+                    write_padded_box(mn, mx, cb, pad_abs);
+                    both.grow(cb);
+                }
+                exact[i] = both;
+            }
+        });
+    }
+    // 4. the grid and the two quantised trees
+    quantise_tree(hs);
+    pack_wide_boxes(hs);
+    return "";
+}
+
+const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v, int ns,
+                             const void *tris_v, int nt, HostScene &hs){
+    if(nl < 0 || ns < 0 || nt < 0) return "negative primitive count";
+    if((nl > 0 && !lights_v) || (ns > 0 && !spheres_v) || (nt > 0 && !tris_v)) return "null primitive array";
+    if((uint64_t) nt >= (1ull << 28)) return "too many triangles (limit 2^28)";
+    const RefSphere *spheres = (const RefSphere *) spheres_v;
+    const RefTriangle *tris = (const RefTriangle *) tris_v;
+
+    hs = HostScene();
+    hs.num_spheres = ns; hs.num_lights = nl; hs.num_tris = nt;
+    std::map<MatKey, uint32_t> mat_table;
+
+    {   // spheres take the first material numbers, in input order
+        std::vector<uint32_t> sphere_material((size_t) ns);
+        for(int i = 0; i < ns; ++i) sphere_material[(size_t) i] = intern_material(spheres[i].m, mat_table, hs.materials);
+        const char *e = flatten_rounds_host(lights_v, nl, spheres_v, ns, sphere_material.data(), hs.rounds, hs.lights);
+        if(e && *e) return e;
     }
 
     auto t0 = std::chrono::steady_clock::now();
@@ -459,54 +690,15 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
     if(const char *e = getenv("HPT_MAX_LEAF")){ int v = atoi(e); if(v >= 1 && v <= 8) B.max_leaf = v; }
 #endif
     B.prims.resize(nt);
-    // Dead triangles.  A record whose edge v1 - v0 or v2 - v0 has a component that is not finite -- a NaN or infinite
-    // coordinate, or two finite ones whose difference overflows -- is hit by no ray: in hit_triangle (pt_device_math.h; the
-    // reference's geometric.cuh:261-291) the determinant a = dot(e1, cross(rd, e2)) is then infinite or NaN, f = 1 / a is 0 or
-    // NaN, and t = f * (...) is 0 or NaN, which `t > kEps` rejects.  Such a record keeps its leaf slot (the slots are a
-    // permutation of the input; the scan kernels index them) but must not reach a box, pad_abs or the grid, where one
-    // infinity makes every plane NaN and every ray visit every node: it enters the build as a point at the low corner of the
-    // live triangles' box (the origin when there is none).
-    Box scene_box; scene_box.reset();
-    {   std::vector<Box> part((size_t) kChunks);
-        std::vector<std::vector<uint32_t>> dead((size_t) kChunks);          // input indices of the dead triangles, per chunk
-        for(Box &b : part) b.reset();
-        parallel_chunks((size_t) nt, [&](int c, size_t b0, size_t e0){
-            for(size_t i = b0; i < e0; ++i){
-                Prim &p = B.prims[i];
-                const RefTriangle &t = tris[i];
-                p.index = (uint32_t) i;
-                bool live = true;
-                for(int a = 0; a < 3; ++a) live = live && std::isfinite(t.v1[a] - t.v0[a]) && std::isfinite(t.v2[a] - t.v0[a]);
-                if(!live){
-                    // placed below, once the live triangles' box is known
-                    for(int a = 0; a < 3; ++a) p.box.mn[a] = p.box.mx[a] = p.cen[a] = 0.0f;
-                    dead[(size_t) c].push_back((uint32_t) i);
-                    continue;
-                }
-                p.box.reset();
-                p.box.grow(t.v0); p.box.grow(t.v1); p.box.grow(t.v2);
-                for(int a = 0; a < 3; ++a) p.cen[a] = 0.5f * (p.box.mn[a] + p.box.mx[a]);
-                part[(size_t) c].grow(p.box);
-            }
-        });
-        for(const Box &b : part) scene_box.grow(b);
-        size_t ndead = 0; for(const std::vector<uint32_t> &d : dead) ndead += d.size();
-        if(ndead > 0){
-            float at[3];
-            for(int a = 0; a < 3; ++a) at[a] = ndead < (size_t) nt ? scene_box.mn[a] : 0.0f;
-            for(const std::vector<uint32_t> &d : dead) for(uint32_t i : d){
-                Prim &p = B.prims[i];
-                for(int a = 0; a < 3; ++a) p.box.mn[a] = p.box.mx[a] = p.cen[a] = at[a];
-            }
-            scene_box.grow(at);
-        }
-    }
-    float extent = 0.0f;
-    if(nt > 0) for(int a = 0; a < 3; ++a){
-        extent = std::max(extent, scene_box.mx[a] - scene_box.mn[a]);
-        extent = std::max(extent, std::max(std::fabs(scene_box.mn[a]), std::fabs(scene_box.mx[a])));
-    }
-    B.pad_abs = 2e-6f * extent;
+    // (dead triangles enter as a point: triangle_boxes)
+    Box scene_box;
+    triangle_boxes(tris, nt, scene_box, [&](size_t i, const Box &b, bool live){
+        Prim &p = B.prims[i];
+        p.index = (uint32_t) i;
+        p.box = b;
+        for(int a = 0; a < 3; ++a) p.cen[a] = live ? 0.5f * (b.mn[a] + b.mx[a]) : b.mn[a];
+    });
+    B.pad_abs = box_padding(scene_box, nt);
     B.nodes.resize((nt > 0 ? (size_t) nt : 1) + Builder::kSlotSlack);          // an inner node has two non-empty subtrees: fewer than nt of them
     lap("prims");
 
@@ -542,6 +734,7 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
         size_t lvl_begin = 0, lvl_end = 1;
         order[0] = 0u;
         while(lvl_begin < lvl_end){
+            hs.level_begin.push_back((uint32_t) lvl_begin);
             const size_t cnt = lvl_end - lvl_begin;
             size_t per_chunk[kChunks] = {};
             parallel_chunks(cnt, [&](int c, size_t b0, size_t e0){
@@ -562,6 +755,7 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
             });
             lvl_begin = lvl_end; lvl_end += total;
         }
+        hs.level_begin.push_back((uint32_t) lvl_end);
         order.resize(lvl_end);
         // (slots a build thread reserved and did not use are not reachable and drop out here)
         const size_t reachable = order.size();
@@ -577,48 +771,12 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
         hs.nodes.swap(sorted);
     }
     lap("renumber");
-    {   // quantised twin: 16-bit grid over the union of the (padded) node boxes
-        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        {   std::vector<Box> part((size_t) kChunks);
-            for(Box &b : part) b.reset();
-            parallel_chunks(hs.nodes.size(), [&](int c, size_t b0, size_t e0){
-                Box &pb = part[(size_t) c];
-                for(size_t i = b0; i < e0; ++i){
-                    const BvhNode &n = hs.nodes[i];
-                    if(n.left != kEmptyChild){ pb.grow(n.lmin); pb.grow(n.lmax); }
-                    if(n.right != kEmptyChild){ pb.grow(n.rmin); pb.grow(n.rmax); }
-                }
-            });
-            for(const Box &b : part) for(int a = 0; a < 3; ++a){ lo[a] = std::min(lo[a], b.mn[a]); hi[a] = std::max(hi[a], b.mx[a]); }
-        }
-        for(int a = 0; a < 3; ++a){
-            if(!(lo[a] <= hi[a])){ lo[a] = 0.0f; hi[a] = 1.0f; }
-            hs.qorigin[a] = lo[a];
-            float ext = hi[a] - lo[a];
-            hs.qscale[a] = ext > 0.0f ? ext / 65535.0f : 1.0f;
-            hs.qscale[a] = std::nextafter(hs.qscale[a], INFINITY);          // never shorter than the box
-        }
-        auto qlo = [&](float v, int a){ double q = std::floor(((double) v - (double) hs.qorigin[a]) / (double) hs.qscale[a]) - 1.0; return (uint16_t) std::min(65535.0, std::max(0.0, q)); };
-        auto qhi = [&](float v, int a){ double q = std::ceil(((double) v - (double) hs.qorigin[a]) / (double) hs.qscale[a]) + 1.0; return (uint16_t) std::min(65535.0, std::max(0.0, q)); };
-        hs.qnodes.resize(hs.nodes.size());
-        parallel_chunks(hs.nodes.size(), [&](int, size_t b0, size_t e0){
-            for(size_t i = b0; i < e0; ++i){
-                const BvhNode &n = hs.nodes[i]; QBvhNode &q = hs.qnodes[i];
-                for(int a = 0; a < 3; ++a){
-                    if(n.left != kEmptyChild){ q.plane[a][0][0] = qlo(n.lmin[a], a); q.plane[a][1][0] = qhi(n.lmax[a], a); } else { q.plane[a][0][0] = 65535; q.plane[a][1][0] = 0; }
-                    if(n.right != kEmptyChild){ q.plane[a][0][1] = qlo(n.rmin[a], a); q.plane[a][1][1] = qhi(n.rmax[a], a); } else { q.plane[a][0][1] = 65535; q.plane[a][1][1] = 0; }
-                }
-                q.left = n.left; q.right = n.right;
-            }
-        });
-    }
+    quantise_tree(hs);
     if(hs.bvh_depth > kMaxBvhDepth) return "internal error: BVH deeper than the traversal stack";
     lap("quantise");
     {   // four-wide twin: greedy collapse of the binary tree, breadth-first numbering, same quantised child boxes
-        struct Kid { const float *mn, *mx; uint32_t code; };
+        struct Kid { const float *mn, *mx; uint32_t code, src; };      // src: binary node * 2 + side, what a refit reads the box from
         auto half_area = [](const Kid &k){ float dx = k.mx[0] - k.mn[0], dy = k.mx[1] - k.mn[1], dz = k.mx[2] - k.mn[2]; return dx * dy + dy * dz + dz * dx; };
-        auto qlo = [&](float v, int a){ double q = std::floor(((double) v - (double) hs.qorigin[a]) / (double) hs.qscale[a]) - 1.0; return (uint32_t) std::min(65535.0, std::max(0.0, q)); };
-        auto qhi = [&](float v, int a){ double q = std::ceil(((double) v - (double) hs.qorigin[a]) / (double) hs.qscale[a]) + 1.0; return (uint32_t) std::min(65535.0, std::max(0.0, q)); };
         struct Kids { Kid k[4]; int n; uint32_t code[4]; };
         pod_vector<uint32_t> todo(hs.nodes.size() + 1);             // binary node each wide node was collapsed from (breadth-first)
         pod_vector<Kids> all(hs.nodes.size() + 1);
@@ -635,8 +793,8 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
                     Kids ks; ks.n = 0;
                     auto open = [&](uint32_t idx){
                         const BvhNode &b = hs.nodes[idx];
-                        if(b.left != kEmptyChild) ks.k[ks.n++] = Kid{ b.lmin, b.lmax, b.left };
-                        if(b.right != kEmptyChild) ks.k[ks.n++] = Kid{ b.rmin, b.rmax, b.right };
+                        if(b.left != kEmptyChild) ks.k[ks.n++] = Kid{ b.lmin, b.lmax, b.left, idx * 2u };
+                        if(b.right != kEmptyChild) ks.k[ks.n++] = Kid{ b.rmin, b.rmax, b.right, idx * 2u + 1u };
                     };
                     open(todo[lvl_begin + i]);
                     while(ks.n < 4){
@@ -670,25 +828,19 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
             lvl_begin = lvl_end; lvl_end += total;
         }
         all.resize(lvl_end);
-        // pass 2: quantise and pack
+        // pass 2: the child codes and where each child's box comes from, then quantise and pack
         hs.wnodes.resize(all.size());
+        hs.wide_src.resize(all.size() * 4);
         parallel_chunks(all.size(), [&](int, size_t b0, size_t e0){
             for(size_t qi = b0; qi < e0; ++qi){
                 const Kids &ks = all[qi];
-                WideNode w;
-                uint32_t lo[3][4], hi[3][4];
                 for(int k = 0; k < 4; ++k){
-                    if(k < ks.n){ for(int a = 0; a < 3; ++a){ lo[a][k] = qlo(ks.k[k].mn[a], a); hi[a][k] = qhi(ks.k[k].mx[a], a); } }
-                    else { for(int a = 0; a < 3; ++a){ lo[a][k] = 65535u; hi[a][k] = 0u; } }
+                    hs.wnodes[qi].w[12 + k] = ks.code[k];
+                    hs.wide_src[qi * 4 + (size_t) k] = k < ks.n ? ks.k[k].src : kEmptyChild;
                 }
-                for(int a = 0; a < 3; ++a){
-                    w.w[a * 4 + 0] = lo[a][0] | (lo[a][1] << 16); w.w[a * 4 + 1] = lo[a][2] | (lo[a][3] << 16);
-                    w.w[a * 4 + 2] = hi[a][0] | (hi[a][1] << 16); w.w[a * 4 + 3] = hi[a][2] | (hi[a][3] << 16);
-                }
-                for(int k = 0; k < 4; ++k) w.w[12 + k] = ks.code[k];
-                hs.wnodes[qi] = w;
             }
         });
+        pack_wide_boxes(hs);
     }
 
     lap("wide");
@@ -707,11 +859,7 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
         for(size_t s = b0; s < e0; ++s){
             const RefTriangle &t = tris[B.prims[s].index];        // leaf order = the order the build left the primitives in
             DevTriangle &d = hs.tris[s];
-            for(int a = 0; a < 3; ++a){
-                d.v0[a] = t.v0[a];
-                d.e1[a] = t.v1[a] - t.v0[a];          // geometric.cuh:266-267
-                d.e2[a] = t.v2[a] - t.v0[a];
-            }
+            triangle_geometry(d, t);
             d.ordinal = (uint32_t) (ns + nl) + B.prims[s].index;
             d.material = mat_of[B.prims[s].index];
             d.flags = (t.m.eta <= 0.0f) ? 1u : 0u;

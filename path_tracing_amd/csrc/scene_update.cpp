@@ -1,0 +1,162 @@
+// Scene updates (include/hpt.h): a live scene's triangles, spheres and lights moved in place.  The triangles' tree is
+// refitted on the device (refit_kernels.hip) to the bytes of refit_host_scene (scene_build.cpp), which is the definition;
+// the host's share here is the refusals, packing and uploading the vertices, and the few builder lines that sit between
+// the launches (pad_abs and the dead point from the scene box, the grid from node 0).  Compiled with hipcc (host code only).
+#include "hpt_host.h"
+
+#include <chrono>
+#include <cmath>
+
+using namespace hpt;
+
+namespace {
+
+double ms_since(std::chrono::steady_clock::time_point t0){
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the refusals of hpt_scene_update_triangles, in the header's order
+int check_triangles(const hpt_scene *s, const void *tris, int nt){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    char msg[200];
+    const char *err = check_triangle_update(s->geo.h_tris.data(), s->geo.nt, tris, nt, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    return on_scene_device(s);
+}
+
+// scratch of the refit, and the build's wide-node map on the device: allocated by the first update and kept
+int ensure_scratch(hpt_scene *s){
+    hpt_scene::Update &u = s->up;
+    const size_t nt = (size_t) s->geo.nt, nn = (size_t) s->geo.sd.num_nodes;
+    HIP_TRY(u.verts.reserve(std::max<size_t>(nt * 9, 1)));
+    HIP_TRY(u.slot_box.reserve(std::max<size_t>(nt * 6, 1)));
+    HIP_TRY(u.exact.reserve(std::max<size_t>(nn * 6, 1)));
+    HIP_TRY(u.partial.reserve(std::max<size_t>((size_t) refit_blocks((uint32_t) nt) * 6, 6)));
+    HIP_TRY(u.result.reserve(8));
+    if(!u.ev_a) HIP_TRY(hipEventCreate(&u.ev_a));
+    if(!u.ev_b) HIP_TRY(hipEventCreate(&u.ev_b));
+    if(!u.ready){
+        if(u.wide_src.size() != (size_t) u.num_wide * 4 || u.level_begin.size() < 2 || u.level_begin.back() != (uint32_t) nn)
+            return fail(HPT_ERR_INVALID, "internal error: the scene keeps no refit tables");
+        HIP_TRY(u.d_wide_src.reserve(std::max<size_t>(u.num_wide, 1)));
+        if(u.num_wide) HIP_TRY(hipMemcpy(u.d_wide_src.get(), u.wide_src.data(), (size_t) u.num_wide * 16, hipMemcpyHostToDevice));
+        u.ready = true;
+    }
+    return HPT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int hpt_scene_update_check(const hpt_scene *s, const void *tris, int nt){ return check_triangles(s, tris, nt); }
+
+int hpt_scene_update_triangles(hpt_scene *s, const void *tris, int nt){
+    if(int rc = check_triangles(s, tris, nt)) return rc;
+    hpt_scene::Update &u = s->up;
+    hpt_scene::Geometry &g = s->geo;
+
+    // the nine floats of every triangle, input order
+    auto t0 = std::chrono::steady_clock::now();
+    u.h_verts.resize((size_t) nt * 9);
+    for(size_t i = 0; i < (size_t) nt; ++i) memcpy(u.h_verts.data() + i * 9, (const unsigned char *) tris + i * HPT_TRIANGLE_BYTES, 36);
+    const double ms_pack = ms_since(t0);
+
+    t0 = std::chrono::steady_clock::now();
+    if(int rc = ensure_scratch(s)) return rc;
+    if(nt) HIP_TRY(hipMemcpy(u.verts.get(), u.h_verts.data(), (size_t) nt * 36, hipMemcpyHostToDevice));
+    const double ms_upload = ms_since(t0);
+
+    const uint32_t num_nodes = (uint32_t) g.sd.num_nodes;
+    float4 *nodes = (float4 *) g.nodes.get();
+    HIP_TRY(hipEventRecord(u.ev_a, nullptr));
+    // leaf records, slot boxes, the live triangles' box and the dead count
+    HIP_TRY(hipMemsetAsync(u.result.get(), 0, 8 * sizeof(float), nullptr));
+    launch_refit_tris(nullptr, u.verts.get(), (float4 *) g.tris.get(), (uint32_t) nt, (uint32_t) g.sd.num_rounds, u.slot_box.get(), u.partial.get(),
+                      (uint32_t *) (u.result.get() + 6));
+    launch_refit_reduce(nullptr, u.partial.get(), nt ? refit_blocks((uint32_t) nt) : 0u, u.result.get());
+    HIP_TRY(hipGetLastError());
+    float res[8];
+    HIP_TRY(hipMemcpy(res, u.result.get(), sizeof res, hipMemcpyDeviceToHost));
+    uint32_t ndead; memcpy(&ndead, &res[6], 4);
+    // the dead point and pad_abs, as the builder has them (scene_build.cpp, triangle_boxes and box_padding)
+    float mn[3] = { res[0], res[1], res[2] }, mx[3] = { res[3], res[4], res[5] }, at[3] = { 0.0f, 0.0f, 0.0f };
+    if(ndead > 0){
+        for(int a = 0; a < 3; ++a){
+            at[a] = ndead < (uint32_t) nt ? mn[a] : 0.0f;
+            mn[a] = std::min(mn[a], at[a]); mx[a] = std::max(mx[a], at[a]);
+        }
+    }
+    const float pad_abs = box_padding_of(mn, mx, nt);
+    // node boxes, deepest level first
+    for(size_t l = u.level_begin.size() - 1; l-- > 0; )
+        launch_refit_level(nullptr, nodes, num_nodes, u.level_begin[l], u.level_begin[l + 1] - u.level_begin[l], u.slot_box.get(), (uint32_t) nt,
+                           u.exact.get(), pad_abs, at[0], at[1], at[2]);
+    HIP_TRY(hipGetLastError());
+    // the grid is the union of the stored boxes, which is the union of the root's two (padding is monotone)
+    BvhNode root;
+    HIP_TRY(hipMemcpy(&root, nodes, sizeof root, hipMemcpyDeviceToHost));
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for(int a = 0; a < 3; ++a){
+        if(root.left != kEmptyChild){ lo[a] = std::min(lo[a], std::min(root.lmin[a], root.lmax[a])); hi[a] = std::max(hi[a], std::max(root.lmin[a], root.lmax[a])); }
+        if(root.right != kEmptyChild){ lo[a] = std::min(lo[a], std::min(root.rmin[a], root.rmax[a])); hi[a] = std::max(hi[a], std::max(root.rmin[a], root.rmax[a])); }
+    }
+    RefitGrid grid;
+    grid_of_box(lo, hi, grid.qorigin, grid.qscale);
+    for(int a = 0; a < 3; ++a){ g.sd.qorigin[a] = grid.qorigin[a]; g.sd.qscale[a] = grid.qscale[a]; }
+    launch_refit_quantise(nullptr, nodes, (uint4 *) g.qnodes.get(), num_nodes, grid);
+    launch_refit_wide(nullptr, nodes, num_nodes, (uint4 *) g.wnodes.get(), u.d_wide_src.get(), u.num_wide, grid);
+    launch_tri_frames(nullptr, (const float4 *) g.tris.get(), nt, g.tri_frames.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(u.ev_b, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    float ms_refit = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms_refit, u.ev_a, u.ev_b));
+
+    if(nt) g.h_tris.assign((const unsigned char *) tris, (const unsigned char *) tris + (size_t) nt * HPT_TRIANGLE_BYTES);
+    s->bd.ready = false; s->pm.bounds_ready = false;
+    u.info.updates += 1; u.info.dead_tris = ndead; u.info.live_tris = (uint64_t) nt - ndead;
+    u.info.ms_pack = ms_pack; u.info.ms_upload = ms_upload; u.info.ms_refit = ms_refit;
+    return HPT_OK;
+}
+
+int hpt_scene_update_rounds(hpt_scene *s, const void *lights, int nl, const void *spheres, int ns){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    hpt_scene::Geometry &g = s->geo;
+    char msg[200];
+    const char *err = check_rounds_update(g.h_spheres.data(), g.ns, g.nl, lights, nl, spheres, ns, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(int rc = on_scene_device(s)) return rc;
+    std::vector<DevRound> rounds; std::vector<DevLight> dl;
+    err = flatten_rounds_host(lights, nl, spheres, ns, s->up.sphere_material.data(), rounds, dl);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(!rounds.empty()) HIP_TRY(hipMemcpy(g.rounds.get(), rounds.data(), rounds.size() * sizeof(DevRound), hipMemcpyHostToDevice));
+    if(!dl.empty()) HIP_TRY(hipMemcpy(g.lights.get(), dl.data(), dl.size() * sizeof(DevLight), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    if(nl) g.h_lights.assign((const unsigned char *) lights, (const unsigned char *) lights + (size_t) nl * HPT_LIGHT_BYTES);
+    if(ns) g.h_spheres.assign((const unsigned char *) spheres, (const unsigned char *) spheres + (size_t) ns * HPT_SPHERE_BYTES);
+    s->bd.ready = false; s->pm.bounds_ready = false;
+    return HPT_OK;
+}
+
+int hpt_scene_get_update_info(const hpt_scene *s, hpt_update_info *out){
+    if(!s || !out) return fail(HPT_ERR_INVALID, "null argument");
+    *out = s->up.info;
+    return HPT_OK;
+}
+
+int hpt_bvh_refit_host(const void *lights, int nl, const void *spheres, int ns, const void *tris, const void *new_tris, int nt,
+                       hpt_bvh_info *info, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap){
+    if(!info) return fail(HPT_ERR_INVALID, "null info");
+    HostScene hs;
+    const char *err = build_host_scene(lights, nl, spheres, ns, tris, nt, hs);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    char msg[200];
+    err = check_triangle_update(tris, nt, new_tris, nt, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    err = refit_host_scene(hs, new_tris, nt);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    return export_host_tree(hs, info, qnodes_out, qnodes_cap, tris_out, tris_cap);
+}
+
+} // extern "C"
