@@ -331,7 +331,7 @@ int hpt_wrapper_set_devices(int num_devices);
  * device versions of bsdf_evaluate / bsdf_pdf / bsdf_sample, FrDielectric, FrSchlick, the GGX D / Lambda / G terms,
  * the visible-normal sample, the local frame, sin/cos(2 pi u), is_valid_color and clamp_radiance (reference
  * include/geometric.cuh:119-235, 419-562) exactly as the shading kernel calls them.  24 floats in and 40 floats out per
- * record; the layout is documented at k_probe_functions (path_tracing_amd/csrc/pt_kernels.hip) and mirrored by
+ * record; the layout is documented at k_probe_functions (path_tracing_amd/csrc/pt_frame.hip) and mirrored by
  * oracle_function_kats (oracle/pt_oracle.cpp). */
 int hpt_probe_functions(const float *records_in, int n, float *results_out);
 

@@ -92,7 +92,7 @@ struct Scene {
 };
 
 // ---- host walk of the exported tree ----------------------------------------------------------
-// Visits what one ray of the device's plain traversal visits, in its order (path_tracing_amd/csrc/pt_kernels.hip,
+// Visits what one ray of the device's plain traversal visits, in its order (path_tracing_amd/csrc/pt_trace.hip,
 // trace_chunk without a budget): a node step slab-tests both children's quantised boxes, descends into the nearer hit
 // child and stacks the other; a leaf tests all of its triangles; the walk ends on an empty stack.  The primitive test is
 // the oracle's own intersect_triangle on the INPUT triangle the leaf slot's ordinal names, so the hit found is what the

@@ -15,15 +15,12 @@
 //
 // Arithmetic contract as in pt_device_math.h (-ffp-contract=off, expressions in reference order).
 #include "bdpt_kernels.h"
-#include "pt_device_math.h"
+#include "pt_device_common.h"
 
 namespace hpt {
 
 namespace {
 
-HPT_DEV uint32_t f2u(float f){ return __float_as_uint(f); }
-HPT_DEV float u2f(uint32_t u){ return __uint_as_float(u); }
-HPT_DEV f3 xyz(float4 v){ return mk3(v.x, v.y, v.z); }
 HPT_DEV f3 ld3(const float *p){ return mk3(p[0], p[1], p[2]); }
 
 constexpr uint32_t kBdMiss = 0xFFFFFFFFu;
@@ -32,31 +29,6 @@ constexpr uint32_t kBdLight = 0xC0000000u;       // | light index
 
 // glm::normalize: v * inversesqrt(dot(v, v)) -- the CPU scene model's normalisation
 HPT_DEV f3 gnormalize(f3 a){ float inv = 1.0f / sqrtf(dot3(a, a)); return a * inv; }
-
-HPT_DEV uint32_t lds_push(bool want, uint32_t *lds_counter){
-    unsigned long long mask = __ballot(want);
-    if(mask == 0ull) return 0u;
-    uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
-    uint32_t base = 0u;
-    int leader = __ffsll((long long) mask) - 1;
-    if((int) (threadIdx.x & 63u) == leader) base = atomicAdd(lds_counter, (uint32_t) __popcll(mask));
-    base = (uint32_t) __shfl((int) base, leader, 64);
-    return base + prefix;
-}
-
-HPT_DEV bool tile_to_pixel(const Tiling &tl, uint32_t p, int &x, int &y){
-    uint32_t ts2 = (uint32_t) (tl.tile * tl.tile);
-    uint32_t lt = p / ts2, q = p % ts2;
-    uint32_t gt = lt * (uint32_t) tl.world + (uint32_t) tl.rank;
-    if(gt >= (uint32_t) tl.ntiles) return false;
-    uint32_t ty = gt / (uint32_t) tl.tiles_x, tx = (gt % (uint32_t) tl.tiles_x + ty) % (uint32_t) tl.tiles_x;   // rows rotated, as in pt_kernels.hip
-    uint32_t sub = q >> 6, l = q & 63u;
-    uint32_t spr = (uint32_t) tl.tile >> 3;
-    uint32_t bx = sub % spr, by = sub / spr;
-    x = (int) (tx * (uint32_t) tl.tile + bx * 8u + (l & 7u));
-    y = (int) (ty * (uint32_t) tl.tile + by * 8u + (l >> 3));
-    return x < tl.W && y < tl.H;
-}
 
 // ---- CPU scene model: primitive tests (reference src/object.cpp) --------------------------------
 // AABB::intersectAABB, src/object.cpp:104-121 (degenerate boxes are pre-widened on the host)
@@ -134,19 +106,8 @@ HPT_DEV bool bd_walk(const BdptSceneDev &sc, uint32_t root, f3 ro, f3 rd, float 
             const float4 *n = sc.nodes + (size_t) cur * 4;
             float4 n0 = n[0], n1 = n[1], n2 = n[2], n3 = n[3];
             if(COUNT) tally->nodes += 1u;
-            float a0 = fmaf(n0.x, ix, -ox), a1 = fmaf(n1.x, ix, -ox);
-            float b0 = fmaf(n0.y, iy, -oy), b1 = fmaf(n1.y, iy, -oy);
-            float c0 = fmaf(n0.z, iz, -oz), c1 = fmaf(n1.z, iz, -oz);
-            float ln = fmaxf(fmaxf(fminf(a0, a1), fminf(b0, b1)), fmaxf(fminf(c0, c1), 0.0f));
-            float lf = fminf(fminf(fmaxf(a0, a1), fmaxf(b0, b1)), fminf(fmaxf(c0, c1), limit));
-            a0 = fmaf(n2.x, ix, -ox); a1 = fmaf(n3.x, ix, -ox);
-            b0 = fmaf(n2.y, iy, -oy); b1 = fmaf(n3.y, iy, -oy);
-            c0 = fmaf(n2.z, iz, -oz); c1 = fmaf(n3.z, iz, -oz);
-            float rn = fmaxf(fmaxf(fminf(a0, a1), fminf(b0, b1)), fmaxf(fminf(c0, c1), 0.0f));
-            float rf = fminf(fminf(fmaxf(a0, a1), fmaxf(b0, b1)), fminf(fmaxf(c0, c1), limit));
-            uint32_t lc = f2u(n0.w), rc = f2u(n1.w);
-            bool hl = (ln <= lf * 1.000002f) && (lc != kEmptyChild);
-            bool hr = (rn <= rf * 1.000002f) && (rc != kEmptyChild);
+            bool hl, hr; float ln, rn; uint32_t lc, rc;
+            bvh2_node_step(n0, n1, n2, n3, ix, iy, iz, ox, oy, oz, limit, hl, hr, ln, rn, lc, rc);
             if(hl && hr){
                 bool left_first = ln <= rn;
                 stk[sp * kBlock] = left_first ? rc : lc;
@@ -834,11 +795,7 @@ void k_bdpt_reduce(PathBuf pb, BdptPathBuf bp, int n_lv, const uint32_t *cqueue,
     }
 }
 
-uint32_t grid_for(uint32_t items){
-    uint32_t g = (items + kBlock - 1) / kBlock;
-    if(g < 1u) g = 1u;
-    return g > 4096u ? 4096u : g;
-}
+constexpr uint32_t kBdMaxGroups = 4096u;      // grid cap of the grid-stride kernels here (grid_for)
 
 } // namespace
 
@@ -851,7 +808,7 @@ void launch_bdpt_light_trace(hipStream_t s, const BdptSceneDev &sc, LightVertexD
 void launch_bdpt_generate(hipStream_t s, const Tiling &tl, const CameraDev &cam, PathBuf pb, BdptPathBuf bp, uint32_t *qcount,
                           int samples_this_pass, uint32_t first_sample, uint64_t seed){
     uint32_t total = (uint32_t) tl.n_local * (uint32_t) samples_this_pass;
-    hipLaunchKernelGGL(k_bdpt_generate, dim3(grid_for(total)), dim3(kBlock), 0, s, tl, cam, pb, bp, qcount, total, first_sample, seed);
+    hipLaunchKernelGGL(k_bdpt_generate, dim3(grid_for(total, kBdMaxGroups)), dim3(kBlock), 0, s, tl, cam, pb, bp, qcount, total, first_sample, seed);
 }
 // max_groups != 0 caps the grid (the blind tail iterations of HPT_FLAG_NO_HOST_WAIT): extend, connect and reduce walk
 // their queues with a stride, so a small grid is only slower when the queue is long -- which it is not there
@@ -859,7 +816,7 @@ static uint32_t capped(uint32_t g, uint32_t max_groups){ return max_groups != 0u
 
 void launch_bdpt_extend(hipStream_t s, const BdptSceneDev &sc, PathBuf pb, const uint32_t *queue, const uint32_t *qcount,
                         uint32_t max_items, uint32_t max_groups){
-    hipLaunchKernelGGL(k_bdpt_extend, dim3(capped(grid_for(max_items), max_groups)), dim3(kBlock), 0, s, sc, pb, queue, qcount);
+    hipLaunchKernelGGL(k_bdpt_extend, dim3(capped(grid_for(max_items, kBdMaxGroups), max_groups)), dim3(kBlock), 0, s, sc, pb, queue, qcount);
 }
 void launch_bdpt_vertex(hipStream_t s, const BdptSceneDev &sc, PathBuf pb, BdptPathBuf bp, const uint32_t *queue,
                         const uint32_t *qcount, uint32_t max_items, uint32_t *next_queue, uint32_t *next_count,
@@ -890,7 +847,7 @@ void launch_bdpt_connect(hipStream_t s, const BdptSceneDev &sc, PathBuf pb, Bdpt
 }
 void launch_bdpt_reduce(hipStream_t s, PathBuf pb, BdptPathBuf bp, int n_lv, const uint32_t *cqueue, const uint32_t *ccount,
                         uint32_t max_items, uint32_t max_groups){
-    hipLaunchKernelGGL(k_bdpt_reduce, dim3(capped(grid_for(max_items), max_groups)), dim3(kBlock), 0, s, pb, bp, n_lv, cqueue, ccount);
+    hipLaunchKernelGGL(k_bdpt_reduce, dim3(capped(grid_for(max_items, kBdMaxGroups), max_groups)), dim3(kBlock), 0, s, pb, bp, n_lv, cqueue, ccount);
 }
 
 } // namespace hpt

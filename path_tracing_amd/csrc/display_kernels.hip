@@ -87,7 +87,7 @@ __device__ __forceinline__ uint32_t ssd4(uint32_t a, uint32_t b){
     return s;
 }
 
-// One lane owns four consecutive canonical values = one word of `last` (k_tonemap's shape, pt_kernels.hip); the byte is
+// One lane owns four consecutive canonical values = one word of `last` (k_tonemap's shape, pt_frame.hip); the byte is
 // the number of thresholds <= x, eight steps in LDS.  A lane's squared differences fit a uint32 (<= 260100), a wave's
 // (x 64) and a workgroup's (x 256 = 66.6e6) too; they are added up by shuffles, then through LDS, and the workgroup
 // issues one 64-bit atomic per metric.  Every lane reaches the barriers and the shuffles: lanes past the image hold 0.

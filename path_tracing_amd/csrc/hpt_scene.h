@@ -1,5 +1,5 @@
 // Device-side scene layout of the path-tracing hot path, shared by the host flattening /
-// BVH code (scene_build.cpp) and the HIP kernels (pt_kernels.hip).  Plain structs only.
+// BVH code (scene_build.cpp) and the HIP kernels (pt_*.hip).  Plain structs only.
 //
 // Everything is 16-byte records so one lane fetches a record with dwordx4 loads:
 //   BVH node      64 B  both children's boxes + child codes (one fetch tests two boxes)

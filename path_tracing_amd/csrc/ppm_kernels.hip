@@ -5,7 +5,7 @@
 //   grid    stable radix sort of the deposits' bucket keys, bucket ranges, packed records
 //   gather  k_ppm_gather: one lane per hit point, 27 cells, resolve into the pass's radiance (ppm_cu.cu:300-322)
 //
-// Every closest-hit ray goes through the PT path's trace launches (pt_kernels.hip) unchanged: the shade kernels here
+// Every closest-hit ray goes through the PT path's trace launches (pt_trace.hip) unchanged: the shade kernels here
 // fill the PathBuf slots those launches read (origin, direction, flags) and read back the hit they write.
 //
 // The reference scatters every photon into a hash grid of hit points with float atomics, so its sums depend on
@@ -16,7 +16,7 @@
 // step on every axis, whichever side looks.  No float atomics anywhere, so the image is a function of the seed.
 // Built with -ffp-contract=off like the PT kernels (pt_device_math.h).
 #include "ppm_kernels.h"
-#include "pt_device_math.h"
+#include "pt_device_common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -24,30 +24,9 @@ namespace hpt {
 
 namespace {
 
-HPT_DEV uint32_t f2u(float f){ return __float_as_uint(f); }
-HPT_DEV float u2f(uint32_t u){ return __uint_as_float(u); }
-HPT_DEV f3 xyz(float4 v){ return mk3(v.x, v.y, v.z); }
-
-// wave64 push onto a global list: ballot, mbcnt prefix, one atomic per wave.  Called by every lane of the wave.
-HPT_DEV uint32_t wave_push(bool want, uint32_t *counter){
-    unsigned long long mask = __ballot(want);
-    if(mask == 0ull) return 0u;
-    uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
-    int leader = __ffsll((long long) mask) - 1;
-    uint32_t base = 0u;
-    if((int) (threadIdx.x & 63u) == leader) base = atomicAdd(counter, (uint32_t) __popcll(mask));
-    base = (uint32_t) __shfl((int) base, leader, 64);
-    return base + prefix;
-}
-
 HPT_DEV void wave_count(bool v, unsigned long long *counter){
     unsigned long long mask = __ballot(v);
     if(mask != 0ull && (int) (threadIdx.x & 63u) == __ffsll((long long) mask) - 1) atomicAdd(counter, (unsigned long long) __popcll(mask));
-}
-
-HPT_DEV unsigned long long wave_sum(unsigned long long v){
-    for(int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
 }
 
 // grid cell of a point: floorf((p - scene_min) / cell) per axis (ppm_cu.cu:34-38, 256-260), clamped to [-2^30, 2^30]
@@ -67,7 +46,7 @@ HPT_DEV uint32_t bucket_of(int gx, int gy, int gz, uint32_t buckets){
     return h & (buckets - 1u);
 }
 
-// hit record of a traced PathBuf slot (the decode of k_shade, pt_kernels.hip)
+// hit record of a traced PathBuf slot (the decode of k_shade, pt_shade.hip)
 struct PpmHit { f3 pos, normal; uint32_t mat; bool is_light; };
 HPT_DEV PpmHit decode_hit(const SceneDev &sc, f3 ro, f3 rd, uint2 h){
     PpmHit r;
@@ -159,9 +138,9 @@ void k_ppm_eye_shade(SceneDev sc, PathBuf pb, PpmHitBuf hb, const uint32_t *queu
             }
         }
     }
-    uint32_t q = wave_push(alive, next_count);
+    uint32_t q = lds_push(alive, next_count);
     if(alive) next_queue[q] = path;
-    uint32_t k = wave_push(hit_point, hp_count);
+    uint32_t k = lds_push(hit_point, hp_count);
     if(hit_point) hb.list[k] = path;
     wave_count(direct, &pc->direct);
     wave_count(hit_point, &pc->hit_points);
@@ -275,7 +254,7 @@ void k_ppm_photon_shade(SceneDev sc, PathBuf pb, PpmGrid g, const uint32_t *queu
             }
         }
     }
-    uint32_t q = wave_push(alive, next_count);
+    uint32_t q = lds_push(alive, next_count);
     if(alive) next_queue[q] = path;
     wave_count(i < count, &pc->photon_rays);
     wave_count(deposit, &pc->deposits);

@@ -1,4 +1,25 @@
-// Launch interface between the C ABI (hpt_api.cpp) and the HIP kernels (pt_kernels.hip).
+// Launch interface between the C ABI (hpt_api.cpp) and the HIP kernels of the unidirectional path-tracing hot path,
+// written for gfx950 (MI355X): a wavefront pipeline over queues of path slots
+//
+//   generate -> [ trace -> shade ]* -> trace -> resolve -> finalize
+//
+// generate  primary rays for (pixel, sample) slots                 (reference src/pt_cu.cu:36-46)          pt_frame.hip
+// trace     one merged launch per iteration: closest hit of every queued path (spheres + light balls       pt_trace.hip
+//           by scan, triangles by BVH; what it must return: reference include/geometric.cuh:327-388)
+//           and the any-hit shadow rays of the previous iteration, whose unoccluded contributions are
+//           added to the sample's radiance (include/geometric.cuh:293-325, src/pt_cu.cu:136-146,
+//           174-196).  A trace step is two launches: every ray gets a budget of node steps, the few
+//           that need more are set aside and finished by the resume launch.
+// shade     light-hit emission, next-event estimation set-up, BSDF sampling, throughput update;            pt_shade.hip
+//           survivors and shadow requests are compacted in LDS (wave64 ballot + mbcnt prefix) and
+//           flushed with one global atomic per workgroup            (reference src/pt_cu.cu:54-241)
+// resolve   per pixel, adds this pass's samples in sample order (src/pt_cu.cu:243-245)                     pt_frame.hip
+// finalize  mean over samples into the packed local framebuffer      (src/pt_cu.cu:248)                    pt_frame.hip
+// k_extend / k_connect are the one-ray-per-lane forms kept for the brute-force scan variants (tests).      pt_scan.hip
+//
+// One lane owns one path for the whole launch, every (pixel, sample) owns one slot for the
+// whole pass, and sums run in a fixed order, so results do not depend on scheduling, queue
+// order, pass size or the number of devices.  Built with -ffp-contract=off (pt_device_math.h); shared device helpers: pt_device_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

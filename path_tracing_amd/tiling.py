@@ -8,7 +8,7 @@ run over 8x8 pixel blocks (one wave64 of primary rays = one 8x8 block).  Every r
 buffer has the same size ceil(ntiles/world) * tile^2 so the gather is a plain fixed-size
 collective; slots past the image edge or past the last tile stay zero.
 
-The device code uses the same map (csrc/pt_kernels.hip: tile_to_pixel, k_untile); these
+The device code uses the same map (tile_to_pixel in csrc/pt_device_common.h, k_untile in csrc/pt_frame.hip); these
 numpy versions are the host logic used by the multi-rank driver and its CPU tests.
 """
 from __future__ import annotations

@@ -7,8 +7,11 @@ Makefile's HIPFLAGS and counts, per kernel and per basic block, the instruction 
   scratch  scratch_* loads and stores (VGPR spills)
 plus the register and spill counts of the kernel's metadata.  It counts nothing else.
 usage: python scripts/isa_report.py [file.hip ...] [--filter SUBSTR] [--min-valu 8] [--no-blocks] [--asm-out DIR]
-       (default file: path_tracing_amd/csrc/pt_kernels.hip)"""
+       (default file: path_tracing_amd/csrc/pt_trace.hip)
+       python scripts/isa_report.py --digest [file.hip ...]    one line per kernel: name, instructions, SHA-256 of its body
+       (comments left out, the function number taken out of local labels) -- two trees whose listings agree run the same device code"""
 import argparse
+import hashlib
 import os
 import re
 import shutil
@@ -170,6 +173,32 @@ def parse(asm):
     return kernels
 
 
+_LOCAL_LABEL = re.compile(r"(\.LBB|\.Lfunc_[A-Za-z_]*)\d+")
+
+
+def digests(asm):
+    """[(name, instructions, sha256 of the body)] for every kernel of an assembly text.  The body is every line of code
+    (instructions, labels, directives) from the kernel's label to its .Lfunc_end.  The function's number in local labels
+    is dropped (.LBB12_3 -> .LBB_3, .Lfunc_end12 -> .Lfunc_end), which is all that moving a kernel inside a file or to
+    another file changes in the code; the compiler's comments are left out, because its loop notes repeat those numbers
+    and are padded to a column by the label's length.  Nothing else is altered."""
+    meta = _metadata(asm)
+    out, cur = [], None
+    for line in asm.splitlines():
+        m = re.match(r"^([A-Za-z_$][\w$.]*):", line)
+        if m and m.group(1) in meta:
+            cur = [short_name(m.group(1)), 0, hashlib.sha256()]
+            out.append(cur)
+        elif cur is not None and line.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is not None:
+            code = line.split(";", 1)[0].strip()
+            if code:
+                cur[1] += code[0] != "." and not code.endswith(":")
+                cur[2].update((_LOCAL_LABEL.sub(r"\1", code) + "\n").encode())
+    return [(name, n, h.hexdigest()) for name, n, h in out]
+
+
 def report(src, extra=()):
     """parse(compile_asm(src))"""
     return parse(compile_asm(src, extra))
@@ -197,13 +226,20 @@ def format_blocks(kernel, min_valu=8):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("files", nargs="*", default=[os.path.join(CSRC, "pt_kernels.hip")])
+    ap.add_argument("files", nargs="*", default=[os.path.join(CSRC, "pt_trace.hip")])
     ap.add_argument("--filter", default="", help="only kernels whose name contains this")
     ap.add_argument("--min-valu", type=int, default=8)
     ap.add_argument("--no-blocks", action="store_true")
     ap.add_argument("--asm-out", default=None, help="keep the assembly in this directory")
     ap.add_argument("--from-asm", action="store_true", help="the files are assembly already")
+    ap.add_argument("--digest", action="store_true", help="per kernel: name, instruction count, SHA-256 of the body (see digests)")
     a = ap.parse_args()
+    if a.digest:
+        for f in a.files:
+            for name, n, h in sorted(digests(open(f).read() if a.from_asm else compile_asm(f))):
+                if a.filter in name:
+                    print("%-44s %6d  %s" % (name, n, h))
+        return
     for f in a.files:
         if a.from_asm:
             asm = open(f).read()

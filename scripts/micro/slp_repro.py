@@ -3,7 +3,7 @@
 
 The product source sets the hit-level words of a next-event record (local wo, Lambda(wo), throughput, material, shadow
 segment start) BEFORE the nested branches behind the unit-ball rejection loop of k_shade.  This script writes a copy of
-pt_kernels.hip with those five assignments moved back INSIDE both branches (the form that was miscompiled), builds that
+pt_shade.hip with those five assignments moved back INSIDE both branches (the form that was miscompiled), builds that
 copy twice -- HIPFLAGS as they are, and without -fno-slp-vectorize -- and renders tests/golden/scenes/input.txt with both
 libraries against the committed golden image.  A miscompiled build loses the y component of the float3 values the
 vectorizer paired into packed-f32 operations: green = 0 in the next-event contributions.
@@ -22,7 +22,7 @@ INNER = "n_wo = ctx.wo; n_lam = pre.lam_o; n_thr = throughput; n_mat = mat_idx; 
 
 
 def make_source():
-    src = open(os.path.join(CSRC, "pt_kernels.hip")).read()
+    src = open(os.path.join(CSRC, "pt_shade.hip")).read()
     assert src.count(HOIST) == 1, "k_shade no longer has the hoisted assignments in the expected form"
     src = src.replace(HOIST, "")
     a = "                                nee = true;\n                                n_wi = to_local(light_dir, ctx.T, ctx.B, ctx.N);"
@@ -30,7 +30,7 @@ def make_source():
     assert src.count(a) == 1 and src.count(b) == 1
     src = src.replace(a, "                                " + INNER + "\n" + a).replace(b, "                                    " + INNER + "\n" + b)
     os.makedirs(OUT, exist_ok=True)
-    open(os.path.join(OUT, "pt_kernels.hip"), "w").write(src)
+    open(os.path.join(OUT, "pt_shade.hip"), "w").write(src)
 
 
 def build():
@@ -40,9 +40,9 @@ def build():
     print(subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout.splitlines()[0])
     for tag, fl in (("off", flags), ("on", flags.replace("-fno-slp-vectorize", ""))):
         objs = []
-        for f in ("pt_kernels.hip", "bdpt_kernels.hip", "ppm_kernels.hip", "hpt_api.cpp", "render_pt.cpp", "render_bdpt.cpp", "render_ppm.cpp",
+        for f in ("pt_trace.hip", "pt_shade.hip", "pt_scan.hip", "pt_frame.hip", "bdpt_kernels.hip", "ppm_kernels.hip", "hpt_api.cpp", "render_pt.cpp", "render_bdpt.cpp", "render_ppm.cpp",
                   "hpt_multi.cpp"):
-            path = os.path.join(OUT if f == "pt_kernels.hip" else CSRC, f)
+            path = os.path.join(OUT if f == "pt_shade.hip" else CSRC, f)
             o = os.path.join(OUT, "%s_%s.o" % (os.path.splitext(f)[0], tag))
             subprocess.check_call(["/opt/rocm/bin/hipcc"] + fl.split() + ["-I", CSRC, "-x", "hip", "-c", "-o", o, path])
             objs.append(o)

@@ -1,7 +1,7 @@
 """Inputs of the function-level known-answer tests: seeded records for the BSDF / Fresnel / GGX
 functions over the material classes of input.txt -- diffuse r = 1; rough dielectric-opaque r = 0.3 / 0.6; conductors
 m = 0.9 r = 0.2 and m = 0.8 r = 0.3; mirror m = 1 r = 0; glass eta 1.5 / 2.4 -- plus random materials.
-Record layout (24 floats): k_probe_functions in path_tracing_amd/csrc/pt_kernels.hip."""
+Record layout (24 floats): k_probe_functions in path_tracing_amd/csrc/pt_frame.hip."""
 import numpy as np
 
 CLASSES = [

@@ -1,5 +1,5 @@
 """Case table of the path-tracing coverage suite: scenes, cameras and parameters at which the kernels of
-csrc/pt_kernels.hip (k_trace's quantised slab tests, hardware reciprocal, LDS tree top, node-step budget and four-wide
+csrc/pt_trace.hip, pt_shade.hip and pt_frame.hip (k_trace's quantised slab tests, hardware reciprocal, LDS tree top, node-step budget and four-wide
 resume walk; k_shade; resolve, finalize, untile) and the host loop of render_pt.cpp can go wrong and the tests of
 test_gpu_parity.py do not look.  A plain module: no GPU, no tests.
 
@@ -155,7 +155,7 @@ def raw_camera_case(which):
 
 
 def primary_dirs(cam, W, H, jitter=0.5):
-    """Directions of primary_ray (csrc/pt_kernels.hip) in numpy float32, one per pixel at a fixed jitter: [H, W, 3]."""
+    """Directions of primary_ray (csrc/pt_device_common.h) in numpy float32, one per pixel at a fixed jitter: [H, W, 3]."""
     f = np.float32
     px = (np.arange(W, dtype=f) + f(jitter))[None, :, None]
     py = (np.arange(H, dtype=f) + f(jitter))[:, None, None]

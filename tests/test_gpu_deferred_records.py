@@ -1,4 +1,4 @@
-"""Closest-hit rays set aside as dense records (csrc/pt_kernels.hip: the `defer` block and the resume refill of trace_chunk,
+"""Closest-hit rays set aside as dense records (csrc/pt_trace.hip: the `defer` block and the resume refill of trace_chunk,
 k_trace's hand-off to lqueue[0]) against the CPU oracle and against renders whose records land somewhere else.
 
 Past iteration 0 the first trace launch writes a ray it sets aside as a record of three 16-byte cells ({origin, best t},

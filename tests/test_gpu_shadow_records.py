@@ -1,5 +1,5 @@
-"""Shadow-ray records indexed by queue position (csrc/pt_kernels.hip: flush_nee in k_shade, the any-hit side of
-trace_chunk, k_connect) against the CPU oracle and against renders whose records land somewhere else.
+"""Shadow-ray records indexed by queue position (csrc: flush_nee in k_shade, pt_shade.hip; the any-hit side of
+trace_chunk, pt_trace.hip; k_connect, pt_scan.hip) against the CPU oracle and against renders whose records land somewhere else.
 
 k_shade stores the record of a next-event candidate at `first queue position of the workgroup's chunk + rank among the
 chunk's records`, the shadow queue lists those indices, and the path slot rides in contrib.w.  Where a record lands

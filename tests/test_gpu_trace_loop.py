@@ -1,4 +1,4 @@
-"""The exits of trace_chunk's outer loop (csrc/pt_kernels.hip): the smallest renders in which a refill starts no lane or
+"""The exits of trace_chunk's outer loop (csrc/pt_trace.hip): the smallest renders in which a refill starts no lane or
 a wave has nothing to do, bit for bit against oracle.pt_render.
 
 The loop has one exit, after the refill: "every lane idle and the chunk exhausted".  A refill that starts nobody while the

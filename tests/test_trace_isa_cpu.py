@@ -1,5 +1,5 @@
 """k_trace's loop-carried ray state is not copied per trip: a static check of the gfx950 assembly (no GPU; one device-side
-compile of csrc/pt_kernels.hip with the Makefile's flags, through scripts/isa_report.py).
+compile of csrc/pt_trace.hip with the Makefile's flags, through scripts/isa_report.py).
 
 Before round 5 trace_chunk's outer loop had two exits and a `continue`; the register coalescer then copied the lane's whole
 ray state (20-24 VGPRs) into a second register set at the top of every trip and back before the node walk.  PARENT holds
@@ -34,7 +34,7 @@ _KERNELS = {}
 
 def trace_kernels():
     if not _KERNELS:
-        src = os.path.join(ROOT, "path_tracing_amd", "csrc", "pt_kernels.hip")
+        src = os.path.join(ROOT, "path_tracing_amd", "csrc", "pt_trace.hip")
         _KERNELS.update({k["name"]: k for k in isa_report.report(src) if k["name"].startswith("k_trace<")})
     return _KERNELS
 
