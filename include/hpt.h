@@ -284,7 +284,10 @@ int hpt_ppm_render_wrapper(const void *lights, int num_lights, const void *spher
  * hpt_sppm_render advances the state by `passes` (> 0) passes and writes the estimate (W*H*3 floats, row-major)
  * into host_image; flags may hold HPT_FLAG_TIME_KERNELS and HPT_FLAG_COUNT_WORK only, and the scene's
  * hpt_ppm_stats then describe this call (candidates: the pairs examined in the cells visited).  hpt_sppm_reset
- * returns to K = 0.  hpt_sppm_read_state copies R2 and N (W*H floats each, row-major; either may be NULL) and K. */
+ * returns to K = 0 (R2, N, tau and D as at creation) and, where the state was created with scene_min or scene_max NULL,
+ * takes that bound from the scene again, as it is now: after a scene update a reset state is a state freshly created
+ * on the new scene.  Bounds the caller gave stay as given.  hpt_sppm_read_state copies R2 and N (W*H floats each,
+ * row-major; either may be NULL) and K. */
 typedef struct hpt_sppm hpt_sppm;
 int hpt_sppm_create(hpt_scene *scene, const void *camera, int W, int H, int eye_depth, int light_depth, int spl,
                     float radius, float alpha, const float *scene_min, const float *scene_max,
@@ -770,8 +773,10 @@ int hpt_trace_visibility(hpt_scene *scene, const float *p1, const float *p2, int
  * accepts an update of zero triangles.  hpt_scene_update_check makes the refusals of hpt_scene_update_triangles and
  * nothing else: no device work.  After HPT_ERR_DEVICE from an update the scene must be destroyed.
  *
- * What the caller keeps in step: an hpt_sppm state created before an update still holds the old scene's bounds and
- * statistics -- reset or recreate it (not checked).  hpt_history and hpt_accum have no motion vectors for moving
+ * What the caller keeps in step: an hpt_sppm state created before an update renders the new scene, but still holds
+ * the statistics gathered on the old one and the bounds it took when it was created or last reset -- reset it
+ * (hpt_sppm_reset re-reads the bounds the state was created without; bounds handed to hpt_sppm_create are the
+ * caller's to keep right) or recreate it (not checked).  hpt_history and hpt_accum have no motion vectors for moving
  * geometry: with a still camera they would average two scenes, so reset them after an update.
  *
  * hpt_scene_get_update_info describes the last hpt_scene_update_triangles (zeros before the first): how many have been

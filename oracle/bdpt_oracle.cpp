@@ -100,6 +100,9 @@ bool cpu_sphere(const RSphere &s, V3 O, V3 vec, float tMin, float tMax, float &t
 // Triangle::check_intersect, src/object.cpp:72-95
 bool cpu_triangle(const RTriangle &tr, V3 O, V3 vec, float tMin, float tMax, float &t){
     const V3 e1 = tr.v1 - tr.v0, e2 = tr.v2 - tr.v0;
+    // a triangle with a non-finite edge is dead (include/hpt.h, scene updates): no ray hits it.  The reference's lines below
+    // would report a hit at t = NaN, every comparison with a NaN being false; for finite edges nothing changes
+    if(!(std::isfinite(e1.x) && std::isfinite(e1.y) && std::isfinite(e1.z) && std::isfinite(e2.x) && std::isfinite(e2.y) && std::isfinite(e2.z))) return false;
     const V3 pvec = cross(vec, e2);
     const float det = dot(e1, pvec);
     if((double) std::fabs(det) < 1e-6) return false;

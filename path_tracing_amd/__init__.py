@@ -421,6 +421,7 @@ class Sppm:
         return img
 
     def reset(self):
+        """Back to K = 0; bounds left to the scene at creation (scene_min / scene_max None) are taken from it again."""
         _check(self._lib.hpt_sppm_reset(self._h))
 
     def state(self) -> dict:

@@ -364,6 +364,7 @@ struct hpt_sppm {
     int W = 0, H = 0, eye_depth = 0, light_depth = 0, spl = 0;
     float radius = 0.05f, alpha = 1.0f;
     float smin[3] = { 0, 0, 0 }, smax[3] = { 0, 0, 0 };
+    bool scene_smin = false, scene_smax = false;      // created with scene_min / scene_max NULL: hpt_sppm_reset re-reads the scene's
     hpt_params P{};                  // seed, sample_offset, max_delta (clamped), tile
     Tiling tl{};
     int64_t passes = 0;              // K
@@ -377,6 +378,14 @@ extern "C" {
 int hpt_sppm_reset(hpt_sppm *z){
     if(!z) return fail(HPT_ERR_INVALID, "null state");
     if(int rcd = on_scene_device(z->scene)) return rcd;
+    // bounds the caller left to the scene are the scene's of now: an update since the last reset has invalidated them
+    if(z->scene_smin || z->scene_smax){
+        ppm_scene_bounds(z->scene);
+        for(int a = 0; a < 3; ++a){
+            if(z->scene_smin) z->smin[a] = z->scene->pm.min[a];
+            if(z->scene_smax) z->smax[a] = z->scene->pm.max[a];
+        }
+    }
     launch_sppm_init(nullptr, z->st, (uint32_t) z->tl.n_local, z->radius * z->radius);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(nullptr));
@@ -407,8 +416,8 @@ int hpt_sppm_create(hpt_scene *s, const void *camera, int W, int H, int eye_dept
     z->scene = s; memcpy(z->camera, camera, HPT_CAMERA_BYTES);
     z->W = W; z->H = H; z->eye_depth = eye_depth; z->light_depth = light_depth; z->spl = spl;
     z->radius = radius; z->alpha = alpha; z->P = P; z->tl = tl;
-    ppm_scene_bounds(s);
-    for(int a = 0; a < 3; ++a){ z->smin[a] = scene_min ? scene_min[a] : s->pm.min[a]; z->smax[a] = scene_max ? scene_max[a] : s->pm.max[a]; }
+    z->scene_smin = !scene_min; z->scene_smax = !scene_max;              // filled by hpt_sppm_reset below
+    for(int a = 0; a < 3; ++a){ if(scene_min) z->smin[a] = scene_min[a]; if(scene_max) z->smax[a] = scene_max[a]; }
     const size_t n = (size_t) tl.n_local;
     hipError_t e = z->tau_r2.reserve(n);
     if(e == hipSuccess) e = z->photons.reserve(n);

@@ -948,7 +948,15 @@ const char *build_bdpt_host_scene(const void *lights_v, int nl, const void *sphe
                 r.flags = (s.m.eta <= 0.0f) ? 1u : 0u;
                 r.pad[0] = it.seq;
                 out.spheres.push_back(r);
-            } else gtris.push_back(it);
+            } else {
+                // a dead triangle (a non-finite edge, triangle_boxes' rule) stays out of the group's tree: the test the
+                // bidirectional kernels make (src/object.cpp:72-95) would report a hit at t = NaN, every comparison with
+                // a NaN being false, and its box would be built from whichever coordinates are finite
+                const RefTriangle &t = tris[it.index];
+                bool live = true;
+                for(int a = 0; a < 3; ++a) live = live && std::isfinite(t.v1[a] - t.v0[a]) && std::isfinite(t.v2[a] - t.v0[a]);
+                if(live) gtris.push_back(it);
+            }
         }
         g.sphere_count = (uint32_t) out.spheres.size() - g.sphere_first;
         Builder B;

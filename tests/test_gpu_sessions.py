@@ -6,7 +6,9 @@ counters, the own framebuffers and the render events, all grow-only and reached 
 refreshes for itself; a test that opens a handle for one render sees none of it.  Here the size, depth, delta cap, tile,
 samples per pass, flags and integrator change from step to step, up and down, and the repeated steps must give the bytes
 of their first occurrence.  Statistics steps hold hpt_get_stats to "the last render only": zeros after photon mapping
-and guides (which count into hpt_ppm_stats), the oracle's ray counts after a counting PT render.
+and guides (which count into hpt_ppm_stats), the oracle's ray counts after a counting PT render.  The update steps
+(sessions G, G_rounds, G_parallel, R4..R6) replace the records the handle holds; everything after them is the oracles'
+result on the records in force, and the exported tree the host definition's refit of the builder's.
 
 A mismatch names the session, the step, its record and the first differing value.  The `_device` steps run on a torch
 side stream and are waited for before the next step (include/hpt.h, hpt_render_pt_device: work on one scene is ordered
@@ -71,7 +73,7 @@ class Run:
 
     def __init__(self, hpt, session, expected):
         self.hpt, self.session, self.expected = hpt, session, expected
-        self.sd = sc.scene(session.scene)
+        self.sd = self.cur = sc.current(session.scene)          # cur: the records the handle holds, replaced by the update steps
         self.L, self.sp, self.tr = self.sd["L"], self.sd["sp"], self.sd["tr"]
         self.states, self.gathered, self.results, self.side = {}, {}, [], None
         self.h = self.constants = None
@@ -173,21 +175,36 @@ class Run:
         elif k == "sppm_destroy":
             self.states.pop(kw["name"]).close()
         elif k == "probe_closest":
-            o, d, _ = sc.probe_rays(self.sd, kw["n"], kw["seed"])
+            o, d, _ = sc.probe_rays(self.cur, kw["n"], kw["seed"])
             t, prim = self.h.trace_closest(o, d)
             got = dict(t=t, prim=prim)
         elif k == "probe_visibility":
-            o, _, p2 = sc.probe_rays(self.sd, kw["n"], kw["seed"])
+            o, _, p2 = sc.probe_rays(self.cur, kw["n"], kw["seed"])
             got = dict(visible=self.h.trace_visibility(o, p2))
         elif k == "export_bvh":
-            dev, host = self.h.export_bvh(), hpt.export_bvh_host(self.L, self.sp, self.tr)
+            # the builder's tree while the handle holds the triangles it was created from (before any update, and after
+            # an update back to them), else the definition's refit of that tree to the current triangles
+            base = self.cur["edits"][0] == "base"
+            host = hpt.export_bvh_host(self.L, self.sp, self.tr) if base else hpt.refit_bvh_host(self.L, self.sp, self.tr, self.cur["tr"])
+            dev = self.h.export_bvh()
             for key in TREE_KEYS:
                 _same(s, i, "exported " + key, dev[key], host[key])
+        elif k in sc.UPDATES:
+            self.cur = sc.after_update(self.cur, st)
+            if k == "update_triangles":
+                self.h.update_triangles(self.cur["tr"])
+                info = self.h.update_info()
+                for key in ("updates", "live_tris", "dead_tris"):
+                    _equal(s, i, "hpt_update_info." + key, info[key], e[key])
+            else:
+                self.h.update_rounds(self.cur["L"], self.cur["sp"])
         elif k == "stats":
             self.check_stats(i, e)
         elif k == "refused":
             call = dict(pt=self.pt, bdpt=self.bdpt, ppm=self.ppm, guides=self.guides, guides_null=self.guides_null, sppm_create=self.sppm_create,
-                        sppm_render=lambda a: self.states[a["name"]].render(a["passes"]))[kw["call"]]
+                        sppm_render=lambda a: self.states[a["name"]].render(a["passes"]),
+                        update_triangles=lambda a: self.h.update_triangles(*sc.refused_update_args(self.cur, a)),
+                        update_rounds=lambda a: self.h.update_rounds(*sc.refused_update_args(self.cur, a)))[kw["call"]]
             try:
                 call(kw)
             except hpt.HptError as err:
@@ -289,6 +306,22 @@ def test_session_e_fan_out(hpt, orc):
 
 def test_session_f_one_shot_wrappers(hpt, orc):
     _run(hpt, orc, "F")
+
+
+def test_session_g_a_scene_over_time(hpt, orc):
+    """Updates between rounds that grow and shrink the workspace and run every flag; two progressive states without and
+    with a reset; a rank group with an update between its ranks; every update refusal; the builder's bytes at the end."""
+    _run(hpt, orc, "G")
+
+
+def test_session_g_rounds(hpt, orc):
+    _run(hpt, orc, "G_rounds")
+
+
+def test_session_g_parallel_light(hpt, orc):
+    """A progressive state under a parallel light across an update: stale bounds without a reset, the new scene's bounds
+    after one (hpt_sppm_reset re-reads the bounds the state was created without)."""
+    _run(hpt, orc, "G_parallel")
 
 
 @pytest.mark.parametrize("seed", sc.R_SEEDS)

@@ -9,9 +9,13 @@ import sys
 import numpy as np
 import pytest
 
+import ppm_oracle
+import refit_cases as rc
 import session_cases as sc
 
-SIZED = [n for n in sc.NAMES if n not in ("A_fresh", "D", "F")]
+SIZED = [n for n in sc.NAMES if n not in ("A_fresh", "D", "F", "G_rounds", "G_parallel")]
+SHOWN = 0.05                    # the share of pixels an update must change in the render that shows it (test_gpu_refit.py's bar)
+R_ATTEMPTS = {1: 2, 2: 10, 3: 35, 4: 387, 5: 381, 6: 103}
 
 
 @pytest.fixture(scope="module")
@@ -203,14 +207,24 @@ def test_sessions_e_and_f_are_the_listed_calls():
 
 
 def test_random_sessions_are_functions_of_their_seeds():
-    assert sc.R_SEEDS == [1, 2, 3]
+    assert sc.R_SEEDS == [1, 2, 3, 4, 5, 6] and sc.R_UPDATING == 4
     for seed in sc.R_SEEDS:
         a, attempt = sc.random_session(seed)
         b, again = sc.random_session(seed)
-        assert a == b and attempt == again and len(a.steps) == sc.R_STEPS and a == sc.session("R%d" % seed)
+        assert a == b and attempt == again == R_ATTEMPTS[seed] and len(a.steps) == sc.R_STEPS and a == sc.session("R%d" % seed)
         kinds = {st.kind for st in a.steps}
         assert len(kinds) >= 8 and {"pt", "bdpt", "ppm", "guides"} <= kinds
-    assert len({repr(sc.session("R%d" % seed).steps) for seed in sc.R_SEEDS}) == 3
+        # the updates and their refusals are offered from R_UPDATING on, and there every session holds them
+        updating = any(st.kind in sc.UPDATES or sc.is_update_refusal(st) for st in a.steps)
+        assert updating == (seed >= sc.R_UPDATING)
+        if updating:
+            assert sum(st.kind in sc.UPDATES for st in a.steps) >= 2 and any(sc.is_update_refusal(st) for st in a.steps)
+        # a draw that missed a condition only the oracles see is listed by number: a few, and none that was not needed
+        assert len(sc.R_REJECTED[seed]) <= 3 and all(n < attempt for n in sc.R_REJECTED[seed])
+    assert len({repr(sc.session("R%d" % seed).steps) for seed in sc.R_SEEDS}) == 6
+    later = [st for seed in sc.R_SEEDS if seed >= sc.R_UPDATING for st in sc.session("R%d" % seed).steps]
+    assert {"update_triangles", "update_rounds"} <= {st.kind for st in later}
+    assert {"update_triangles", "update_rounds"} <= {st.kw["call"] for st in later if st.kind == "refused"}
     # another process, another hash seed: the same steps
     code = "import session_cases as sc\nfor s in sc.R_SEEDS: print(repr(sc.random_session(s)))"
     env = dict(os.environ, PYTHONHASHSEED="12345")
@@ -219,3 +233,128 @@ def test_random_sessions_are_functions_of_their_seeds():
     vocabulary = {st.kind for seed in sc.R_SEEDS for st in sc.session("R%d" % seed).steps}
     assert {"pt_device_rank", "untile", "set_groups", "sppm_create", "sppm_render", "sppm_state", "sppm_destroy", "probe_closest",
             "probe_visibility", "export_bvh", "stats", "refused"} <= vocabulary
+
+
+# ---- scene updates in the table ----------------------------------------------------------------------------------------
+
+def _update_witnesses(orc, s):
+    """[(update step, [(render step, share of its pixels the update changed)])]: for every accepted update, the renders
+    between it and the next update, each compared with the same render on the records in force BEFORE the update."""
+    ex, notes = sc.expected(orc, s), sc.notes(orc, s)
+    ups = [i for i, st in enumerate(s.steps) if st.kind in sc.UPDATES]
+    out = []
+    for i, nxt in zip(ups, ups[1:] + [len(s.steps)]):
+        before = notes[i - 1]["cur"] if i else sc.current(s.scene)
+        shares = [(j, rc.changed_share(ex[j]["image"], sc.render_step(orc, before, s.steps[j], notes[j]["order"])["image"]))
+                  for j in range(i + 1, nxt) if s.steps[j].kind in sc.WITNESSES]
+        out.append((i, shares))
+    return out
+
+
+@pytest.mark.parametrize("name", sc.UPDATING)
+def test_every_update_is_shown_by_a_render_before_the_next(orc, name):
+    """Otherwise a dropped update could pass.  No update of the table hands over the records the handle already holds, so
+    none is exempt."""
+    s = sc.session(name)
+    assert all(sc.update_conditions(s).values()), sc.update_conditions(s)
+    for i, shares in _update_witnesses(orc, s):
+        print("%s step %d, %s %s: %s" % (name, i, s.steps[i].kind, s.steps[i].kw["edit"],
+                                         ", ".join("%s at %d %.3f" % (s.steps[j].kind, j, share) for j, share in shares)))
+        assert max(share for _, share in shares) >= SHOWN, (name, i, s.steps[i], shares)
+
+
+@pytest.mark.parametrize("name", sc.UPDATING)
+def test_progressive_states_across_updates(orc, name):
+    """A render after a reset that followed an update: where the scene has a parallel light, the image under the bounds the
+    reset takes differs from the one under the bounds the state was created with (G_parallel; a reset that kept the old
+    bounds cannot pass); everywhere else the two are the same bytes, the bounds reaching the image by a parallel light's
+    plane alone.  A render after an update without a reset differs from a fresh state's: the statistics are carried."""
+    s = sc.session(name)
+    ex, notes = sc.expected(orc, s), sc.notes(orc, s)
+    parallel = bool(np.asarray(sc.scene(s.scene)["L"]["is_parallel"]).any())
+    assert parallel == (name == "G_parallel")
+    stale = [i for i, n in enumerate(notes) if "stale" in n]
+    carried = [i for i, n in enumerate(notes) if "fresh" in n]
+    for i in stale:
+        share = rc.changed_share(ex[i]["image"], notes[i]["stale"])
+        print("%s step %d: the reset's bounds against the create-time bounds, changed share %.3f" % (name, i, share))
+        cur, made = notes[i]["cur"], sc.scene(s.scene)
+        moved = ppm_oracle.scene_bounds(cur["sp"], cur["tr"])[0].tobytes() != ppm_oracle.scene_bounds(made["sp"], made["tr"])[0].tobytes()
+        if parallel and moved:
+            assert share >= SHOWN, (name, i, share)
+        else:
+            assert share == 0.0, (name, i, share)
+    for i in carried:
+        assert rc.changed_share(ex[i]["image"], notes[i]["fresh"]) > 0.0, (name, i)
+    if name in ("G", "G_rounds", "G_parallel"):
+        assert stale and carried, (name, stale, carried)
+    if name == "G_parallel":
+        assert stale == [5, 10] and carried == [3]
+        assert rc.changed_share(ex[5]["image"], notes[5]["stale"]) >= SHOWN and s.steps[10].repeat_of == 1
+
+
+@pytest.mark.parametrize("name", sc.UPDATING)
+def test_refused_updates_are_followed_by_every_kind_of_render(name):
+    s = sc.session(name)
+    for i, st in enumerate(s.steps):
+        if sc.is_update_refusal(st):
+            assert {"pt", "bdpt", "ppm", "export_bvh"} <= {p.kind for p in s.steps[i + 1:]}, (name, i)
+            assert st.kw["code"] == sc.ERR_INVALID
+    made = {st.kw["label"] for n in ("G", "G_rounds") for st in sc.session(n).steps if sc.is_update_refusal(st)}
+    assert made == {r[0] for r in sc.UPDATE_REFUSALS} and len(made) == 5
+
+
+def test_session_g_is_a_scene_over_time(orc):
+    s = sc.session("G")
+    assert s.scene == "cornell2k" and s.handle == "scene"
+    kinds = [st.kind for st in s.steps]
+    ups = [(i, st.kw["edit"]) for i, st in enumerate(s.steps) if st.kind == "update_triangles"]
+    assert [e for _, e in ups] == ["turn30", "lowered", "dead20", "shrunk", "base"]
+    at = dict((e, i) for i, e in ups)
+    # the workspace rises after the first update and falls after the second
+    fp = dict(sc.footprints(s))
+    for q in ("slots", "n_local"):
+        top = max(fp, key=lambda i: fp[i][q])
+        assert at["turn30"] < top < at["lowered"] and all(fp[i][q] < fp[top][q] for i in fp if i != top)
+        assert any(i > at["lowered"] for i in fp)
+    assert s.steps[at["turn30"] + 1].kw["samples_per_pass"] == 1 and s.steps[at["turn30"] + 1].kw["spp"] == 2
+    # every flag, budget 1, max_delta 1 and 250 and every tile on an updated scene
+    after = [st for st in s.steps[at["turn30"]:] if st.kind in sc.WITNESSES + ("pt_device_rank",)]
+    flags = {f for st in after for f in (sc.RUSSIAN_ROULETTE, sc.SINGLE_PIPELINE, sc.OUTPUT_SUM, sc.TIME_KERNELS, sc.COUNT_WORK, sc.NO_HOST_WAIT)
+             if st.kw.get("flags", 0) & f}
+    assert len(flags) == 6
+    assert {1, 250} <= {st.kw.get("max_delta", 0) for st in after} and 1 in {st.kw.get("budget", 0) for st in after}
+    assert {8, 32, 64} <= {st.kw.get("tile", 0) or 32 for st in after}
+    # both states advanced without a reset after the first update, then reset, advanced and read
+    seq = kinds[at["turn30"]:at["lowered"]]
+    assert seq.count("sppm_render") == 4 and seq.count("sppm_reset") == 2 and seq.count("sppm_state") == 2
+    assert seq.index("sppm_render") < seq.index("sppm_reset") < len(seq) - 1 - seq[::-1].index("sppm_render")
+    for i, st in enumerate(s.steps):
+        if st.kind in ("pt", "ppm") and st.kw.get("flags", 0) & sc.COUNT_WORK:
+            assert kinds[i + 1] == "stats"
+    # set_groups none and file around an update, each followed by BDPT
+    assert kinds[at["shrunk"] - 2:at["shrunk"] + 3] == ["set_groups", "bdpt", "update_triangles", "set_groups", "bdpt"]
+    assert [s.steps[at["shrunk"] + d].kw["which"] for d in (-2, 1)] == ["none", "file"]
+    # the end: the builder's records, the first round's PT and BDPT steps again, statistics
+    assert kinds[at["base"]:] == ["update_triangles", "export_bvh", "pt", "bdpt", "stats"]
+    assert [st.repeat_of for st in s.steps[-3:-1]] == [1, 2] and kinds[1:3] == ["pt", "bdpt"]
+    ex = sc.expected(orc, s)
+    assert [ex[i] for i, _ in ups] == [dict(updates=n + 1, live_tris=1872 - d, dead_tris=d) for n, d in enumerate((0, 0, 20, 0, 0))]
+
+
+def test_session_g_rank_group_straddles_an_update(orc):
+    s = sc.session("G")
+    ex, notes = sc.expected(orc, s), sc.notes(orc, s)
+    end = [i for i, st in enumerate(s.steps) if st.kind == "untile"]
+    assert len(end) == 1
+    ranks = [i for i, st in enumerate(s.steps) if st.kind == "pt_device_rank"]
+    assert [s.steps[i].kw["rank"] for i in ranks] == [0, 1, 2] and s.steps[ranks[2]].kw["flags"] == sc.NO_HOST_WAIT
+    assert [st.kind for st in s.steps[ranks[0] + 1:ranks[1]]] == ["update_triangles"]
+    rows = notes[end[0]]["rows"]
+    assert rows[0].tobytes() != rows[1].tobytes() and rows[1].tobytes() == rows[2].tobytes()
+    mixed = ex[end[0]]["image"]
+    shares = [rc.changed_share(mixed, r) for r in rows[:2]]
+    print("G: the assembled image differs from rank 0's scene in %.3f of the pixels, from rank 1's in %.3f" % tuple(shares))
+    assert min(shares) > 0.0
+    for r, i in enumerate(ranks):                 # and every rank has pixels of its own to show
+        assert np.asarray(ex[i]["local"]).any(), r
