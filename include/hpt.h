@@ -572,8 +572,9 @@ void hpt_display_destroy(hpt_display *d);
  * second moment ("temporal variance", below).  Without it the variance-guided filter estimates the variance of every
  * frame spatially and divides by hpt_history_length's n.  The guide position is an average
  * over jittered samples, so pixels that straddle an edge mostly fail the direct-view or the plane test and restart.
- * There are no motion vectors: geometry that moves ("scene updates", below) is not followed -- reset the history after an
- * update.  Once n reaches max_history the mean turns into an
+ * hpt_history_advance has no motion vectors: geometry that moves ("scene updates", below) is followed only by
+ * hpt_history_advance_motion with the motion guide ("motion", below); a history that is not given that guide is reset
+ * after an update.  Once n reaches max_history the mean turns into an
  * exponential average with weight 1 / max_history for the new frame, which is what lets lighting seen from a new angle
  * (a highlight, a reflection) converge to its new value instead of keeping the old one forever. */
 typedef struct hpt_history hpt_history;
@@ -776,8 +777,9 @@ int hpt_trace_visibility(hpt_scene *scene, const float *p1, const float *p2, int
  * What the caller keeps in step: an hpt_sppm state created before an update renders the new scene, but still holds
  * the statistics gathered on the old one and the bounds it took when it was created or last reset -- reset it
  * (hpt_sppm_reset re-reads the bounds the state was created without; bounds handed to hpt_sppm_create are the
- * caller's to keep right) or recreate it (not checked).  hpt_history and hpt_accum have no motion vectors for moving
- * geometry: with a still camera they would average two scenes, so reset them after an update.
+ * caller's to keep right) or recreate it (not checked).  hpt_accum has no motion vectors for moving geometry: with a
+ * still camera it would average two scenes, so reset it after an update.  hpt_history follows the geometry when it is
+ * given the motion guide, in the per-frame call order of "motion" below; without that guide it is reset like hpt_accum.
  *
  * hpt_scene_get_update_info describes the last hpt_scene_update_triangles (zeros before the first): how many have been
  * made, how many triangles were live and dead, and the milliseconds of packing the vertices (36 bytes per triangle),
@@ -789,7 +791,7 @@ int hpt_trace_visibility(hpt_scene *scene, const float *p1, const float *p2, int
  *
  * Out of scope: vertices handed over as a device pointer; topology changes and automatic rebuilds (a caller whose
  * geometry has moved far destroys and creates); hpt_multi_* and the scene the one-shot wrappers keep, which compare
- * bytes and rebuild as before; pt_cli, whose loop has no notion of a scene over time. */
+ * bytes and rebuild as before.  (pt_cli turns an OBJ's triangles between frames with --spin, "motion" below.) */
 typedef struct hpt_update_info {
     uint64_t updates, live_tris, dead_tris;
     double ms_pack, ms_upload, ms_refit;
@@ -801,6 +803,86 @@ int hpt_scene_get_update_info(const hpt_scene *scene, hpt_update_info *out);
 int hpt_bvh_refit_host(const void *lights, int num_lights, const void *spheres, int num_spheres, const void *triangles,
                        const void *new_triangles, int num_triangles, hpt_bvh_info *info,
                        void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);
+
+/* ---- motion ---------------------------------------------------------------------------------------------
+ * hpt_history keeps a viewer's accumulation when the camera moves, and the scene updates move the geometry in place; this
+ * is what joins them.  The scene remembers one previous geometry, a fifth guide image says where each pixel's surface
+ * point was one frame ago, and a history advance that projects THAT point into the previous camera follows geometry
+ * that moves.  A pixel of static geometry under a still camera stays a plain running mean, bit for bit.
+ *
+ * Per frame, a viewer calls, in this order:
+ *   hpt_scene_update_triangles / hpt_scene_update_rounds     this frame's geometry (any number of them, or none)
+ *   hpt_render_guides_motion[_device]                        the four guides and prev_position
+ *   hpt_render_pt_device (or any integrator), hpt_untile     the frame
+ *   hpt_history_advance_motion                               the frame into the history, through prev_position
+ *   hpt_scene_keep_previous                                  this frame's geometry becomes the next frame's previous one
+ *
+ * The previous geometry.  A scene has its current geometry G (what hpt_scene_create and the updates have made it) and a
+ * previous geometry G'; at creation G' = G.  The updates change G only.  hpt_scene_keep_previous sets G' := G; it is
+ * blocking and runs on the null stream, like the updates.  Several updates inside one frame are all measured against the
+ * same G'.  hpt_scene_has_motion returns 1 if any update succeeded since creation or since the last
+ * hpt_scene_keep_previous, else 0, and < 0 on a null scene (a host flag, no device work).  G' holds the nine vertex
+ * floats of every triangle in input order (36 bytes per triangle) and centre and radius of every sphere (16 bytes); it is
+ * allocated by the first update, so a scene that is never updated pays nothing.  Lights and light balls have no previous
+ * state: a light ball never becomes a hit point.  A dead triangle (non-finite edge) has non-finite previous vertices.
+ * hpt_scene_keep_previous returns HPT_ERR_INVALID with a message, before the device is touched, for a null scene or a
+ * current device other than the scene's.
+ *
+ * The motion guide.  hpt_render_guides_motion and hpt_render_guides_motion_device are hpt_render_guides and
+ * hpt_render_guides_device with a fifth output, prev_position (W*H*3 floats).  With prev_position NULL they ARE those
+ * calls: the same refusals and the same bytes; "not all outputs NULL" counts five outputs, and the four other images are
+ * the same bytes whether or not prev_position is asked for.  IEEE float, evaluated as written, left to right, dot as
+ * defined for the history.  Sample s of pixel p that ends in a hit point X on a primitive adds Y to a fifth per-pixel sum
+ * Pprev, in sample order beside P:
+ *   triangle with input index i, current vertices a0, a1, a2 and previous vertices b0, b1, b2.  If the 36 bytes of the two
+ *     sets are equal, Y = X, the same bits.  Otherwise e1 = a1 - a0, e2 = a2 - a0, d = X - a0;
+ *     d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2), d20 = dot(d, e1), d21 = dot(d, e2);
+ *     den = d00 * d11 - d01 * d01;  beta = (d11 * d20 - d01 * d21) / den;  gamma = (d00 * d21 - d01 * d20) / den;
+ *     f1 = b1 - b0, f2 = b2 - b0;  Y = (b0 + f1 * beta) + f2 * gamma per component.
+ *   sphere j, current centre and radius c, r and previous c', r'.  If the 16 bytes are equal, Y = X.  Otherwise
+ *     k = r' / r and Y = c' + (X - c) * k per component.
+ * Nothing is special-cased: a zero den, or previous vertices that were dead, give a non-finite Y.  It poisons the pixel's
+ * sum, and the history's range test then restarts that pixel (NaN fails every comparison there).
+ * prev_position = Pprev / (float) C per channel, zero where C = 0, exactly as position is resolved.  On a scene whose G'
+ * equals G byte for byte prev_position therefore equals position bit for bit, at any spp.
+ *
+ * hpt_history_advance_motion is hpt_history_advance with a sixth image, d_prev_position; hpt_history_motion_check is
+ * hpt_history_check with it.  With d_prev_position NULL both ARE those calls, byte for byte.  With it the three guides
+ * must be given, and it may not overlap d_mean_out or the frame.  Write X = position[p], Xp = prev_position[p],
+ * N = normal[p]; "still": the camera's 84 bytes equal the previous advance's; "same": the three words of Xp equal those of
+ * X bitwise.  Steps 1, 5 and 6 of hpt_history_advance, the counts, the second moment (q rides along exactly as in
+ * "temporal variance": where m is the pixel's own record, q_r is its own q) and the stored state are unchanged -- the pixel
+ * stores X, N and coverage of this frame, never Xp.  Steps 2 to 4 become:
+ *   2'. no hit point (coverage[p] > 0 is false): if still and coverage_prev[p] > 0 is also false, m = mean[p], n_r = n[p]
+ *       (sky stays sky); otherwise n_r = 0 (something was there a frame ago).
+ *   3'. still and same: one tap, the pixel's own previous record, weight 1 and no division.  It is taken when
+ *       coverage_prev[p] > 0 holds and the tap passes the plane test t = dot(N, position_prev[p] - X),
+ *       t * t <= tol2 * P.dist2 with P = project(this camera, X), and the normal test dot(N, normal_prev[p]) >= normal_min,
+ *       each when it is on.  Taken: m = mean_prev[p], n_r = n_prev[p], the same bits; otherwise n_r = 0.  This restarts a
+ *       wall pixel the moving object covered one frame ago and keeps every other static pixel an exact running mean.
+ *   4'. everything else: the direct-view test as in step 4, with X and this camera; the range test with
+ *       Q = project(previous camera, Xp); the taps as in step 4 with the plane test t = dot(N, position_prev[q] - Xp)
+ *       against tol2 * P.dist2 and the normal test with the current N; the result rule unchanged (wsum > 0.01f).
+ * Limit: both tap tests use the CURRENT normal, so geometry that turns by more than acos(normal_min) per frame (about 25
+ * degrees at the default) restarts; a turn of a few degrees does not.  There is no previous-normal guide.  Motion seen
+ * through a mirror or glass bounce is not followed: those pixels fail the direct-view test and restart, as before.
+ *
+ * pt_cli --frames N --obj mesh.obj --spin DEG turns the OBJ's triangles by f * DEG degrees (from the original vertices,
+ * so rounding does not accumulate) about the vertical axis through their centroid before frame f and calls
+ * hpt_scene_update_triangles; with --reproject the frames go through the call order above, without it the accumulation
+ * is reset after every update. */
+int hpt_scene_keep_previous(hpt_scene *scene);
+int hpt_scene_has_motion(const hpt_scene *scene);
+int hpt_render_guides_motion(hpt_scene *scene, const void *camera, int W, int H, int spp, const hpt_params *params,
+                             float *albedo, float *normal, float *position, float *coverage, float *prev_position);
+int hpt_render_guides_motion_device(hpt_scene *scene, const void *camera, int W, int H, int spp, const hpt_params *params,
+                                    void *d_albedo, void *d_normal, void *d_position, void *d_coverage, void *d_prev_position);
+int hpt_history_advance_motion(hpt_history *h, const void *camera, const void *d_frame_rgb,
+                               const void *d_normal, const void *d_position, const void *d_coverage,
+                               const void *d_prev_position, const hpt_history_params *p, void *d_mean_out, void *hip_stream);
+int hpt_history_motion_check(int W, int H, const void *camera, const void *d_frame_rgb,
+                             const void *d_normal, const void *d_position, const void *d_coverage,
+                             const void *d_prev_position, const hpt_history_params *p, const void *d_mean_out);
 
 #ifdef __cplusplus
 }

@@ -180,7 +180,8 @@ def load_library() -> C.CDLL:
                      "hpt_denoiser_run_guided", "hpt_denoiser_estimate_variance", "hpt_history_length", "hpt_guided_check",
                      "hpt_history_create_flags", "hpt_history_variance", "hpt_history_read_moments", "hpt_history_variance_check",
                      "hpt_scene_update_triangles", "hpt_scene_update_rounds", "hpt_scene_update_check", "hpt_scene_get_update_info",
-                     "hpt_bvh_refit_host"):
+                     "hpt_bvh_refit_host", "hpt_scene_keep_previous", "hpt_scene_has_motion", "hpt_render_guides_motion",
+                     "hpt_render_guides_motion_device", "hpt_history_advance_motion", "hpt_history_motion_check"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -325,25 +326,37 @@ class Scene:
         The scene must stay open while the state lives."""
         return Sppm(self, camera, W, H, eye_depth, light_depth, spl, radius, alpha, params, scene_min, scene_max)
 
-    def render_guides(self, camera, W, H, spp=4, params: Params | None = None) -> dict:
+    def render_guides(self, camera, W, H, spp=4, params: Params | None = None, prev_position=False) -> dict:
         """First-hit guide images for the denoiser (include/hpt.h, hpt_render_guides): the means over spp eye-pass samples
         of base colour, ray-facing normal and position of the first non-delta surface, and the number of samples that
-        found one.  dict(albedo, normal, position: float32 [H, W, 3]; coverage: float32 [H, W])."""
+        found one.  dict(albedo, normal, position: float32 [H, W, 3]; coverage: float32 [H, W]); with prev_position=True
+        also prev_position [H, W, 3], where each pixel's point was in the scene's previous geometry
+        (hpt_render_guides_motion)."""
         params = params or make_params()
         cam = np.ascontiguousarray(camera, CAMERA)
         g = dict(albedo=np.empty((H, W, 3), np.float32), normal=np.empty((H, W, 3), np.float32),
                  position=np.empty((H, W, 3), np.float32), coverage=np.empty((H, W), np.float32))
+        if prev_position:
+            g["prev_position"] = np.empty((H, W, 3), np.float32)
+            _check(self._lib.hpt_render_guides_motion(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), _vp(g["albedo"]),
+                                                      _vp(g["normal"]), _vp(g["position"]), _vp(g["coverage"]), _vp(g["prev_position"])))
+            return g
         _check(self._lib.hpt_render_guides(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), _vp(g["albedo"]),
                                            _vp(g["normal"]), _vp(g["position"]), _vp(g["coverage"])))
         return g
 
     def render_guides_device(self, camera, W, H, spp=4, params: Params | None = None, albedo=None, normal=None, position=None,
-                             coverage=None):
+                             coverage=None, prev_position=None):
         """render_guides into DEVICE images (ints or torch tensors, float32, [H, W, 3]; coverage [H, W]; None = not
-        wanted, at least one is): the same bytes, complete when the call returns."""
+        wanted, at least one is): the same bytes, complete when the call returns.  prev_position: the motion guide
+        (hpt_render_guides_motion_device)."""
         params = params or make_params()
         cam = np.ascontiguousarray(camera, CAMERA)
         ptr = [_dptr(x) if x is not None else None for x in (albedo, normal, position, coverage)]
+        if prev_position is not None:
+            _check(self._lib.hpt_render_guides_motion_device(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), *ptr,
+                                                             _dptr(prev_position)))
+            return
         _check(self._lib.hpt_render_guides_device(self._h, _vp(cam.reshape(1)), W, H, int(spp), C.byref(params), *ptr))
 
     def stats(self) -> dict:
@@ -372,6 +385,18 @@ class Scene:
     def update_check(self, triangles):
         """Raises HptError where update_triangles would refuse these records; no device work."""
         update_check(self, triangles)
+
+    def keep_previous(self):
+        """The current geometry becomes the previous one (include/hpt.h, "motion"): once per frame, after the frame's
+        guides and before the next frame's updates.  Blocking."""
+        _check(self._lib.hpt_scene_keep_previous(self._h))
+
+    def has_motion(self) -> bool:
+        """True when an update succeeded since the scene was created or keep_previous() was last called."""
+        rc = int(self._lib.hpt_scene_has_motion(self._h))
+        if rc < 0:
+            _check(1)
+        return rc == 1
 
     def update_info(self) -> dict:
         """The last update_triangles: dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
@@ -535,6 +560,17 @@ def guided_check(W, H, linear_rgb, variance, out, variance_out=None, params: Gui
                                            C.byref(params) if params is not None else None))
 
 
+def history_motion_check(W, H, camera, frame, normal=None, position=None, coverage=None, prev_position=None,
+                         params: HistoryParams | None = None, mean_out=None) -> None:
+    """Every argument check of History.advance with the motion guide on a W x H history, without a history or a device
+    (hpt_history_motion_check); raises HptError as the advance would.  Images are device pointers (ints) or tensors."""
+    opt = lambda x: _dptr(x) if x is not None else None
+    cam = np.ascontiguousarray(camera, CAMERA).reshape(1) if camera is not None else None
+    _check(load_library().hpt_history_motion_check(int(W), int(H), _vp(cam) if cam is not None else None, opt(frame), opt(normal),
+                                                   opt(position), opt(coverage), opt(prev_position),
+                                                   C.byref(params) if params is not None else None, opt(mean_out)))
+
+
 def history_variance_check(W, H, out, fallback=None, min_length=0.0, moments=True) -> None:
     """Every argument check of History.variance on a W x H history, without a history or a device
     (hpt_history_variance_check); raises HptError as the call would."""
@@ -661,10 +697,16 @@ class History:
             _check(self._lib.hpt_history_create(int(W), int(H), C.byref(self._h)))
 
     def advance(self, camera, frame, normal=None, position=None, coverage=None, params: HistoryParams | None = None, mean_out=None,
-                stream: int = 0):
-        """mean_out (may be `frame` itself) receives the new mean; params None = the defaults."""
+                stream: int = 0, prev_position=None):
+        """mean_out (may be `frame` itself) receives the new mean; params None = the defaults.  prev_position (DEVICE,
+        W*H*3, of Scene.render_guides_device) makes the advance follow moving geometry (hpt_history_advance_motion)."""
         cam = np.ascontiguousarray(camera, CAMERA)
         opt = [_dptr(x) if x is not None else None for x in (normal, position, coverage)]
+        if prev_position is not None:
+            _check(self._lib.hpt_history_advance_motion(self._h, _vp(cam.reshape(1)), _dptr(frame), opt[0], opt[1], opt[2],
+                                                        _dptr(prev_position), C.byref(params) if params is not None else None,
+                                                        _dptr(mean_out) if mean_out is not None else None, C.c_void_p(stream)))
+            return
         _check(self._lib.hpt_history_advance(self._h, _vp(cam.reshape(1)), _dptr(frame), opt[0], opt[1], opt[2],
                                              C.byref(params) if params is not None else None,
                                              _dptr(mean_out) if mean_out is not None else None, C.c_void_p(stream)))

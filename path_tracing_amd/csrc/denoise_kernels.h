@@ -12,12 +12,24 @@ struct GuideAccum {
     float4 *alb_cnt;     // sum of base colours xyz | number of samples that ended in a hit point (uint32 bits)
     float4 *nrm;         // sum of ray-facing normals xyz | unused
     float4 *pos;         // sum of positions xyz | unused
+    float4 *prev;        // sum of previous positions xyz | unused (the motion guide; `pos` again where nothing has moved)
+};
+
+// The scene's current and previous geometry as the motion guide reads them (include/hpt.h, "motion"): nine vertex floats
+// per triangle in input order, and centre | radius per sphere.  The current spheres are sc.rounds.
+struct GuideMotion {
+    const float *verts, *prev_verts;
+    const float4 *prev_rounds;
 };
 
 // one lane per entry of hb.list (their number in *hp_count): the lane owns its pixel slot, plain loads and stores
 void launch_guides_accumulate(hipStream_t s, const SceneDev &sc, PpmHitBuf hb, const uint32_t *hp_count, uint32_t max_items, GuideAccum ga);
-// d_local[3 p ..] = the mean of `which` (0 albedo, 1 normal, 2 position; zero where the count is zero) or, which = 3,
-// (count, 0, 0), for launch_untile
+// the same sums plus ga.prev: where each hit point was in the previous geometry; `hit` is the eye pass's PathBuf::hit,
+// whose primitive code a finished path keeps
+void launch_guides_accumulate_motion(hipStream_t s, const SceneDev &sc, PpmHitBuf hb, const uint2 *hit, const uint32_t *hp_count,
+                                     uint32_t max_items, GuideAccum ga, GuideMotion gm);
+// d_local[3 p ..] = the mean of `which` (0 albedo, 1 normal, 2 position, 4 previous position; zero where the count is
+// zero) or, which = 3, (count, 0, 0), for launch_untile
 void launch_guides_resolve(hipStream_t s, uint32_t n_local, GuideAccum ga, int which, float *d_local);
 
 // The filter's packed records, one per pixel of the row-major image.

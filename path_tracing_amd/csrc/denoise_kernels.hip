@@ -1,13 +1,14 @@
 // HIP kernels of the guide buffers and the denoiser (include/hpt.h, "guides and denoiser"), written for gfx950 (MI355X).
 //
 //   guides    hpt_render_guides runs photon mapping's eye pass (ppm_kernels.hip, unchanged) once per sample; after each,
-//             k_guides_accumulate adds the hit points' base colour, normal and position into per-pixel sums, and
+//             k_guides_accumulate adds the hit points' base colour, normal and position into per-pixel sums
+//             (k_guides_accumulate_motion also where each hit point was in the scene's previous geometry), and
 //             k_guides_resolve forms the means for launch_untile.
 //   denoiser  k_denoise_pack turns the guide images into 16-byte records, k_denoise_pack_color forms c_0, and k_atrous
 //             runs one level of the edge-avoiding a-trous filter per launch.
 //
 // Everything is IEEE float arithmetic evaluated as written (-ffp-contract=off, correctly rounded divide), with no
-// transcendental and no atomic: the CPU restatements (tests/guides_oracle.cpp, tests/denoise_oracle.cpp) give the same bits.
+// transcendental and no atomic: the CPU restatements (tests/guides_oracle.cpp, tests/motion_oracle.cpp, tests/denoise_oracle.cpp) give the same bits.
 #include "denoise_kernels.h"
 #include "pt_device_math.h"
 
@@ -34,6 +35,57 @@ void k_guides_accumulate(SceneDev sc, PpmHitBuf hb, const uint32_t *hp_count, Gu
     ga.alb_cnt[slot] = a; ga.nrm[slot] = sn; ga.pos[slot] = sp;
 }
 
+// dot as the history defines it (include/hpt.h): left to right
+HPT_DEV float dot_lr(f3 a, f3 b){ return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// Where the hit point X on primitive code `prim` (PathBuf::hit.y) was in the previous geometry (include/hpt.h, "motion").
+// A primitive whose current and previous bytes are equal returns X itself; nothing else is special-cased, so a zero
+// denominator or dead previous vertices give a non-finite point.
+HPT_DEV f3 previous_point(const SceneDev &sc, const GuideMotion &gm, uint32_t prim, f3 X){
+    if(prim & kHitRoundFlag){
+        const uint32_t j = prim & 0x7FFFFFFFu;                   // a hit point is never on a light ball: j < num_spheres
+        const DevRound rr = sc.rounds[j];
+        const float4 q = gm.prev_rounds[j];
+        if(__float_as_uint(rr.c[0]) == __float_as_uint(q.x) && __float_as_uint(rr.c[1]) == __float_as_uint(q.y) && __float_as_uint(rr.c[2]) == __float_as_uint(q.z) && __float_as_uint(rr.r) == __float_as_uint(q.w)) return X;
+        const float k = q.w / rr.r;
+        return mk3(q.x + (X.x - rr.c[0]) * k, q.y + (X.y - rr.c[1]) * k, q.z + (X.z - rr.c[2]) * k);
+    }
+    const uint32_t i = __float_as_uint(sc.tris[(size_t) prim * 3].w) - (uint32_t) sc.num_rounds;       // scan ordinal -> input index
+    const float *a = gm.verts + (size_t) i * 9, *b = gm.prev_verts + (size_t) i * 9;
+    float av[9], bv[9];
+    bool same = true;
+#pragma unroll
+    for(int k = 0; k < 9; ++k){ av[k] = a[k]; bv[k] = b[k]; same = same && __float_as_uint(av[k]) == __float_as_uint(bv[k]); }
+    if(same) return X;
+    const f3 a0 = mk3(av[0], av[1], av[2]), b0 = mk3(bv[0], bv[1], bv[2]);
+    const f3 e1 = mk3(av[3] - a0.x, av[4] - a0.y, av[5] - a0.z), e2 = mk3(av[6] - a0.x, av[7] - a0.y, av[8] - a0.z);
+    const f3 d = mk3(X.x - a0.x, X.y - a0.y, X.z - a0.z);
+    const float d00 = dot_lr(e1, e1), d01 = dot_lr(e1, e2), d11 = dot_lr(e2, e2), d20 = dot_lr(d, e1), d21 = dot_lr(d, e2);
+    const float den = d00 * d11 - d01 * d01;
+    const float beta = (d11 * d20 - d01 * d21) / den, gamma = (d00 * d21 - d01 * d20) / den;
+    const f3 f1 = mk3(bv[3] - b0.x, bv[4] - b0.y, bv[5] - b0.z), f2 = mk3(bv[6] - b0.x, bv[7] - b0.y, bv[8] - b0.z);
+    return mk3((b0.x + f1.x * beta) + f2.x * gamma, (b0.y + f1.y * beta) + f2.y * gamma, (b0.z + f1.z * beta) + f2.z * gamma);
+}
+
+// k_guides_accumulate plus the fifth sum.  The same single-owner argument: entry i's lane alone touches its pixel slot.
+__global__ __launch_bounds__(kBlock)
+void k_guides_accumulate_motion(SceneDev sc, PpmHitBuf hb, const uint2 *hit, const uint32_t *hp_count, GuideAccum ga, GuideMotion gm){
+    const uint32_t count = *hp_count;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if(i >= count) return;
+    const uint32_t slot = hb.list[i];
+    const float4 pm = hb.pos_mat[slot], n = hb.nrm[slot];
+    const DevMaterial &dm = sc.mats[__float_as_uint(pm.w)];
+    float4 a = ga.alb_cnt[slot], sn = ga.nrm[slot], sp = ga.pos[slot], sq = ga.prev[slot];
+    a.x = a.x + dm.base[0]; a.y = a.y + dm.base[1]; a.z = a.z + dm.base[2];
+    a.w = __uint_as_float(__float_as_uint(a.w) + 1u);
+    sn.x = sn.x + n.x; sn.y = sn.y + n.y; sn.z = sn.z + n.z;
+    sp.x = sp.x + pm.x; sp.y = sp.y + pm.y; sp.z = sp.z + pm.z;
+    const f3 Y = previous_point(sc, gm, hit[slot].y, mk3(pm.x, pm.y, pm.z));
+    sq.x = sq.x + Y.x; sq.y = sq.y + Y.y; sq.z = sq.z + Y.z;
+    ga.alb_cnt[slot] = a; ga.nrm[slot] = sn; ga.pos[slot] = sp; ga.prev[slot] = sq;
+}
+
 __global__ __launch_bounds__(kBlock)
 void k_guides_resolve(uint32_t n_local, GuideAccum ga, int which, float *d_local){
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
@@ -43,7 +95,7 @@ void k_guides_resolve(uint32_t n_local, GuideAccum ga, int which, float *d_local
     float x = 0.0f, y = 0.0f, z = 0.0f;
     if(which == 3) x = c;
     else if(c > 0.0f){
-        const float4 *src = which == 0 ? ga.alb_cnt : which == 1 ? ga.nrm : ga.pos;
+        const float4 *src = which == 0 ? ga.alb_cnt : which == 1 ? ga.nrm : which == 4 ? ga.prev : ga.pos;
         const float4 v = src[p];
         x = v.x / c; y = v.y / c; z = v.z / c;
     }
@@ -155,6 +207,12 @@ inline uint32_t blocks_for(size_t n){ return (uint32_t) ((n + kBlock - 1) / kBlo
 void launch_guides_accumulate(hipStream_t s, const SceneDev &sc, PpmHitBuf hb, const uint32_t *hp_count, uint32_t max_items, GuideAccum ga){
     if(max_items == 0u) return;
     hipLaunchKernelGGL(k_guides_accumulate, dim3(blocks_for(max_items)), dim3(kBlock), 0, s, sc, hb, hp_count, ga);
+}
+
+void launch_guides_accumulate_motion(hipStream_t s, const SceneDev &sc, PpmHitBuf hb, const uint2 *hit, const uint32_t *hp_count,
+                                     uint32_t max_items, GuideAccum ga, GuideMotion gm){
+    if(max_items == 0u) return;
+    hipLaunchKernelGGL(k_guides_accumulate_motion, dim3(blocks_for(max_items)), dim3(kBlock), 0, s, sc, hb, hit, hp_count, ga, gm);
 }
 
 void launch_guides_resolve(hipStream_t s, uint32_t n_local, GuideAccum ga, int which, float *d_local){

@@ -80,12 +80,13 @@ int resolve_params(const hpt_history_params *p, Resolved &r){
 
 // every check of an advance that needs no handle; fills the camera constants and the resolved parameters
 int check_advance(int W, int H, const void *camera, const void *frame, const void *normal, const void *position, const void *coverage,
-                  const hpt_history_params *p, const void *mean_out, HistoryCamera &cam, Resolved &res){
+                  const void *prev_position, const hpt_history_params *p, const void *mean_out, HistoryCamera &cam, Resolved &res){
     if(int rc = check_size(W, H)) return rc;
     if(!camera) return fail(HPT_ERR_INVALID, "null camera");
     if(!frame) return fail(HPT_ERR_INVALID, "null frame");
     const int given = (normal ? 1 : 0) + (position ? 1 : 0) + (coverage ? 1 : 0);
     if(given != 0 && given != 3) return fail(HPT_ERR_INVALID, "hpt_history_advance: the guide images are given all three or not at all");
+    if(prev_position && given != 3) return fail(HPT_ERR_INVALID, "hpt_history_advance_motion: d_prev_position needs the three guide images");
     if(int rc = resolve_params(p, res)) return rc;
     if(!camera_constants(camera, cam)) return fail(HPT_ERR_INVALID, "hpt_history_advance: degenerate camera (its constants are not finite, or UL - eye lies in the image plane)");
     const size_t npx = (size_t) W * H;
@@ -97,6 +98,8 @@ int check_advance(int W, int H, const void *camera, const void *frame, const voi
         if(overlap(ptr[i], bytes[i], ptr[j], bytes[j]))
             return fail(HPT_ERR_INVALID, "hpt_history_advance: the images must not overlap (d_mean_out may be d_frame_rgb itself)");
     }
+    if(prev_position && (overlap(prev_position, npx * 12, frame, npx * 12) || (mean_out && overlap(prev_position, npx * 12, mean_out, npx * 12))))
+        return fail(HPT_ERR_INVALID, "hpt_history_advance_motion: d_prev_position must not overlap d_frame_rgb or d_mean_out");
     return HPT_OK;
 }
 
@@ -141,8 +144,13 @@ extern "C" {
 
 int hpt_history_check(int W, int H, const void *camera, const void *d_frame_rgb, const void *d_normal, const void *d_position,
                       const void *d_coverage, const hpt_history_params *p, const void *d_mean_out){
+    return hpt_history_motion_check(W, H, camera, d_frame_rgb, d_normal, d_position, d_coverage, nullptr, p, d_mean_out);
+}
+
+int hpt_history_motion_check(int W, int H, const void *camera, const void *d_frame_rgb, const void *d_normal, const void *d_position,
+                             const void *d_coverage, const void *d_prev_position, const hpt_history_params *p, const void *d_mean_out){
     HistoryCamera cam; Resolved res;
-    return check_advance(W, H, camera, d_frame_rgb, d_normal, d_position, d_coverage, p, d_mean_out, cam, res);
+    return check_advance(W, H, camera, d_frame_rgb, d_normal, d_position, d_coverage, d_prev_position, p, d_mean_out, cam, res);
 }
 
 int hpt_history_variance_check(int W, int H, int32_t create_flags, const void *d_fallback, float min_length, const void *d_variance_out){
@@ -184,14 +192,22 @@ void hpt_history_destroy(hpt_history *h){ delete h; }
 
 int hpt_history_advance(hpt_history *h, const void *camera, const void *d_frame_rgb, const void *d_normal, const void *d_position,
                         const void *d_coverage, const hpt_history_params *p, void *d_mean_out, void *hip_stream){
+    return hpt_history_advance_motion(h, camera, d_frame_rgb, d_normal, d_position, d_coverage, nullptr, p, d_mean_out, hip_stream);
+}
+
+int hpt_history_advance_motion(hpt_history *h, const void *camera, const void *d_frame_rgb, const void *d_normal, const void *d_position,
+                               const void *d_coverage, const void *d_prev_position, const hpt_history_params *p, void *d_mean_out,
+                               void *hip_stream){
     if(!h) return fail(HPT_ERR_INVALID, "null history");
     HistoryArgs a{};
     Resolved res;
-    if(int rc = check_advance(h->W, h->H, camera, d_frame_rgb, d_normal, d_position, d_coverage, p, d_mean_out, a.cam, res)) return rc;
+    if(int rc = check_advance(h->W, h->H, camera, d_frame_rgb, d_normal, d_position, d_coverage, d_prev_position, p, d_mean_out, a.cam, res)) return rc;
     if(int rc = on_device(h->device)) return rc;
     hipStream_t st = (hipStream_t) hip_stream;
-    a.mode = h->frames == 0 ? kHistoryFirst : memcmp(camera, h->camera, HPT_CAMERA_BYTES) == 0 ? kHistoryIdentity : kHistoryMoved;
-    const int next = a.mode == kHistoryMoved ? h->cur ^ 1 : h->cur;       // only a moved frame reads its neighbours
+    const bool still = h->frames != 0 && memcmp(camera, h->camera, HPT_CAMERA_BYTES) == 0;
+    a.mode = h->frames == 0 ? kHistoryFirst : d_prev_position ? kHistoryMotion : still ? kHistoryIdentity : kHistoryMoved;
+    a.prev_position = (const float *) d_prev_position; a.still = still ? 1 : 0;
+    const int next = a.mode >= kHistoryMoved ? h->cur ^ 1 : h->cur;       // only a moved or motion frame reads other pixels' records
     a.prev = h->set(h->cur); a.next = h->set(next);
     if(h->moments()){ a.sq_prev = h->sq[h->cur].get(); a.sq_next = h->sq[next].get(); }
     a.frame = (const float *) d_frame_rgb; a.normal = (const float *) d_normal; a.position = (const float *) d_position;

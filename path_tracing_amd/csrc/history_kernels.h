@@ -20,7 +20,8 @@ struct HistorySet {
     float4 *nrm;         // normal.xyz, 0
 };
 
-enum HistoryMode : int { kHistoryFirst = 0, kHistoryIdentity = 1, kHistoryMoved = 2 };
+// kHistoryMotion: a frame that comes with the motion guide (include/hpt.h, "motion"), whatever the camera did
+enum HistoryMode : int { kHistoryFirst = 0, kHistoryIdentity = 1, kHistoryMoved = 2, kHistoryMotion = 3 };
 
 struct HistoryArgs {
     HistorySet prev, next;           // first / identity: the kernel works in place on `next` (prev == next)
@@ -40,6 +41,10 @@ struct HistoryArgs {
     // behind everything else, so the kernels without moments read the arguments they always read from where they always were.
     const float4 *sq_prev;
     float4 *sq_next;
+    // kHistoryMotion only: where each pixel's guide point was one frame ago (3 W H), and whether the camera's bytes are
+    // the previous advance's.  Last, for the same reason.
+    const float *prev_position;
+    int still;
 };
 // one lane per pixel; the grid depends on W and H only.  sq_next selects the kernels that carry the second moment.
 void launch_history_advance(hipStream_t s, const HistoryArgs &a);

@@ -4,7 +4,8 @@
 //                      create or reset and a frame from an unmoved camera touch the pixel's own records only and work in
 //                      place; a frame from a moved camera projects the pixel's guide point into the previous camera, reads
 //                      up to four neighbours' records from the previous set (three 16-byte loads per tap) and writes the
-//                      other set.  MOMENTS (a history created with HPT_HISTORY_MOMENTS) carries the running mean of the
+//                      other set; with the motion guide (kHistoryMotion) the point projected is where the guide point was one
+//                      frame ago, and a pixel whose point has not moved under a still camera keeps its own record.  MOMENTS (a history created with HPT_HISTORY_MOMENTS) carries the running mean of the
 //                      squared frame values through the same steps with the same taps and weights: a fourth 16-byte record
 //                      per pixel and a fourth load per tap.
 //   k_history_variance one lane per pixel, a pure map: the variance of the mean from mean, second moment and length where
@@ -61,11 +62,43 @@ void k_history_advance(HistoryArgs a){
             m = V3{ mp.x, mp.y, mp.z }; n_r = mp.w;
             if(MOMENTS){ const float4 sp = a.sq_prev[p]; m2 = V3{ sp.x, sp.y, sp.z }; }
         }
-        if(MODE == kHistoryMoved && GUIDES && cov > 0.0f){
+        // the point that is looked up in the previous frame: the guide point itself, or with the motion guide where it was then
+        bool taps = MODE == kHistoryMoved && GUIDES && cov > 0.0f;
+        V3 Xr = X;
+        if(MODE == kHistoryMotion){
+            const V3 Xp = ld3(a.prev_position + 3u * p);
+            const bool same = __float_as_uint(Xp.x) == __float_as_uint(X.x) && __float_as_uint(Xp.y) == __float_as_uint(X.y) &&
+                              __float_as_uint(Xp.z) == __float_as_uint(X.z);
+            if(!(cov > 0.0f)){                       // 2': sky stays sky under a still camera, anything else was something
+                if(a.still && !(a.prev.pos_cov[p].w > 0.0f)){
+                    const float4 mp = a.prev.mean_n[p];
+                    m = V3{ mp.x, mp.y, mp.z }; n_r = mp.w;
+                    if(MOMENTS){ const float4 sp = a.sq_prev[p]; m2 = V3{ sp.x, sp.y, sp.z }; }
+                }
+            } else if(a.still && same){              // 3': the pixel's own record, weight 1, no division
+                const float4 pc = a.prev.pos_cov[p];
+                bool take = pc.w > 0.0f;
+                if(take && a.plane_on){
+                    const Projected now = project(a.cam, X);
+                    const float t = dot3(N, V3{ pc.x - X.x, pc.y - X.y, pc.z - X.z });
+                    take = t * t <= a.tol2 * now.dist2;
+                }
+                if(take && a.normal_on){
+                    const float4 nq = a.prev.nrm[p];
+                    take = dot3(N, V3{ nq.x, nq.y, nq.z }) >= a.normal_min;
+                }
+                if(take){
+                    const float4 mp = a.prev.mean_n[p];
+                    m = V3{ mp.x, mp.y, mp.z }; n_r = mp.w;
+                    if(MOMENTS){ const float4 sp = a.sq_prev[p]; m2 = V3{ sp.x, sp.y, sp.z }; }
+                }
+            } else { taps = true; Xr = Xp; }         // 4'
+        }
+        if(taps){
             const uint32_t y = p / (uint32_t) a.W, x = p - y * (uint32_t) a.W;
             const Projected now = project(a.cam, X);
             const bool direct = now.s > 0.0f && fabsf(now.u - ((float) x + 0.5f)) <= 1.0f && fabsf(now.v - ((float) y + 0.5f)) <= 1.0f;
-            const Projected was = project(a.cam_prev, X);
+            const Projected was = project(a.cam_prev, Xr);
             const float up = was.u - 0.5f, vp = was.v - 0.5f;
             // compared in float before any conversion: NaN and infinity end here
             if(direct && was.s > 0.0f && up >= -1.0f && up < (float) a.W && vp >= -1.0f && vp < (float) a.H){
@@ -85,7 +118,7 @@ void k_history_advance(HistoryArgs a){
                         const float4 pc = a.prev.pos_cov[q];
                         if(!(pc.w > 0.0f)) continue;
                         if(a.plane_on){
-                            const float t = dot3(N, V3{ pc.x - X.x, pc.y - X.y, pc.z - X.z });
+                            const float t = dot3(N, V3{ pc.x - Xr.x, pc.y - Xr.y, pc.z - Xr.z });
                             if(!(t * t <= lim)) continue;
                         }
                         if(a.normal_on){
@@ -175,6 +208,8 @@ void launch_advance(hipStream_t s, const dim3 &grid, const dim3 &block, const Hi
     } else if(a.mode == kHistoryIdentity){
         if(g) hipLaunchKernelGGL((k_history_advance<kHistoryIdentity, true, MOMENTS>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((k_history_advance<kHistoryIdentity, false, MOMENTS>), grid, block, 0, s, a);
+    } else if(a.mode == kHistoryMotion){
+        hipLaunchKernelGGL((k_history_advance<kHistoryMotion, true, MOMENTS>), grid, block, 0, s, a);      // the host gives all four guides
     } else {
         if(g) hipLaunchKernelGGL((k_history_advance<kHistoryMoved, true, MOMENTS>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((k_history_advance<kHistoryMoved, false, MOMENTS>), grid, block, 0, s, a);

@@ -60,6 +60,10 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     if((reproject || guided) && motion->guide_spp < 1){ std::cerr << "[Error] --guide-spp must be at least 1" << std::endl; return -1; }
     DeviceMem d_local, d_frame, d_mean, d_rgb8, d_normal, d_position, d_coverage;      // released after L has waited for its stream
     DeviceMem d_albedo, d_variance, d_length, d_filtered;                              // --guided
+    DeviceMem d_prev_position;                                                         // --spin --reproject
+    const bool spin = motion && motion->triangles_at;
+    if(spin && (!run.triangles || run.num_triangles < 1)){ std::cerr << "[Error] --spin: the scene has no triangles" << std::endl; return -1; }
+    std::vector<unsigned char> spun;                                                   // this frame's triangle records
     Loop L;
     if(!d_frame.alloc(values * sizeof(float)) || !d_mean.alloc(values * sizeof(float)) || !d_rgb8.alloc(values) ||
        (!ppm && !d_local.alloc((size_t) n_local * 3 * sizeof(float)))){
@@ -70,6 +74,9 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         if(!d_normal.alloc(values * sizeof(float)) || !d_position.alloc(values * sizeof(float)) || !d_coverage.alloc(values / 3 * sizeof(float))){
             std::cerr << "[Error] --reproject, --guided: out of device memory" << std::endl; return -1;
         }
+    }
+    if(spin && reproject && !d_prev_position.alloc(values * sizeof(float))){
+        std::cerr << "[Error] --spin --reproject: out of device memory" << std::endl; return -1;
     }
     if(guided){
         if(!d_albedo.alloc(values * sizeof(float)) || !d_variance.alloc(values * sizeof(float)) || !d_length.alloc(values / 3 * sizeof(float)) ||
@@ -101,12 +108,21 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         int rc;
         if(motion && motion->camera_at){ memcpy(cam_last, cam_now, sizeof cam_now); motion->camera_at(f, cam_now); }
         const bool moved = motion && motion->camera_at && f > 0 && memcmp(cam_now, cam_last, sizeof cam_now) != 0;
-        const bool guides = (reproject || guided) && (f == 0 || moved);
+        const bool updated = spin && f > 0;
+        if(updated){     // blocking, on the null stream: the last frame's work on the loop's stream has ended with its metrics
+            if(hipError_t e = hipStreamSynchronize(L.stream)) return hip_failed("stream", e);
+            spun.assign((const unsigned char *) run.triangles, (const unsigned char *) run.triangles + (size_t) run.num_triangles * HPT_TRIANGLE_BYTES);
+            motion->triangles_at(f, spun.data(), run.num_triangles);
+            if(hpt_scene_update_triangles(run.scene, spun.data(), run.num_triangles) != HPT_OK) return hpt_failed("hpt_scene_update_triangles");
+        }
+        const bool follow = spin && reproject;          // the motion guide every frame
+        const bool guides = (reproject || guided) && (f == 0 || moved || spin);
         if(guides){      // blocking, on the scene's own stream: before this frame's render is enqueued, after the last frame's metrics
             hpt_params g{};
             g.seed = p.seed; g.sample_offset = p.sample_offset; g.max_delta = p.max_delta; g.tile = p.tile;
-            if(hpt_render_guides_device(run.scene, cam_now, W, H, motion->guide_spp, &g, d_albedo.p, d_normal.p, d_position.p, d_coverage.p) != HPT_OK)
-                return hpt_failed("hpt_render_guides_device");
+            if(hpt_render_guides_motion_device(run.scene, cam_now, W, H, motion->guide_spp, &g, d_albedo.p, d_normal.p, d_position.p, d_coverage.p,
+                                               follow ? d_prev_position.p : nullptr) != HPT_OK)
+                return hpt_failed("hpt_render_guides_motion_device");
             if(guided && hpt_denoiser_set_guides(L.denoiser, d_albedo.p, d_normal.p, d_position.p, d_coverage.p, L.stream) != HPT_OK)
                 return hpt_failed("hpt_denoiser_set_guides");
         }
@@ -123,11 +139,14 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
             if(hpt_untile(d_local.p, d_frame.p, W, H, &p, L.stream) != HPT_OK) return hpt_failed("hpt_untile");
         }
         if(reproject){
-            if(hpt_history_advance(L.history, cam_now, d_frame.p, guides ? d_normal.p : nullptr, guides ? d_position.p : nullptr,
-                                   guides ? d_coverage.p : nullptr, nullptr, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_history_advance");
+            if(hpt_history_advance_motion(L.history, cam_now, d_frame.p, guides ? d_normal.p : nullptr, guides ? d_position.p : nullptr,
+                                          guides ? d_coverage.p : nullptr, follow ? d_prev_position.p : nullptr, nullptr, d_mean.p, L.stream) != HPT_OK)
+                return hpt_failed("hpt_history_advance_motion");
+            // this frame's guides are rendered: its geometry is what the next frame's update is measured against
+            if(follow && hpt_scene_keep_previous(run.scene) != HPT_OK) return hpt_failed("hpt_scene_keep_previous");
             if(guided && hpt_history_length(L.history, d_length.p, L.stream) != HPT_OK) return hpt_failed("hpt_history_length");
         } else {
-            if(moved && hpt_accum_reset(L.accum, L.stream) != HPT_OK) return hpt_failed("hpt_accum_reset");
+            if((moved || updated) && hpt_accum_reset(L.accum, L.stream) != HPT_OK) return hpt_failed("hpt_accum_reset");
             if(hpt_accum_add(L.accum, d_frame.p, d_mean.p, L.stream) != HPT_OK) return hpt_failed("hpt_accum_add");
         }
         if(guided){

@@ -13,7 +13,10 @@ namespace hpt_host {
 // What a frame loop needs of the scene moved for `mode` ("pt", "bdpt" or "ppm"): the single-device handle (null for a
 // fan-out over several devices), its photons / light samples per light, and the run's parameters with the seed taken
 // once, so that every frame of the loop draws from the same streams.  False when nothing was moved.  (scene_model.cpp)
-struct MovedRun { hpt_scene *scene = nullptr; int light_sample = 0; hpt_params params{}; };
+struct MovedRun {
+    hpt_scene *scene = nullptr; int light_sample = 0; hpt_params params{};
+    const void *triangles = nullptr; int num_triangles = 0;      // the moved scene's triangle records (--spin edits copies of them)
+};
 bool moved_run(const std::string &mode, MovedRun &out);
 
 // `frames` frames of `frame_spp` samples (ppm: passes) each, frame f (from 0) with sample_offset = f * frame_spp, every
@@ -43,8 +46,15 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // HPT_HISTORY_MOMENTS, and after hpt_history_length and hpt_denoiser_estimate_variance the loop calls hpt_history_variance
 // in place on the estimate: a pixel whose history is at least four frames long gets its own variance over time, the
 // others keep the spatial estimate.  Without it the loop, its launches and its output are unchanged.
+//
+// With `triangles_at` (--spin) the scene's geometry moves between frames: before frame f > 0 the loop hands it a copy of the
+// moved scene's triangle records, which it edits in place (vertices only), and calls hpt_scene_update_triangles.  Without
+// reproject the accumulator is reset after every update, which is the advice for a history that is not given the motion
+// guide.  With reproject the guides are rendered on every frame with the motion guide (hpt_render_guides_motion_device),
+// the history advances through hpt_history_advance_motion and hpt_scene_keep_previous follows (include/hpt.h, "motion").
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
+    std::function<void(int frame, void *triangles, int count)> triangles_at;      // empty: the geometry stays
     bool reproject = false;
     int guide_spp = 4;
     bool guided = false;

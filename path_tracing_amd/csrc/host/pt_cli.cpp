@@ -17,6 +17,8 @@
 //   --orbit DEG       with --frames: frame f renders from the scene's eye rotated by f * DEG degrees about the look-at point
 //                     around the up vector (rotation in double, rounded to float, then the usual camera).  By itself it does
 //                     what the reference's GUI does when the camera moves: the accumulation restarts on every moved frame.
+//   --spin DEG        with --frames and --obj: frame f turns the OBJ's triangles by f * DEG degrees about the vertical axis
+//                     through their centroid and updates the live scene; --reproject follows them (the motion guide)
 //   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
 //                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
 //                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
@@ -59,7 +61,8 @@ int main(int argc, char **argv){
     int frames = 0, frame_spp = 0;
     double until_rms = -1.0;
     std::string rms_log;
-    double orbit_deg = 0.0;
+    double orbit_deg = 0.0, spin_deg = 0.0;
+    bool spin = false;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
@@ -89,6 +92,7 @@ int main(int argc, char **argv){
         else if(arg == "--until-rms" && i + 1 < argc) until_rms = std::stod(argv[++i]);
         else if(arg == "--rms-log" && i + 1 < argc) rms_log = argv[++i];
         else if(arg == "--orbit" && i + 1 < argc){ orbit_deg = std::stod(argv[++i]); orbit = true; }
+        else if(arg == "--spin" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
         else if(arg == "--temporal-variance") temporal_variance = true;
@@ -119,6 +123,9 @@ int main(int argc, char **argv){
                       << "  --rms-log <file>  one line \"<frame> <rms>\" per frame\n"
                       << "  --orbit <deg>     with --frames: frame f renders from the eye rotated by f * deg degrees about the look-at point\n"
                       << "                    around the up vector; the accumulation restarts on every moved frame\n"
+                      << "  --spin <deg>      with --frames and --obj: before frame f the OBJ's triangles are turned by f * deg degrees about the\n"
+                      << "                    vertical axis through their centroid (hpt_scene_update_triangles); with --reproject the history\n"
+                      << "                    follows them through the motion guide, without it the accumulation restarts after every update\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
                       << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
                       << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n"
@@ -141,6 +148,8 @@ int main(int argc, char **argv){
         std::cerr << "[Error] --temporal-variance needs --frames N (N >= 1), --reproject and --guided.\n"; return -1;
     }
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
+    if(spin && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --spin needs --frames and --obj.\n"; return -1; }
+    if(spin && !std::isfinite(spin_deg)){ std::cerr << "[Error] --spin needs a finite angle.\n"; return -1; }
     if(guided && frames < 1){ std::cerr << "[Error] --guided needs --frames N (N >= 1).\n"; return -1; }
     if(guided && guide_spp < 1){ std::cerr << "[Error] --frames --guided needs --guide-spp of at least 1.\n"; return -1; }
     if(orbit && !std::isfinite(orbit_deg)){ std::cerr << "[Error] --orbit needs a finite angle.\n"; return -1; }
@@ -157,6 +166,8 @@ int main(int argc, char **argv){
         std::cerr << "[Error] Cannot open input file: " << input_file << "\n";
         return -1;
     }
+    int first_obj_id = 0;                  // the OBJ's faces are numbered from here on
+    for(const hpt_host::SceneItem &it : scene.items) first_obj_id = std::max(first_obj_id, it.obj_id + 1);
     if(!obj_file.empty()){
         hpt_host::Material grey; grey.base_color = {0.7f, 0.7f, 0.7f}; grey.roughness = 1.0f;
         std::string err;
@@ -205,8 +216,27 @@ int main(int argc, char **argv){
             const CudaCamera cc = hpt_host::make_cuda_camera(moved, F, W, H);
             memcpy(camera84, &cc, sizeof cc);
         };
+        if(spin) motion.triangles_at = [&](int f, void *triangles, int count){
+            // frame f: the ORIGINAL vertices of the OBJ's triangles turned by f * deg about the y axis through their centroid,
+            // in double, so that rounding does not accumulate over the frames
+            CudaTriangle *tr = (CudaTriangle *) triangles;
+            double c[3] = { 0.0, 0.0, 0.0 }, n = 0.0;
+            for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                for(const float3 *v : { &tr[i].v0, &tr[i].v1, &tr[i].v2 }){ c[0] += v->x; c[1] += v->y; c[2] += v->z; n += 1.0; }
+            }
+            if(n == 0.0) return;
+            for(double &x : c) x /= n;
+            const double t = (double) f * spin_deg * 3.14159265358979323846 / 180.0, cs = std::cos(t), sn = std::sin(t);
+            for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                for(float3 *v : { &tr[i].v0, &tr[i].v1, &tr[i].v2 }){
+                    const double x = v->x - c[0], z = v->z - c[2];
+                    v->x = (float) (c[0] + x * cs + z * sn);
+                    v->z = (float) (c[2] - x * sn + z * cs);
+                }
+            }
+        };
         const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
-                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject || guided ? &motion : nullptr);
+                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject || guided || spin ? &motion : nullptr);
         if(n < 0) return -1;
         std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
     }

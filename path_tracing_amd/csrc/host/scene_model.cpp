@@ -500,6 +500,7 @@ bool hpt_host::moved_run(const std::string &mode, MovedRun &out){
     MovedScene &ms = mode == "bdpt" ? g_bdpt : mode == "ppm" ? g_ppm : g_pt;
     if(!ms.ready()) return false;
     out.scene = ms.device; out.light_sample = ms.light_sample; out.params = run_params();
+    out.triangles = ms.flat.triangles.data(); out.num_triangles = (int) ms.flat.triangles.size();
     return true;
 }
 

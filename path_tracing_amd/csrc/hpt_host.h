@@ -146,6 +146,7 @@ struct hpt_scene {
         hpt::DevBuf<uint32_t> cand, acc;
         hpt::DevBuf<hpt::PpmCounters> pc;
         hpt::DevBuf<float4> g_alb, g_nrm, g_pos;     // hpt_render_guides: per-pixel sums over the call's samples (GuideAccum)
+        hpt::DevBuf<float4> g_prev;                  // ... and of the previous positions, once a call asks for the motion guide
         std::vector<hipEvent_t> marks;               // TIME_KERNELS: five events per pass (eye, photon, grid, gather, end)
         hpt_ppm_stats stats{};
     } pm;
@@ -163,6 +164,13 @@ struct hpt_scene {
         std::vector<float> h_verts;
         hipEvent_t ev_a = nullptr, ev_b = nullptr;
         hpt_update_info info{};
+        // the previous geometry G' (include/hpt.h, "motion"), allocated by the first update from the records the scene
+        // keeps: the vertices as `verts` holds them (which from then on is the current geometry's) and centre | radius of
+        // every sphere.  Until then G' is G and nothing is held.
+        bool prev_ready = false;
+        bool motion = false;                         // an update succeeded since creation / the last hpt_scene_keep_previous
+        hpt::DevBuf<float> prev_verts;
+        hpt::DevBuf<float4> prev_rounds;
     } up;
 
     // timing and statistics of the last render

@@ -269,11 +269,11 @@ namespace {
 // un-tiled into whichever images the caller asks for -- host images (hpt_render_guides) or, with `device`, device
 // images (hpt_render_guides_device).  Blocking, one device.
 int render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
-                  float *albedo, float *normal, float *position, float *coverage, bool device){
+                  float *albedo, float *normal, float *position, float *coverage, float *prev_position, bool device){
     if(!s) return fail(HPT_ERR_INVALID, "null scene");
     if(!camera) return fail(HPT_ERR_INVALID, "null camera");
     if(spp < 1) return fail(HPT_ERR_INVALID, "spp must be >= 1");
-    if(!albedo && !normal && !position && !coverage) return fail(HPT_ERR_INVALID, "hpt_render_guides: every output is null");
+    if(!albedo && !normal && !position && !coverage && !prev_position) return fail(HPT_ERR_INVALID, "hpt_render_guides: every output is null");
     if(int rcd = on_scene_device(s)) return rcd;
     PpmRun r;
     hpt_params &P = r.P;
@@ -289,7 +289,15 @@ int render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const
     const size_t n_local = r.n_local;
     hipError_t e = reserve_all(n_local, s->pm.g_alb, s->pm.g_nrm, s->pm.g_pos);
     if(e != hipSuccess) return fail_hip("guide accumulators", e);
-    const GuideAccum ga{ s->pm.g_alb.get(), s->pm.g_nrm.get(), s->pm.g_pos.get() };
+    // the motion guide (include/hpt.h, "motion"): a fifth sum, filled only where the scene holds a previous geometry -- until
+    // the first update G' is G, every previous point is the point itself and the image is resolved from the positions
+    const bool motion = prev_position && s->up.prev_ready;
+    if(motion){
+        e = s->pm.g_prev.reserve(s->pm.g_alb.capacity());
+        if(e != hipSuccess) return fail_hip("guide accumulators", e);
+    }
+    const GuideAccum ga{ s->pm.g_alb.get(), s->pm.g_nrm.get(), s->pm.g_pos.get(), motion ? s->pm.g_prev.get() : s->pm.g_pos.get() };
+    const GuideMotion gm{ s->up.verts.get(), s->up.prev_verts.get(), s->up.prev_rounds.get() };
 
     const PpmStep step(s, r);
     hipStream_t st = step.st;
@@ -298,30 +306,32 @@ int render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const
     HIP_TRY(hipMemsetAsync(ga.alb_cnt, 0, n_local * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(ga.nrm, 0, n_local * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(ga.pos, 0, n_local * sizeof(float4), st));
+    if(motion) HIP_TRY(hipMemsetAsync(ga.prev, 0, n_local * sizeof(float4), st));
     HIP_TRY(hipEventRecord(s->tm.ev_start, st));
     for(int pass = 0; pass < spp; ++pass){
         HIP_TRY(hipMemsetAsync(step.w.counters.get(), 0, (size_t) r.n_counters * sizeof(uint32_t), st));
         ppm_mark(s, r, pass, 0);
         rc = ppm_eye_phase(s, r, step, (uint32_t) ((int64_t) P.sample_offset + pass));
         if(rc) return rc;
-        launch_guides_accumulate(st, s->geo.sd, s->pm.hb, r.hp_count(s), r.n_local, ga);
+        if(motion) launch_guides_accumulate_motion(st, s->geo.sd, s->pm.hb, step.w.pb.hit, r.hp_count(s), r.n_local, ga, gm);
+        else launch_guides_accumulate(st, s->geo.sd, s->pm.hb, r.hp_count(s), r.n_local, ga);
         for(int k = 1; k <= 4; ++k) ppm_mark(s, r, pass, k);                // the eye phase is the only one: ms_eye
     }
-    float *outs[4] = { albedo, normal, position, coverage };
+    float *outs[5] = { albedo, normal, position, coverage, prev_position };
     const size_t npx = (size_t) W * H;
     std::vector<float> tmp;
-    for(int which = 0; which < 4; ++which){
+    for(int which = 0; which < 5; ++which){
         if(!outs[which]) continue;
         launch_guides_resolve(st, r.n_local, ga, which, s->ws.local_own.get());
         if(device){      // the three-channel images straight into the caller's; coverage is the first channel of one
-            launch_untile(st, r.tl, s->ws.local_own.get(), which < 3 ? outs[which] : s->ws.image_own.get());
+            launch_untile(st, r.tl, s->ws.local_own.get(), which != 3 ? outs[which] : s->ws.image_own.get());
             if(which == 3) launch_take_first_channel(st, s->ws.image_own.get(), coverage, (uint32_t) npx);
             HIP_TRY(hipGetLastError());
             continue;
         }
         launch_untile(st, r.tl, s->ws.local_own.get(), s->ws.image_own.get());
         HIP_TRY(hipGetLastError());
-        if(which < 3){
+        if(which != 3){
             HIP_TRY(hipMemcpy(outs[which], s->ws.image_own.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
         } else {
             tmp.resize(npx * 3);
@@ -340,12 +350,23 @@ extern "C" {
 
 int hpt_render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
                       float *albedo, float *normal, float *position, float *coverage){
-    return render_guides(s, camera, W, H, spp, params, albedo, normal, position, coverage, false);
+    return render_guides(s, camera, W, H, spp, params, albedo, normal, position, coverage, nullptr, false);
 }
 
 int hpt_render_guides_device(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
                              void *d_albedo, void *d_normal, void *d_position, void *d_coverage){
-    return render_guides(s, camera, W, H, spp, params, (float *) d_albedo, (float *) d_normal, (float *) d_position, (float *) d_coverage, true);
+    return render_guides(s, camera, W, H, spp, params, (float *) d_albedo, (float *) d_normal, (float *) d_position, (float *) d_coverage, nullptr, true);
+}
+
+int hpt_render_guides_motion(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
+                             float *albedo, float *normal, float *position, float *coverage, float *prev_position){
+    return render_guides(s, camera, W, H, spp, params, albedo, normal, position, coverage, prev_position, false);
+}
+
+int hpt_render_guides_motion_device(hpt_scene *s, const void *camera, int W, int H, int spp, const hpt_params *params,
+                                    void *d_albedo, void *d_normal, void *d_position, void *d_coverage, void *d_prev_position){
+    return render_guides(s, camera, W, H, spp, params, (float *) d_albedo, (float *) d_normal, (float *) d_position, (float *) d_coverage,
+                         (float *) d_prev_position, true);
 }
 
 int hpt_ppm_get_stats(const hpt_scene *s, hpt_ppm_stats *out){

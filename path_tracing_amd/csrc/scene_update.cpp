@@ -45,9 +45,62 @@ int ensure_scratch(hpt_scene *s){
     return HPT_OK;
 }
 
+// centre | radius of every sphere record
+std::vector<float4> pack_spheres(const std::vector<unsigned char> &h_spheres, int ns){
+    std::vector<float4> r((size_t) ns);
+    for(size_t i = 0; i < (size_t) ns; ++i) memcpy(&r[i], h_spheres.data() + i * HPT_SPHERE_BYTES, 16);
+    return r;
+}
+
+// The previous geometry, before the first update changes the current one: G' = G from the records the scene keeps.  `verts`
+// is filled too, so that from here on it holds the current geometry whichever update comes first.
+int ensure_previous(hpt_scene *s){
+    hpt_scene::Update &u = s->up;
+    if(u.prev_ready) return HPT_OK;
+    const hpt_scene::Geometry &g = s->geo;
+    const size_t nt = (size_t) g.nt, ns = (size_t) g.ns;
+    std::vector<float> v(nt * 9);
+    for(size_t i = 0; i < nt; ++i) memcpy(v.data() + i * 9, g.h_tris.data() + i * HPT_TRIANGLE_BYTES, 36);
+    HIP_TRY(u.verts.reserve(std::max<size_t>(nt * 9, 1)));
+    HIP_TRY(u.prev_verts.reserve(std::max<size_t>(nt * 9, 1)));
+    HIP_TRY(u.prev_rounds.reserve(std::max<size_t>(ns, 1)));
+    if(nt){
+        HIP_TRY(hipMemcpy(u.verts.get(), v.data(), nt * 36, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(u.prev_verts.get(), v.data(), nt * 36, hipMemcpyHostToDevice));
+    }
+    if(ns){
+        const std::vector<float4> r = pack_spheres(g.h_spheres, g.ns);
+        HIP_TRY(hipMemcpy(u.prev_rounds.get(), r.data(), ns * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    u.prev_ready = true;
+    return HPT_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int hpt_scene_keep_previous(hpt_scene *s){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(int rc = on_scene_device(s)) return rc;
+    hpt_scene::Update &u = s->up;
+    if(u.prev_ready){         // a scene that was never updated holds no G': it is G
+        const size_t nt = (size_t) s->geo.nt, ns = (size_t) s->geo.ns;
+        if(nt) HIP_TRY(hipMemcpy(u.prev_verts.get(), u.verts.get(), nt * 36, hipMemcpyDeviceToDevice));
+        if(ns){
+            const std::vector<float4> r = pack_spheres(s->geo.h_spheres, s->geo.ns);
+            HIP_TRY(hipMemcpy(u.prev_rounds.get(), r.data(), ns * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    u.motion = false;
+    return HPT_OK;
+}
+
+int hpt_scene_has_motion(const hpt_scene *s){
+    if(!s){ fail(HPT_ERR_INVALID, "null scene"); return -1; }
+    return s->up.motion ? 1 : 0;
+}
 
 int hpt_scene_update_check(const hpt_scene *s, const void *tris, int nt){ return check_triangles(s, tris, nt); }
 
@@ -55,6 +108,7 @@ int hpt_scene_update_triangles(hpt_scene *s, const void *tris, int nt){
     if(int rc = check_triangles(s, tris, nt)) return rc;
     hpt_scene::Update &u = s->up;
     hpt_scene::Geometry &g = s->geo;
+    if(int rc = ensure_previous(s)) return rc;
 
     // the nine floats of every triangle, input order
     auto t0 = std::chrono::steady_clock::now();
@@ -117,6 +171,7 @@ int hpt_scene_update_triangles(hpt_scene *s, const void *tris, int nt){
     s->bd.ready = false; s->pm.bounds_ready = false;
     u.info.updates += 1; u.info.dead_tris = ndead; u.info.live_tris = (uint64_t) nt - ndead;
     u.info.ms_pack = ms_pack; u.info.ms_upload = ms_upload; u.info.ms_refit = ms_refit;
+    u.motion = true;
     return HPT_OK;
 }
 
@@ -130,12 +185,14 @@ int hpt_scene_update_rounds(hpt_scene *s, const void *lights, int nl, const void
     std::vector<DevRound> rounds; std::vector<DevLight> dl;
     err = flatten_rounds_host(lights, nl, spheres, ns, s->up.sphere_material.data(), rounds, dl);
     if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(int rc = ensure_previous(s)) return rc;
     if(!rounds.empty()) HIP_TRY(hipMemcpy(g.rounds.get(), rounds.data(), rounds.size() * sizeof(DevRound), hipMemcpyHostToDevice));
     if(!dl.empty()) HIP_TRY(hipMemcpy(g.lights.get(), dl.data(), dl.size() * sizeof(DevLight), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
     if(nl) g.h_lights.assign((const unsigned char *) lights, (const unsigned char *) lights + (size_t) nl * HPT_LIGHT_BYTES);
     if(ns) g.h_spheres.assign((const unsigned char *) spheres, (const unsigned char *) spheres + (size_t) ns * HPT_SPHERE_BYTES);
     s->bd.ready = false; s->pm.bounds_ready = false;
+    s->up.motion = true;
     return HPT_OK;
 }
 
