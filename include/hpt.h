@@ -781,17 +781,19 @@ int hpt_trace_visibility(hpt_scene *scene, const float *p1, const float *p2, int
  * still camera it would average two scenes, so reset it after an update.  hpt_history follows the geometry when it is
  * given the motion guide, in the per-frame call order of "motion" below; without that guide it is reset like hpt_accum.
  *
- * hpt_scene_get_update_info describes the last hpt_scene_update_triangles (zeros before the first): how many have been
- * made, how many triangles were live and dead, and the milliseconds of packing the vertices (36 bytes per triangle),
- * of uploading them (the first update also allocates the scratch) and of the device part (HIP events around it).
+ * hpt_scene_get_update_info describes the last triangle update of any kind -- hpt_scene_update_triangles or one of the
+ * two of "poses" below -- (zeros before the first): how many have been made, how many triangles were live and dead, and
+ * the milliseconds of packing the vertices (36 bytes per triangle), of uploading them (the first update also allocates
+ * the scratch) and of the device part (HIP events around it).
  *
  * hpt_bvh_refit_host is the definition, on the host alone (no device): it builds from `triangles`, refits to
  * `new_triangles` (same count, same non-vertex bytes) and exports as hpt_bvh_export_host does.  Refitting a tree to the
  * vertices it was built from reproduces the builder's bytes.
  *
- * Out of scope: vertices handed over as a device pointer; topology changes and automatic rebuilds (a caller whose
- * geometry has moved far destroys and creates); hpt_multi_* and the scene the one-shot wrappers keep, which compare
- * bytes and rebuild as before.  (pt_cli turns an OBJ's triangles between frames with --spin, "motion" below.) */
+ * Out of scope: topology changes and automatic rebuilds (a caller whose geometry has moved far destroys and creates);
+ * hpt_multi_* and the scene the one-shot wrappers keep, which compare bytes and rebuild as before.  Vertices handed over
+ * as a device pointer and per-part transforms are "poses" below.  (pt_cli turns an OBJ's triangles between frames with
+ * --spin, "motion" below, and with --spin-device, "poses".) */
 typedef struct hpt_update_info {
     uint64_t updates, live_tris, dead_tris;
     double ms_pack, ms_upload, ms_refit;
@@ -803,6 +805,76 @@ int hpt_scene_get_update_info(const hpt_scene *scene, hpt_update_info *out);
 int hpt_bvh_refit_host(const void *lights, int num_lights, const void *spheres, int num_spheres, const void *triangles,
                        const void *new_triangles, int num_triangles, hpt_bvh_info *info,
                        void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);
+
+/* ---- poses ----------------------------------------------------------------------------------------------------
+ * Two more ways for new vertex positions to reach the refit of "scene updates", neither of which has the host touch a
+ * triangle: nine floats per triangle that are already on the device, and one 3 x 4 transform per rigid part, applied on
+ * the device to a rest pose the scene keeps.  Both end in the same refit and leave the handle as
+ * hpt_scene_update_triangles would with records carrying those vertices and the scene's own 84 other bytes: the exported
+ * tree equals hpt_bvh_refit_host of those records, every integrator renders them, the previous geometry and the motion
+ * guide ("motion") follow them -- they read the device's vertices, whichever call wrote them.  All five calls are blocking
+ * and run on the null stream, like every update: the caller has waited for whatever produced d_verts.
+ *
+ * hpt_scene_update_vertices_device takes num_triangles * 9 floats on the scene's device, in input order v0, v1, v2 per
+ * triangle, copies them device to device and refits.  No record is checked, because no non-vertex byte arrives.
+ *
+ * hpt_scene_set_parts gives every triangle a part: tri_part[i] in [0, num_parts), or tri_part NULL with num_parts == 1
+ * for one part that holds every triangle; num_parts lies in [1, 1 << 20] and a part may own no triangle.  The call
+ * captures the REST POSE: the nine vertex floats of every triangle as the scene holds them now.  It may be called again,
+ * which gives a new map and a new rest pose.  It costs 40 bytes of device memory per triangle, allocated here: a scene
+ * that never calls it pays nothing.  The geometry does not change (hpt_scene_has_motion is not set).
+ *
+ * hpt_scene_pose takes num_parts records of 12 floats, three rows (a, b, c, t) each; num_parts must be the value given to
+ * hpt_scene_set_parts.  Poses are absolute: every call is applied to the rest pose, never to the pose before, so rounding
+ * does not accumulate.  IEEE float, evaluated as written, left to right, no contraction: a vertex (x, y, z) of a triangle in
+ * part k with rows r0, r1, r2 becomes
+ *     X = ((r0.a * x + r0.b * y) + r0.c * z) + r0.t     and Y, Z likewise from r1, r2, with two exceptions made on bits:
+ *   identity    if the 48 bytes of part k's record are those of (1,0,0,0, 0,1,0,0, 0,0,1,0) with +0 throughout, the vertex
+ *               keeps its bits -- a -0 stays -0 (the arithmetic would give +0) and a NaN keeps its payload.  The motion
+ *               guide's Y = X rule and step 3' of the history advance compare bytes, so the pixels of a part left at
+ *               identity stay exact running means.
+ *   non-finite  if X, Y or Z is not finite (exponent bits all ones), all three become 0x7FC00000: processors propagate NaN
+ *               signs and payloads differently, and this makes the bytes a function of the inputs alone.  Such a triangle
+ *               is dead, as at creation, and a later pose revives it.
+ * A non-finite entry of xforms is not refused: it kills the part by the rule above.  After the pose kernel has written
+ * the vertices, the refit runs.
+ *
+ * The rest-pose rule.  Every triangle update that is not a pose -- hpt_scene_update_triangles and
+ * hpt_scene_update_vertices_device -- sets the rest pose to the geometry it leaves, which returns every part to identity;
+ * the part map is kept.
+ *
+ * hpt_scene_get_update_info describes these two updates as well: ms_pack is 0, ms_upload is the time of the table's
+ * upload or of the device-to-device copy, ms_refit the device part, the pose kernel included.
+ *
+ * hpt_scene_read_triangles returns the records the handle holds now, num_triangles * HPT_TRIANGLE_BYTES: the scene's 84
+ * non-vertex bytes with the current vertices.  After one of the two updates above the handle's host records are behind
+ * the device's vertices; they are brought up to date (a download of 36 bytes per triangle) by the first call that reads
+ * them -- this one, the bidirectional scene's build, photon mapping's own bounds -- and by nothing else: path tracing,
+ * the guides, the probes and further updates never pay for it.
+ *
+ * hpt_pose_host is the definition, on the host alone (no device): triangles_out gets the records of `triangles` with
+ * every vertex posed as above; it may be `triangles` itself.  tri_part NULL with num_parts == 1 as above.
+ *
+ * Refusals, HPT_ERR_INVALID with a message before anything touches the device: a null scene, or a null array with a
+ * non-zero count; a count that is not the scene's; num_parts out of range, or not the value given to
+ * hpt_scene_set_parts; a part index out of range (the message names the first triangle); hpt_scene_pose before
+ * hpt_scene_set_parts; a current device other than the scene's; tri_part NULL with num_parts != 1.  hpt_pose_host makes
+ * those that need no scene.  A scene of zero triangles accepts all of these calls with zero counts.  A refused call leaves
+ * the handle as it was.
+ *
+ * Out of scope: blend-weight skinning; poses for spheres and lights (hpt_scene_update_rounds is a small upload already);
+ * a non-blocking or caller-stream variant; hpt_multi_*.
+ *
+ * pt_cli --frames N --obj mesh.obj --spin-device DEG is --spin through these calls: hpt_scene_set_parts once (part 0:
+ * everything that is not the OBJ, left at identity; part 1: the OBJ) and hpt_scene_pose per frame, with the 3 x 4 of
+ * --spin's own double-precision rotation about the centroid rounded to float.  No record is copied per frame.  The pose
+ * multiplies in float where --spin turns in double and rounds once, so the two images differ in the last bits. */
+int hpt_scene_update_vertices_device(hpt_scene *scene, const void *d_verts, int num_triangles);
+int hpt_scene_set_parts(hpt_scene *scene, const int32_t *tri_part, int num_triangles, int num_parts);
+int hpt_scene_pose(hpt_scene *scene, const float *xforms, int num_parts);
+int hpt_scene_read_triangles(hpt_scene *scene, void *triangles_out, int num_triangles);
+int hpt_pose_host(const void *triangles, int num_triangles, const int32_t *tri_part,
+                  const float *xforms, int num_parts, void *triangles_out);
 
 /* ---- motion ---------------------------------------------------------------------------------------------
  * hpt_history keeps a viewer's accumulation when the camera moves, and the scene updates move the geometry in place; this

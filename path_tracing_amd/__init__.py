@@ -181,7 +181,9 @@ def load_library() -> C.CDLL:
                      "hpt_history_create_flags", "hpt_history_variance", "hpt_history_read_moments", "hpt_history_variance_check",
                      "hpt_scene_update_triangles", "hpt_scene_update_rounds", "hpt_scene_update_check", "hpt_scene_get_update_info",
                      "hpt_bvh_refit_host", "hpt_scene_keep_previous", "hpt_scene_has_motion", "hpt_render_guides_motion",
-                     "hpt_render_guides_motion_device", "hpt_history_advance_motion", "hpt_history_motion_check"):
+                     "hpt_render_guides_motion_device", "hpt_history_advance_motion", "hpt_history_motion_check",
+                     "hpt_scene_update_vertices_device", "hpt_scene_set_parts", "hpt_scene_pose", "hpt_scene_read_triangles",
+                     "hpt_pose_host"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -386,6 +388,49 @@ class Scene:
         """Raises HptError where update_triangles would refuse these records; no device work."""
         update_check(self, triangles)
 
+    # -- poses (include/hpt.h) ---------------------------------------------------------------
+    def update_vertices_device(self, v, num_triangles=None):
+        """update_triangles from vertices that are on the device already: a contiguous float32 CUDA torch.Tensor of shape
+        [nt, 3, 3] or [nt * 9] on the scene's device (a tensor does not say which stream produced it: the device is
+        waited for here), or an integer device pointer with num_triangles given (the caller has waited).  Blocking."""
+        if isinstance(v, int):
+            if num_triangles is None:
+                raise HptError("hpt error 1: update_vertices_device: a device pointer needs num_triangles")
+            ptr, nt = v, int(num_triangles)
+        else:
+            import torch
+            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or not v.is_contiguous():
+                raise HptError("hpt error 1: update_vertices_device takes a contiguous float32 CUDA tensor or a device pointer")
+            if not ((v.dim() == 3 and tuple(v.shape[1:]) == (3, 3)) or (v.dim() == 1 and v.numel() % 9 == 0)):
+                raise HptError("hpt error 1: update_vertices_device: the tensor's shape must be [nt, 3, 3] or [nt * 9], not %s" % (tuple(v.shape),))
+            nt = v.numel() // 9
+            if num_triangles is not None and int(num_triangles) != nt:
+                raise HptError("hpt error 1: update_vertices_device: the tensor holds %d triangles, num_triangles says %d" % (nt, int(num_triangles)))
+            torch.cuda.synchronize(v.device)
+            ptr = v.data_ptr() if nt else 0
+        _check(self._lib.hpt_scene_update_vertices_device(self._h, C.c_void_p(ptr) if ptr else None, nt))
+
+    def set_parts(self, tri_part, num_parts):
+        """Gives every triangle a part (int32 per triangle, or None with num_parts == 1) and captures the rest pose: the
+        vertices as the scene holds them now."""
+        tp = np.ascontiguousarray(tri_part, np.int32) if tri_part is not None else None
+        n = len(tp) if tp is not None else self.num_triangles
+        _check(self._lib.hpt_scene_set_parts(self._h, _vp(tp) if tp is not None else None, n, int(num_parts)))
+
+    def pose(self, xforms):
+        """One absolute pose: [num_parts, 3, 4] (or [num_parts, 12]) float32, rows (a, b, c, t), applied to the rest pose on
+        the device; the tree is refitted.  Blocking."""
+        x = np.ascontiguousarray(xforms, np.float32)
+        if x.size % 12:
+            raise HptError("hpt error 1: pose: twelve floats per part")
+        _check(self._lib.hpt_scene_pose(self._h, _vp(x), x.size // 12))
+
+    def read_triangles(self) -> np.ndarray:
+        """The records the handle holds now (layouts.TRIANGLE): the scene's non-vertex bytes with the current vertices."""
+        out = np.zeros(self.num_triangles, TRIANGLE)
+        _check(self._lib.hpt_scene_read_triangles(self._h, _vp(out), len(out)))
+        return out
+
     def keep_previous(self):
         """The current geometry becomes the previous one (include/hpt.h, "motion"): once per frame, after the frame's
         guides and before the next frame's updates.  Blocking."""
@@ -399,7 +444,7 @@ class Scene:
         return rc == 1
 
     def update_info(self) -> dict:
-        """The last update_triangles: dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
+        """The last triangle update of any kind (update_triangles, update_vertices_device, pose): dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
         info = UpdateInfo()
         _check(self._lib.hpt_scene_get_update_info(self._h, C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_}
@@ -858,6 +903,21 @@ def refit_bvh_host(lights, spheres, triangles, new_triangles) -> dict:
         raise HptError("hpt error 1: an update keeps the triangle count: %d triangles, %d were handed over" % (len(triangles), len(new_triangles)))
     return _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_refit_host(
         _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), _vp(new_triangles), len(triangles), info, qn, qcap, tr, tcap))
+
+
+def pose_host(triangles, tri_part, xforms) -> np.ndarray:
+    """hpt_pose_host, the definition of Scene.pose on the host (no device needed): the records with every vertex posed by
+    its part's record of xforms ([num_parts, 3, 4] float32).  tri_part None: one part."""
+    tr = np.ascontiguousarray(triangles, TRIANGLE)
+    tp = np.ascontiguousarray(tri_part, np.int32) if tri_part is not None else None
+    x = np.ascontiguousarray(xforms, np.float32)
+    if x.size % 12:
+        raise HptError("hpt error 1: pose_host: twelve floats per part")
+    if tp is not None and len(tp) != len(tr):
+        raise HptError("hpt error 1: pose_host: one part index per triangle (%d triangles, %d indices)" % (len(tr), len(tp)))
+    out = np.zeros(len(tr), TRIANGLE)
+    _check(load_library().hpt_pose_host(_vp(tr), len(tr), _vp(tp) if tp is not None else None, _vp(x), x.size // 12, _vp(out)))
+    return out
 
 
 def update_check(scene, triangles, num_triangles=None) -> None:

@@ -61,9 +61,19 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     DeviceMem d_local, d_frame, d_mean, d_rgb8, d_normal, d_position, d_coverage;      // released after L has waited for its stream
     DeviceMem d_albedo, d_variance, d_length, d_filtered;                              // --guided
     DeviceMem d_prev_position;                                                         // --spin --reproject
-    const bool spin = motion && motion->triangles_at;
+    const bool posed = motion && motion->pose_at;                                      // --spin-device
+    if(posed && (motion->triangles_at || !motion->parts_of)){ std::cerr << "[Error] a pose needs a part map, and excludes edited records" << std::endl; return -1; }
+    const bool spin = motion && (motion->triangles_at || posed);
     if(spin && (!run.triangles || run.num_triangles < 1)){ std::cerr << "[Error] --spin: the scene has no triangles" << std::endl; return -1; }
     std::vector<unsigned char> spun;                                                   // this frame's triangle records
+    std::vector<float> xforms;                                                         // this frame's pose, 12 floats per part
+    if(posed){       // once: the part map, and the rest pose the scene captures with it
+        std::vector<int32_t> tri_part;
+        const int num_parts = motion->parts_of(run.triangles, run.num_triangles, tri_part);
+        if((int) tri_part.size() != run.num_triangles){ std::cerr << "[Error] --spin-device: one part per triangle" << std::endl; return -1; }
+        if(hpt_scene_set_parts(run.scene, tri_part.data(), run.num_triangles, num_parts) != HPT_OK) return hpt_failed("hpt_scene_set_parts");
+        xforms.resize((size_t) num_parts * 12);
+    }
     Loop L;
     if(!d_frame.alloc(values * sizeof(float)) || !d_mean.alloc(values * sizeof(float)) || !d_rgb8.alloc(values) ||
        (!ppm && !d_local.alloc((size_t) n_local * 3 * sizeof(float)))){
@@ -111,9 +121,14 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         const bool updated = spin && f > 0;
         if(updated){     // blocking, on the null stream: the last frame's work on the loop's stream has ended with its metrics
             if(hipError_t e = hipStreamSynchronize(L.stream)) return hip_failed("stream", e);
-            spun.assign((const unsigned char *) run.triangles, (const unsigned char *) run.triangles + (size_t) run.num_triangles * HPT_TRIANGLE_BYTES);
-            motion->triangles_at(f, spun.data(), run.num_triangles);
-            if(hpt_scene_update_triangles(run.scene, spun.data(), run.num_triangles) != HPT_OK) return hpt_failed("hpt_scene_update_triangles");
+            if(posed){       // twelve floats per part: no record is copied, no vertex is touched on the host
+                motion->pose_at(f, xforms.data(), (int) (xforms.size() / 12));
+                if(hpt_scene_pose(run.scene, xforms.data(), (int) (xforms.size() / 12)) != HPT_OK) return hpt_failed("hpt_scene_pose");
+            } else {
+                spun.assign((const unsigned char *) run.triangles, (const unsigned char *) run.triangles + (size_t) run.num_triangles * HPT_TRIANGLE_BYTES);
+                motion->triangles_at(f, spun.data(), run.num_triangles);
+                if(hpt_scene_update_triangles(run.scene, spun.data(), run.num_triangles) != HPT_OK) return hpt_failed("hpt_scene_update_triangles");
+            }
         }
         const bool follow = spin && reproject;          // the motion guide every frame
         const bool guides = (reproject || guided) && (f == 0 || moved || spin);

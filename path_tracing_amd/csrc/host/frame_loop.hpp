@@ -52,9 +52,16 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // reproject the accumulator is reset after every update, which is the advice for a history that is not given the motion
 // guide.  With reproject the guides are rendered on every frame with the motion guide (hpt_render_guides_motion_device),
 // the history advances through hpt_history_advance_motion and hpt_scene_keep_previous follows (include/hpt.h, "motion").
+//
+// With `pose_at` (--spin-device; needs `parts_of`, excludes `triangles_at`) the geometry moves the same way without the loop
+// copying a record: before frame 0 parts_of fills one part index per triangle from the moved scene's records and returns
+// the number of parts, which goes to hpt_scene_set_parts once; before frame f > 0 pose_at fills 12 floats per part and the
+// loop calls hpt_scene_pose (include/hpt.h, "poses").  Everything else is as with `triangles_at`.
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
     std::function<void(int frame, void *triangles, int count)> triangles_at;      // empty: the geometry stays
+    std::function<int(const void *triangles, int count, std::vector<int32_t> &tri_part)> parts_of;
+    std::function<void(int frame, float *xforms, int num_parts)> pose_at;         // empty: no poses
     bool reproject = false;
     int guide_spp = 4;
     bool guided = false;

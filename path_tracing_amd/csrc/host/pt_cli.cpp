@@ -19,6 +19,8 @@
 //                     what the reference's GUI does when the camera moves: the accumulation restarts on every moved frame.
 //   --spin DEG        with --frames and --obj: frame f turns the OBJ's triangles by f * DEG degrees about the vertical axis
 //                     through their centroid and updates the live scene; --reproject follows them (the motion guide)
+//   --spin-device DEG --spin through hpt_scene_set_parts once and hpt_scene_pose per frame: the OBJ is one rigid part, the host
+//                     hands over twelve floats per frame and copies no record; not together with --spin
 //   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
 //                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
 //                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
@@ -62,7 +64,7 @@ int main(int argc, char **argv){
     double until_rms = -1.0;
     std::string rms_log;
     double orbit_deg = 0.0, spin_deg = 0.0;
-    bool spin = false;
+    bool spin = false, spin_device = false;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
@@ -93,6 +95,7 @@ int main(int argc, char **argv){
         else if(arg == "--rms-log" && i + 1 < argc) rms_log = argv[++i];
         else if(arg == "--orbit" && i + 1 < argc){ orbit_deg = std::stod(argv[++i]); orbit = true; }
         else if(arg == "--spin" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin = true; }
+        else if(arg == "--spin-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin_device = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
         else if(arg == "--temporal-variance") temporal_variance = true;
@@ -126,6 +129,10 @@ int main(int argc, char **argv){
                       << "  --spin <deg>      with --frames and --obj: before frame f the OBJ's triangles are turned by f * deg degrees about the\n"
                       << "                    vertical axis through their centroid (hpt_scene_update_triangles); with --reproject the history\n"
                       << "                    follows them through the motion guide, without it the accumulation restarts after every update\n"
+                      << "  --spin-device <deg>  --spin with the OBJ as one rigid part posed on the device (hpt_scene_set_parts once,\n"
+                      << "                    hpt_scene_pose per frame): the same turn as a 3 x 4 matrix rounded to float, twelve floats per\n"
+                      << "                    frame and no record copied.  The pose multiplies in float where --spin turns in double and\n"
+                      << "                    rounds once, so the images differ from --spin's in the last bits.  Not together with --spin\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
                       << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
                       << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n"
@@ -148,6 +155,9 @@ int main(int argc, char **argv){
         std::cerr << "[Error] --temporal-variance needs --frames N (N >= 1), --reproject and --guided.\n"; return -1;
     }
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
+    if(spin && spin_device){ std::cerr << "[Error] --spin and --spin-device exclude each other.\n"; return -1; }
+    if(spin_device && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --spin-device needs --frames and --obj.\n"; return -1; }
+    if(spin_device && !std::isfinite(spin_deg)){ std::cerr << "[Error] --spin-device needs a finite angle.\n"; return -1; }
     if(spin && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --spin needs --frames and --obj.\n"; return -1; }
     if(spin && !std::isfinite(spin_deg)){ std::cerr << "[Error] --spin needs a finite angle.\n"; return -1; }
     if(guided && frames < 1){ std::cerr << "[Error] --guided needs --frames N (N >= 1).\n"; return -1; }
@@ -235,8 +245,34 @@ int main(int argc, char **argv){
                 }
             }
         };
+        double spin_centre[3] = { 0.0, 0.0, 0.0 };
+        if(spin_device){
+            // part 0: everything that is not the OBJ, left at identity; part 1: the OBJ.  The centroid is --spin's, in double
+            motion.parts_of = [&](const void *triangles, int count, std::vector<int32_t> &tri_part){
+                const CudaTriangle *tr = (const CudaTriangle *) triangles;
+                tri_part.assign((size_t) count, 0);
+                double c[3] = { 0.0, 0.0, 0.0 }, n = 0.0;
+                for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                    tri_part[(size_t) i] = 1;
+                    for(const float3 *v : { &tr[i].v0, &tr[i].v1, &tr[i].v2 }){ c[0] += v->x; c[1] += v->y; c[2] += v->z; n += 1.0; }
+                }
+                if(n != 0.0) for(int a = 0; a < 3; ++a) spin_centre[a] = c[a] / n;
+                return 2;
+            };
+            // frame f: --spin's turn, x' = c + R (x - c) = R x + (c - R c), as three rows (a, b, c, t) rounded to float
+            motion.pose_at = [&](int f, float *xforms, int num_parts){
+                static const float identity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+                for(int k = 0; k < num_parts; ++k) memcpy(xforms + 12 * k, identity, sizeof identity);
+                if(num_parts < 2) return;
+                const double *c = spin_centre;
+                const double t = (double) f * spin_deg * 3.14159265358979323846 / 180.0, cs = std::cos(t), sn = std::sin(t);
+                float *r = xforms + 12;
+                r[0] = (float) cs; r[2] = (float) sn; r[3] = (float) (c[0] - (c[0] * cs + c[2] * sn));
+                r[8] = (float) -sn; r[10] = (float) cs; r[11] = (float) (c[2] - (-c[0] * sn + c[2] * cs));
+            };
+        }
         const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
-                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject || guided || spin ? &motion : nullptr);
+                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject || guided || spin || spin_device ? &motion : nullptr);
         if(n < 0) return -1;
         std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
     }

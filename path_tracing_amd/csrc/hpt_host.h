@@ -171,6 +171,14 @@ struct hpt_scene {
         bool motion = false;                         // an update succeeded since creation / the last hpt_scene_keep_previous
         hpt::DevBuf<float> prev_verts;
         hpt::DevBuf<float4> prev_rounds;
+        // poses (include/hpt.h, "poses"), allocated by hpt_scene_set_parts: the rest pose as `verts` held it then (and as every
+        // later update that is not a pose leaves it), each triangle's part, and the table of the last pose
+        int num_parts = 0;                           // 0: no parts
+        hpt::DevBuf<float> rest_verts, xforms;       // 9 floats per triangle; 12 per part
+        hpt::DevBuf<int32_t> tri_part;
+        // an update that brought no records (device vertices, a pose) leaves the vertex bytes of geo.h_tris behind `verts`:
+        // host_triangles() brings them up to date for the few readers there are
+        bool h_tris_stale = false;
     } up;
 
     // timing and statistics of the last render
@@ -250,6 +258,11 @@ struct LaunchTimer {        // brackets one launch with events when TIME_KERNELS
 inline bool same_bytes(const std::vector<unsigned char> &kept, const void *given, size_t bytes){
     return kept.size() == bytes && (bytes == 0 || memcmp(kept.data(), given, bytes) == 0);
 }
+
+// The records the handle holds now, geo.h_tris: the scene's 84 non-vertex bytes with the current vertices.  After an update
+// that brought vertices on the device only (scene_update.cpp) this downloads `verts` and splices the 36 bytes per record --
+// once, and only here, so a handle whose records nobody reads never pays for it.  Readers of the vertex bytes go through it.
+int host_triangles(hpt_scene *s, const unsigned char **tris);
 
 // the arrays and the description hpt_bvh_export_host hands out, of a scene built (or refitted) on the host (hpt_api.cpp)
 int export_host_tree(const HostScene &hs, hpt_bvh_info *info, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);

@@ -168,6 +168,20 @@ const char *check_rounds_update(const void *kept_spheres, int kept_ns, int kept_
 // device's refit (refit_kernels.hip) is held to these bytes.  dead_out: the number of triangles no ray can hit.
 const char *refit_host_scene(HostScene &hs, const void *tris, int nt, uint64_t *dead_out = nullptr);
 
+// ---- poses (include/hpt.h, "poses"): per-part 3 x 4 transforms applied to a rest pose ----
+
+constexpr int kMaxParts = 1 << 20;
+// The refusals the pose calls share: "" when tri_part (nt entries, or null with num_parts == 1) names parts of [0, num_parts)
+// and num_parts lies in [1, kMaxParts], else the message (a literal or `msg`, which names the first triangle out of range).
+const char *check_parts(const int32_t *tri_part, int nt, int num_parts, char *msg, size_t msg_cap);
+// The definition of a pose: one vertex (x, y, z) under the record r (three rows a, b, c, t), one float operation at a time,
+// left to right; a record whose 48 bytes are the identity's keeps the vertex's bits, a result that is not finite makes all
+// three words 0x7FC00000.  k_pose_verts (refit_kernels.hip) is held to these bytes.
+void pose_vertex_host(const float r[12], const float in[3], float out[3]);
+// records out[i] = tris[i] with its three vertices posed by xforms[tri_part[i]]; out may be tris itself
+const char *pose_host_records(const void *tris, int nt, const int32_t *tri_part, const float *xforms, int num_parts, void *out,
+                              char *msg, size_t msg_cap);
+
 // the builder's lines the device's refit needs on the host between its launches
 float box_padding_of(const float scene_min[3], const float scene_max[3], int nt);                      // pad_abs of a scene box
 void grid_of_box(const float lo[3], const float hi[3], float qorigin[3], float qscale[3]);         // the 16-bit grid over a box

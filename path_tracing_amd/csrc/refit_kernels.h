@@ -36,4 +36,13 @@ void launch_refit_quantise(hipStream_t s, const float4 *nodes, uint4 *qnodes, ui
 void launch_refit_wide(hipStream_t s, const float4 *nodes, uint32_t num_nodes, uint4 *wnodes, const uint4 *wide_src, uint32_t num_wide,
                        RefitGrid grid);
 
+// ---- poses (include/hpt.h, "poses") ----
+constexpr int kPoseLdsParts = 256;        // tables of up to this many parts (12 KB) are staged in LDS
+constexpr int kPoseMaxBlocks = 2048;      // the grid's cap; a grid-stride loop covers the rest
+// One lane per vertex: verts[v] = the record xforms[tri_part[v / 3]] (three rows a, b, c, t) applied to rest[v], to the bytes
+// of pose_vertex_host (scene_build.cpp), which is the definition: an identity record keeps the vertex's bits, a result that
+// is not finite becomes three canonical NaNs.  rest and verts hold nine floats per triangle, input order.
+void launch_pose_verts(hipStream_t s, const float *rest, const int32_t *tri_part, const float *xforms, uint32_t num_parts, uint32_t num_tris,
+                       float *verts);
+
 } // namespace hpt

@@ -3,6 +3,7 @@
 // std::min / std::max, and the float neighbours are taken on the bit pattern, so nothing depends on a math library.
 #include "refit_kernels.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace hpt {
@@ -204,7 +205,65 @@ __global__ __launch_bounds__(kRefitBlock) void k_refit_wide(const float4 *__rest
         wnodes[(size_t) i * 4 + a] = make_uint4(lo[a][0] | (lo[a][1] << 16), lo[a][2] | (lo[a][3] << 16), hi[a][0] | (hi[a][1] << 16), hi[a][2] | (hi[a][3] << 16));
 }
 
+// ---- poses (include/hpt.h, "poses") ---------------------------------------------------------------------------------------
+
+// one row of a record applied to a vertex: one operation at a time, left to right
+__device__ __forceinline__ float pose_row(float a, float b, float c, float t, float x, float y, float z){
+    return ((a * x + b * y) + c * z) + t;
+}
+
+// the 48 bytes of the identity's record, +0 throughout
+__device__ __forceinline__ bool is_identity(const float4 &r0, const float4 &r1, const float4 &r2){
+    constexpr uint32_t one = 0x3F800000u;
+    const uint32_t ones = (__float_as_uint(r0.x) ^ one) | (__float_as_uint(r1.y) ^ one) | (__float_as_uint(r2.z) ^ one);
+    const uint32_t zeros = __float_as_uint(r0.y) | __float_as_uint(r0.z) | __float_as_uint(r0.w) | __float_as_uint(r1.x) | __float_as_uint(r1.z) |
+                           __float_as_uint(r1.w) | __float_as_uint(r2.x) | __float_as_uint(r2.y) | __float_as_uint(r2.w);
+    return (ones | zeros) == 0u;
+}
+
+// One lane per vertex, a grid-stride loop over the 3 * num_tris vertices: neighbouring lanes read and write neighbouring 12
+// bytes, so a wave's loads and stores each cover one contiguous run of 768 bytes.  76 bytes per triangle plus the table,
+// which kStaged copies into LDS once per workgroup (num_parts <= kPoseLdsParts) and otherwise reads through the cache.
+template <bool kStaged>
+__global__ __launch_bounds__(kRefitBlock) void k_pose_verts(const float *__restrict__ rest, const int32_t *__restrict__ tri_part,
+                                                             const float4 *__restrict__ xforms, uint32_t num_parts, uint64_t num_verts,
+                                                             float *__restrict__ verts){
+    __shared__ float4 table[kStaged ? kPoseLdsParts * 3 : 1];
+    if(kStaged){
+        for(uint32_t i = threadIdx.x; i < num_parts * 3u && i < (uint32_t) kPoseLdsParts * 3u; i += (uint32_t) kRefitBlock) table[i] = xforms[i];
+        __syncthreads();
+    }
+    const uint64_t stride = (uint64_t) gridDim.x * (uint64_t) kRefitBlock;
+    for(uint64_t v = (uint64_t) blockIdx.x * (uint64_t) kRefitBlock + threadIdx.x; v < num_verts; v += stride){
+        const uint32_t part = (uint32_t) tri_part[v / 3u];
+        if(part >= num_parts) continue;                     // (refused on the host: never out of the table)
+        const float4 *r = kStaged ? table + (size_t) part * 3 : xforms + (size_t) part * 3;
+        const float4 r0 = r[0], r1 = r[1], r2 = r[2];
+        const float x = rest[v * 3u], y = rest[v * 3u + 1u], z = rest[v * 3u + 2u];
+        float px = x, py = y, pz = z;
+        if(!is_identity(r0, r1, r2)){
+            px = pose_row(r0.x, r0.y, r0.z, r0.w, x, y, z);
+            py = pose_row(r1.x, r1.y, r1.z, r1.w, x, y, z);
+            pz = pose_row(r2.x, r2.y, r2.z, r2.w, x, y, z);
+            if(!(finite_f(px) && finite_f(py) && finite_f(pz))) px = py = pz = __uint_as_float(0x7FC00000u);
+        }
+        verts[v * 3u] = px; verts[v * 3u + 1u] = py; verts[v * 3u + 2u] = pz;
+    }
+}
+
 } // namespace
+
+void launch_pose_verts(hipStream_t s, const float *rest, const int32_t *tri_part, const float *xforms, uint32_t num_parts, uint32_t num_tris,
+                       float *verts){
+    if(num_tris == 0) return;
+    const uint64_t num_verts = (uint64_t) num_tris * 3u;
+    const uint64_t blocks = (num_verts + (uint64_t) kRefitBlock - 1u) / (uint64_t) kRefitBlock;
+    const dim3 grid((uint32_t) std::min<uint64_t>(blocks, (uint64_t) kPoseMaxBlocks));
+    if(num_parts <= (uint32_t) kPoseLdsParts)
+        hipLaunchKernelGGL(k_pose_verts<true>, grid, dim3(kRefitBlock), 0, s, rest, tri_part, (const float4 *) xforms, num_parts, num_verts, verts);
+    else
+        hipLaunchKernelGGL(k_pose_verts<false>, grid, dim3(kRefitBlock), 0, s, rest, tri_part, (const float4 *) xforms, num_parts, num_verts, verts);
+}
 
 void launch_refit_tris(hipStream_t s, const float *verts, float4 *tris, uint32_t num_tris, uint32_t num_rounds, float *slot_box,
                        float *partial, uint32_t *dead_count){

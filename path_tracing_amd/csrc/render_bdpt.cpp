@@ -11,7 +11,9 @@ int ensure_bdpt_scene(hpt_scene *s){
     HostBdptScene hb;
     const hpt_scene::Geometry &g = s->geo;
     bool grouped = !g.g_kind.empty();
-    const char *err = build_bdpt_host_scene(g.h_lights.data(), g.nl, g.h_spheres.data(), g.ns, g.h_tris.data(), g.nt,
+    const unsigned char *h_tris = nullptr;
+    if(int rc = host_triangles(s, &h_tris)) return rc;
+    const char *err = build_bdpt_host_scene(g.h_lights.data(), g.nl, g.h_spheres.data(), g.ns, h_tris, g.nt,
                                             grouped ? g.g_kind.data() : nullptr, grouped ? g.g_index.data() : nullptr,
                                             grouped ? g.g_group.data() : nullptr, (int) g.g_kind.size(), hb);
     if(err && *err) return fail(HPT_ERR_INVALID, err);

@@ -12,15 +12,17 @@ namespace {
 
 // the scene's bounds as the reference's helper computes them (src/ppm_cu_helper.cpp:21-52): spheres +- r and triangle
 // vertices, light balls left out, starting from +-1e9
-void ppm_scene_bounds(hpt_scene *s){
-    if(s->pm.bounds_ready) return;
+int ppm_scene_bounds(hpt_scene *s){
+    if(s->pm.bounds_ready) return HPT_OK;
+    const unsigned char *h_tris = nullptr;
+    if(int rc = host_triangles(s, &h_tris)) return rc;
     float mn[3] = { 1e9f, 1e9f, 1e9f }, mx[3] = { -1e9f, -1e9f, -1e9f };
     for(int i = 0; i < s->geo.ns; ++i){
         float c[4]; memcpy(c, s->geo.h_spheres.data() + (size_t) i * HPT_SPHERE_BYTES, 16);
         for(int a = 0; a < 3; ++a){ mx[a] = std::max(mx[a], c[a] + c[3]); mn[a] = std::min(mn[a], c[a] - c[3]); }
     }
     for(int i = 0; i < s->geo.nt; ++i){
-        float v[9]; memcpy(v, s->geo.h_tris.data() + (size_t) i * HPT_TRIANGLE_BYTES, 36);
+        float v[9]; memcpy(v, h_tris + (size_t) i * HPT_TRIANGLE_BYTES, 36);
         for(int a = 0; a < 3; ++a){
             mx[a] = std::max({ mx[a], v[a], v[3 + a], v[6 + a] });
             mn[a] = std::min({ mn[a], v[a], v[3 + a], v[6 + a] });
@@ -28,6 +30,7 @@ void ppm_scene_bounds(hpt_scene *s){
     }
     for(int a = 0; a < 3; ++a){ s->pm.min[a] = mn[a]; s->pm.max[a] = mx[a]; }
     s->pm.bounds_ready = true;
+    return HPT_OK;
 }
 
 constexpr ParamRules kPpmParams{ "hpt_render_ppm renders the whole image on one device: world must be 0 or 1",
@@ -232,7 +235,7 @@ int hpt_render_ppm(hpt_scene *s, const void *camera, int W, int H, int eye_depth
     if(rc) return rc;
     if(!(radius > 0.0f)) radius = 0.05f;                                    // PPM_RADIUS, include/ppm_cu.cuh:4
     PpmFrame &fr = r.fr;
-    ppm_scene_bounds(s);
+    if(int rcb = ppm_scene_bounds(s)) return rcb;
     for(int a = 0; a < 3; ++a){ fr.smin[a] = scene_min ? scene_min[a] : s->pm.min[a]; fr.smax[a] = scene_max ? scene_max[a] : s->pm.max[a]; }
     fr.cell = radius; fr.r2 = radius * radius;
     set_camera(r.cam, camera);
@@ -280,7 +283,9 @@ int render_guides(hpt_scene *s, const void *camera, int W, int H, int spp, const
     if(int rcp = take_params(params, kGuideParams, P)) return rcp;
     int rc = make_tiling(W, H, &P, r.tl);
     if(rc) return rc;
-    ppm_scene_bounds(s);
+    // the bounds place photons and grid cells, and a guide render has neither: a scene whose host records are behind its
+    // device vertices (a pose, device vertices) is not made to download them for a box no kernel here reads
+    if(!s->up.h_tris_stale) if(int rcb = ppm_scene_bounds(s)) return rcb;
     for(int a = 0; a < 3; ++a){ r.fr.smin[a] = s->pm.min[a]; r.fr.smax[a] = s->pm.max[a]; }
     r.fr.cell = 0.05f; r.fr.r2 = 0.05f * 0.05f;                             // no photons: the grid is not built
     set_camera(r.cam, camera);
@@ -401,7 +406,7 @@ int hpt_sppm_reset(hpt_sppm *z){
     if(int rcd = on_scene_device(z->scene)) return rcd;
     // bounds the caller left to the scene are the scene's of now: an update since the last reset has invalidated them
     if(z->scene_smin || z->scene_smax){
-        ppm_scene_bounds(z->scene);
+        if(int rcb = ppm_scene_bounds(z->scene)) return rcb;
         for(int a = 0; a < 3; ++a){
             if(z->scene_smin) z->smin[a] = z->scene->pm.min[a];
             if(z->scene_smax) z->smax[a] = z->scene->pm.max[a];

@@ -597,6 +597,57 @@ const char *check_triangle_update(const void *kept_v, int kept_nt, const void *t
     return "";
 }
 
+const char *check_parts(const int32_t *tri_part, int nt, int num_parts, char *msg, size_t msg_cap){
+    if(nt < 0) return "negative triangle count";
+    if(num_parts < 1 || num_parts > kMaxParts){ snprintf(msg, msg_cap, "the number of parts must lie in [1, %d]: %d was given", kMaxParts, num_parts); return msg; }
+    if(!tri_part){
+        if(num_parts != 1 && nt > 0) return "a null part map puts every triangle in part 0: the number of parts must be 1";
+        return "";
+    }
+    for(int i = 0; i < nt; ++i)
+        if(tri_part[i] < 0 || tri_part[i] >= num_parts){
+            snprintf(msg, msg_cap, "part %d of triangle %d is not one of the %d parts", tri_part[i], i, num_parts);
+            return msg;
+        }
+    return "";
+}
+
+void pose_vertex_host(const float r[12], const float in[3], float out[3]){
+    static const float kIdentity[12] = { 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f };
+    const float x = in[0], y = in[1], z = in[2];
+    if(memcmp(r, kIdentity, sizeof kIdentity) == 0){ out[0] = x; out[1] = y; out[2] = z; return; }
+    float p[3];
+    for(int a = 0; a < 3; ++a){
+        const float *row = r + 4 * a;
+        p[a] = ((row[0] * x + row[1] * y) + row[2] * z) + row[3];
+    }
+    uint32_t w[3]; memcpy(w, p, 12);
+    bool finite = true;
+    for(int a = 0; a < 3; ++a) finite = finite && (w[a] & 0x7F800000u) != 0x7F800000u;
+    if(!finite) w[0] = w[1] = w[2] = 0x7FC00000u;
+    memcpy(out, w, 12);
+}
+
+const char *pose_host_records(const void *tris_v, int nt, const int32_t *tri_part, const float *xforms, int num_parts, void *out_v,
+                              char *msg, size_t msg_cap){
+    const char *err = check_parts(tri_part, nt, num_parts, msg, msg_cap);
+    if(err && *err) return err;
+    if(!xforms) return "null transform array";
+    if(nt > 0 && (!tris_v || !out_v)) return "null triangle array";
+    const unsigned char *tris = (const unsigned char *) tris_v;
+    unsigned char *out = (unsigned char *) out_v;
+    parallel_chunks((size_t) nt, [&](int, size_t b0, size_t e0){
+        for(size_t i = b0; i < e0; ++i){
+            if(out != tris) memcpy(out + i * sizeof(RefTriangle), tris + i * sizeof(RefTriangle), sizeof(RefTriangle));
+            const float *r = xforms + (size_t) (tri_part ? tri_part[i] : 0) * 12;
+            float v[9]; memcpy(v, out + i * sizeof(RefTriangle), 36);
+            for(int k = 0; k < 3; ++k) pose_vertex_host(r, v + 3 * k, v + 3 * k);
+            memcpy(out + i * sizeof(RefTriangle), v, 36);
+        }
+    });
+    return "";
+}
+
 const char *check_rounds_update(const void *kept_spheres_v, int kept_ns, int kept_nl, const void *lights_v, int nl, const void *spheres_v, int ns,
                                 char *msg, size_t msg_cap){
     if(nl < 0 || ns < 0) return "negative primitive count";

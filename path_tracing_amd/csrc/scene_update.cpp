@@ -1,11 +1,14 @@
 // Scene updates (include/hpt.h): a live scene's triangles, spheres and lights moved in place.  The triangles' tree is
 // refitted on the device (refit_kernels.hip) to the bytes of refit_host_scene (scene_build.cpp), which is the definition;
 // the host's share here is the refusals, packing and uploading the vertices, and the few builder lines that sit between
-// the launches (pad_abs and the dead point from the scene box, the grid from node 0).  Compiled with hipcc (host code only).
+// the launches (pad_abs and the dead point from the scene box, the grid from node 0).  Poses (include/hpt.h, "poses") are two
+// more feeds into the same refit: vertices that are on the device already, and one 3 x 4 record per part applied to a rest
+// pose by k_pose_verts, to the bytes of pose_vertex_host (scene_build.cpp).  Compiled with hipcc (host code only).
 #include "hpt_host.h"
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 
 using namespace hpt;
 
@@ -76,54 +79,39 @@ int ensure_previous(hpt_scene *s){
     return HPT_OK;
 }
 
-} // namespace
+// What an update brings: records from the host (hpt_scene_update_triangles, packed into up.h_verts by the caller), nine floats
+// per triangle on the device, or one record per part applied to the rest pose.  `kind` says which; a scene of zero triangles
+// brings null arrays.
+struct Feed {
+    enum Kind { Records, DeviceVerts, Pose } kind;
+    const void *records = nullptr; const float *d_verts = nullptr; const float *xforms = nullptr;
+};
 
-extern "C" {
-
-int hpt_scene_keep_previous(hpt_scene *s){
-    if(!s) return fail(HPT_ERR_INVALID, "null scene");
-    if(int rc = on_scene_device(s)) return rc;
-    hpt_scene::Update &u = s->up;
-    if(u.prev_ready){         // a scene that was never updated holds no G': it is G
-        const size_t nt = (size_t) s->geo.nt, ns = (size_t) s->geo.ns;
-        if(nt) HIP_TRY(hipMemcpy(u.prev_verts.get(), u.verts.get(), nt * 36, hipMemcpyDeviceToDevice));
-        if(ns){
-            const std::vector<float4> r = pack_spheres(s->geo.h_spheres, s->geo.ns);
-            HIP_TRY(hipMemcpy(u.prev_rounds.get(), r.data(), ns * sizeof(float4), hipMemcpyHostToDevice));
-        }
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    u.motion = false;
-    return HPT_OK;
-}
-
-int hpt_scene_has_motion(const hpt_scene *s){
-    if(!s){ fail(HPT_ERR_INVALID, "null scene"); return -1; }
-    return s->up.motion ? 1 : 0;
-}
-
-int hpt_scene_update_check(const hpt_scene *s, const void *tris, int nt){ return check_triangles(s, tris, nt); }
-
-int hpt_scene_update_triangles(hpt_scene *s, const void *tris, int nt){
-    if(int rc = check_triangles(s, tris, nt)) return rc;
+// The part every triangle update shares: the feed into `verts`, the refit's launches, and the bookkeeping.  With host records
+// it enqueues what hpt_scene_update_triangles always has.
+int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     hpt_scene::Update &u = s->up;
     hpt_scene::Geometry &g = s->geo;
-    if(int rc = ensure_previous(s)) return rc;
+    const int nt = g.nt;
+    const bool pose = f.kind == Feed::Pose;
 
-    // the nine floats of every triangle, input order
     auto t0 = std::chrono::steady_clock::now();
-    u.h_verts.resize((size_t) nt * 9);
-    for(size_t i = 0; i < (size_t) nt; ++i) memcpy(u.h_verts.data() + i * 9, (const unsigned char *) tris + i * HPT_TRIANGLE_BYTES, 36);
-    const double ms_pack = ms_since(t0);
-
-    t0 = std::chrono::steady_clock::now();
     if(int rc = ensure_scratch(s)) return rc;
-    if(nt) HIP_TRY(hipMemcpy(u.verts.get(), u.h_verts.data(), (size_t) nt * 36, hipMemcpyHostToDevice));
+    if(f.kind == Feed::Records){
+        if(nt) HIP_TRY(hipMemcpy(u.verts.get(), u.h_verts.data(), (size_t) nt * 36, hipMemcpyHostToDevice));
+    } else if(f.kind == Feed::DeviceVerts){
+        if(nt) HIP_TRY(hipMemcpy(u.verts.get(), f.d_verts, (size_t) nt * 36, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    } else {
+        HIP_TRY(u.xforms.reserve((size_t) u.num_parts * 12));
+        HIP_TRY(hipMemcpy(u.xforms.get(), f.xforms, (size_t) u.num_parts * 48, hipMemcpyHostToDevice));
+    }
     const double ms_upload = ms_since(t0);
 
     const uint32_t num_nodes = (uint32_t) g.sd.num_nodes;
     float4 *nodes = (float4 *) g.nodes.get();
     HIP_TRY(hipEventRecord(u.ev_a, nullptr));
+    if(pose) launch_pose_verts(nullptr, u.rest_verts.get(), u.tri_part.get(), u.xforms.get(), (uint32_t) u.num_parts, (uint32_t) nt, u.verts.get());
     // leaf records, slot boxes, the live triangles' box and the dead count
     HIP_TRY(hipMemsetAsync(u.result.get(), 0, 8 * sizeof(float), nullptr));
     launch_refit_tris(nullptr, u.verts.get(), (float4 *) g.tris.get(), (uint32_t) nt, (uint32_t) g.sd.num_rounds, u.slot_box.get(), u.partial.get(),
@@ -167,11 +155,150 @@ int hpt_scene_update_triangles(hpt_scene *s, const void *tris, int nt){
     float ms_refit = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms_refit, u.ev_a, u.ev_b));
 
-    if(nt) g.h_tris.assign((const unsigned char *) tris, (const unsigned char *) tris + (size_t) nt * HPT_TRIANGLE_BYTES);
+    // the rest-pose rule: an update that is not a pose leaves the rest pose, and every part at identity
+    if(!pose && u.num_parts && nt){
+        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), (size_t) nt * 36, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    if(f.kind == Feed::Records){
+        if(nt) g.h_tris.assign((const unsigned char *) f.records, (const unsigned char *) f.records + (size_t) nt * HPT_TRIANGLE_BYTES);
+        u.h_tris_stale = false;
+    } else u.h_tris_stale = nt > 0;
     s->bd.ready = false; s->pm.bounds_ready = false;
     u.info.updates += 1; u.info.dead_tris = ndead; u.info.live_tris = (uint64_t) nt - ndead;
     u.info.ms_pack = ms_pack; u.info.ms_upload = ms_upload; u.info.ms_refit = ms_refit;
     u.motion = true;
+    return HPT_OK;
+}
+
+// the refusals the new triangle calls share with the count of check_triangle_update
+int check_count(const hpt_scene *s, int nt){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(nt < 0) return fail(HPT_ERR_INVALID, "negative triangle count");
+    if(nt != s->geo.nt){
+        char msg[200];
+        snprintf(msg, sizeof msg, "an update keeps the triangle count: the scene has %d triangles, %d were handed over", s->geo.nt, nt);
+        return fail(HPT_ERR_INVALID, msg);
+    }
+    return HPT_OK;
+}
+
+} // namespace
+
+int hpt::host_triangles(hpt_scene *s, const unsigned char **tris){
+    hpt_scene::Update &u = s->up;
+    hpt_scene::Geometry &g = s->geo;
+    if(u.h_tris_stale){
+        const size_t nt = (size_t) g.nt;
+        u.h_verts.resize(nt * 9);
+        if(nt) HIP_TRY(hipMemcpy(u.h_verts.data(), u.verts.get(), nt * 36, hipMemcpyDeviceToHost));
+        for(size_t i = 0; i < nt; ++i) memcpy(g.h_tris.data() + i * HPT_TRIANGLE_BYTES, u.h_verts.data() + i * 9, 36);
+        u.h_tris_stale = false;
+    }
+    *tris = g.h_tris.data();
+    return HPT_OK;
+}
+
+extern "C" {
+
+int hpt_scene_keep_previous(hpt_scene *s){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(int rc = on_scene_device(s)) return rc;
+    hpt_scene::Update &u = s->up;
+    if(u.prev_ready){         // a scene that was never updated holds no G': it is G
+        const size_t nt = (size_t) s->geo.nt, ns = (size_t) s->geo.ns;
+        if(nt) HIP_TRY(hipMemcpy(u.prev_verts.get(), u.verts.get(), nt * 36, hipMemcpyDeviceToDevice));
+        if(ns){
+            const std::vector<float4> r = pack_spheres(s->geo.h_spheres, s->geo.ns);
+            HIP_TRY(hipMemcpy(u.prev_rounds.get(), r.data(), ns * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    u.motion = false;
+    return HPT_OK;
+}
+
+int hpt_scene_has_motion(const hpt_scene *s){
+    if(!s){ fail(HPT_ERR_INVALID, "null scene"); return -1; }
+    return s->up.motion ? 1 : 0;
+}
+
+int hpt_scene_update_check(const hpt_scene *s, const void *tris, int nt){ return check_triangles(s, tris, nt); }
+
+int hpt_scene_update_triangles(hpt_scene *s, const void *tris, int nt){
+    if(int rc = check_triangles(s, tris, nt)) return rc;
+    hpt_scene::Update &u = s->up;
+    if(int rc = ensure_previous(s)) return rc;
+
+    // the nine floats of every triangle, input order
+    auto t0 = std::chrono::steady_clock::now();
+    u.h_verts.resize((size_t) nt * 9);
+    for(size_t i = 0; i < (size_t) nt; ++i) memcpy(u.h_verts.data() + i * 9, (const unsigned char *) tris + i * HPT_TRIANGLE_BYTES, 36);
+    const double ms_pack = ms_since(t0);
+
+    Feed f{Feed::Records}; f.records = tris;
+    return refit_from(s, f, ms_pack);
+}
+
+int hpt_scene_update_vertices_device(hpt_scene *s, const void *d_verts, int nt){
+    if(int rc = check_count(s, nt)) return rc;
+    if(nt > 0 && !d_verts) return fail(HPT_ERR_INVALID, "null vertex array");
+    if(int rc = on_scene_device(s)) return rc;
+    if(int rc = ensure_previous(s)) return rc;
+    Feed f{Feed::DeviceVerts}; f.d_verts = (const float *) d_verts;
+    return refit_from(s, f, 0.0);
+}
+
+int hpt_scene_set_parts(hpt_scene *s, const int32_t *tri_part, int nt, int num_parts){
+    if(int rc = check_count(s, nt)) return rc;
+    char msg[200];
+    const char *err = check_parts(tri_part, nt, num_parts, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(int rc = on_scene_device(s)) return rc;
+    if(int rc = ensure_previous(s)) return rc;          // `verts` holds the current geometry from here on
+    hpt_scene::Update &u = s->up;
+    const size_t n = (size_t) nt;
+    u.num_parts = 0;                                     // (a failed allocation leaves the scene without parts)
+    HIP_TRY(u.rest_verts.reserve(std::max<size_t>(n * 9, 1)));
+    HIP_TRY(u.tri_part.reserve(std::max<size_t>(n, 1)));
+    if(n){
+        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), n * 36, hipMemcpyDeviceToDevice));
+        if(tri_part) HIP_TRY(hipMemcpy(u.tri_part.get(), tri_part, n * sizeof(int32_t), hipMemcpyHostToDevice));
+        else HIP_TRY(hipMemset(u.tri_part.get(), 0, n * sizeof(int32_t)));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    u.num_parts = num_parts;
+    return HPT_OK;
+}
+
+int hpt_scene_pose(hpt_scene *s, const float *xforms, int num_parts){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(s->up.num_parts == 0) return fail(HPT_ERR_INVALID, "hpt_scene_pose before hpt_scene_set_parts: the scene has no parts");
+    if(num_parts != s->up.num_parts){
+        char msg[200];
+        snprintf(msg, sizeof msg, "a pose keeps the number of parts: the scene has %d parts, %d records were handed over", s->up.num_parts, num_parts);
+        return fail(HPT_ERR_INVALID, msg);
+    }
+    if(!xforms) return fail(HPT_ERR_INVALID, "null transform array");
+    if(int rc = on_scene_device(s)) return rc;
+    Feed f{Feed::Pose}; f.xforms = xforms;
+    return refit_from(s, f, 0.0);
+}
+
+int hpt_scene_read_triangles(hpt_scene *s, void *out, int nt){
+    if(int rc = check_count(s, nt)) return rc;
+    if(nt > 0 && !out) return fail(HPT_ERR_INVALID, "null triangle array");
+    if(int rc = on_scene_device(s)) return rc;
+    const unsigned char *tris = nullptr;
+    if(int rc = host_triangles(s, &tris)) return rc;
+    if(nt) memcpy(out, tris, (size_t) nt * HPT_TRIANGLE_BYTES);
+    return HPT_OK;
+}
+
+int hpt_pose_host(const void *tris, int nt, const int32_t *tri_part, const float *xforms, int num_parts, void *out){
+    char msg[200];
+    const char *err = pose_host_records(tris, nt, tri_part, xforms, num_parts, out, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
     return HPT_OK;
 }
 
