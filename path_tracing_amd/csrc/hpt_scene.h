@@ -74,11 +74,26 @@ struct DevRound {          // 32 B: sphere or light ball
     uint32_t pad[2];
 };
 
+// What a material is to the shade stage, one bit per question k_shade and bsdf_sample ask of every hit; each bit is the
+// comparison those ask, on the same three floats (material_class below, filled with the table)
+constexpr uint32_t kMatSmoothDielectric = 1u;   // eta > 0 && roughness < 0.001 && metallic < 0.01: the delta transmission lobe
+constexpr uint32_t kMatMirror = 2u;             // metallic > 0.99 && roughness < 0.001: the delta reflection lobe
+constexpr uint32_t kMatNextEvent = 4u;          // eta <= 0 && (metallic < 0.99 || roughness > 0.01): gets a next-event candidate
+constexpr uint32_t kMatMetallic = 8u;           // metallic > 0: Schlick Fresnel, specular weight 1
+
 struct DevMaterial {       // 48 B
     float base[3]; float roughness;
-    float metallic; float eta; uint32_t type; uint32_t pad;
-    float diffuse[3]; float pad2;            // base / pi * (1 - metallic): the diffuse lobe of every BSDF value (geometric.cuh:433)
+    float metallic; float eta; uint32_t type; uint32_t cls;     // cls: kMat* bits (read by k_shade only)
+    float diffuse[3]; float alpha;           // base / pi * (1 - metallic): the diffuse lobe of every BSDF value (geometric.cuh:433);
+                                             // alpha = max(roughness, 1e-3)^2, the GGX width (read by k_shade only)
 };
+
+inline uint32_t material_class(float roughness, float metallic, float eta){
+    return ((eta > 0.0f && roughness < 0.001f && metallic < 0.01f) ? kMatSmoothDielectric : 0u) |
+           ((metallic > 0.99f && roughness < 0.001f) ? kMatMirror : 0u) |
+           ((eta <= 0.0f && (metallic < 0.99f || roughness > 0.01f)) ? kMatNextEvent : 0u) |
+           (metallic > 0.0f ? kMatMetallic : 0u);
+}
 
 struct DevLight {          // 112 B
     float pos[3]; float r;
@@ -86,7 +101,7 @@ struct DevLight {          // 112 B
     float neg_dir[3]; float cutoff;          // normalize(dir * -1) for parallel lights
     float illum[3]; float area;              // 4 * pi * r * r
     uint32_t is_parallel; float cone_ratio;  // (1 - cos_cutoff) / 2
-    uint32_t pad[2];
+    float pdf_area; uint32_t pad;            // 1 / (number of lights * area), the area pdf of a next-event sample (read by k_shade only)
     float raw_dir[3]; uint32_t pad2;         // light.dir as handed over (the BDPT path normalises it itself)
     float ball_c[3]; uint32_t pad3;          // light_ball.center (equals pos for parsed scenes)
 };

@@ -99,6 +99,23 @@ HPT_DEV float rng_next(uint64_t &state){
     uint32_t v = (xs >> rot) | (xs << ((32u - rot) & 31u));
     return (float) (v >> 8) * (1.0f / 16777216.0f);
 }
+// The 24-bit integer k of the stream's next draw (rng_next returns k * 2^-24), for a caller that maps it itself, on a state
+// held as its two 32-bit halves.  The step is lo * M_lo + C once, as one 32x32+64 multiply-add, and the two cross products,
+// three multiplies; left as a 64-bit product in a loop, the compiler multiplies lo * M_lo a second time.  The output
+// permutation on halves: ((old >> 18) ^ old) >> 27 keeps bits 27-58, which are (old >> 27) ^ (old >> 45).
+HPT_DEV uint32_t rng_next_u24(uint32_t &lo, uint32_t &hi){
+    const uint32_t xs = ((hi << 5) | (lo >> 27)) ^ (hi >> 13);
+    const uint32_t rot = hi >> 27;
+    const uint32_t v = (xs >> rot) | (xs << ((32u - rot) & 31u));
+    const uint64_t p = (uint64_t) lo * 0x4C957F2Du + 1442695040888963407ull;
+    hi = (uint32_t) (p >> 32) + lo * 0x5851F42Du + hi * 0x4C957F2Du;
+    lo = (uint32_t) p;
+    return v >> 8;
+}
+// k -> 2 (k * 2^-24) - 1, a coordinate of the unit-ball try.  One fused operation gives the bits of the three separately
+// rounded ones: for k < 2^24 each of k * 2^-24, 2 k * 2^-24 and (k - 2^23) * 2^-23 is a float, so nothing ever rounds
+// (tests/test_ball_coordinate_cpu.py walks every k).
+HPT_DEV float ball_coordinate(uint32_t k){ return fmaf((float) k, 1.0f / 8388608.0f, -1.0f); }
 
 // ---- material record as the BSDF sees it ------------------------------------------------
 struct Mat { f3 base; float roughness, metallic, eta; };
@@ -187,17 +204,22 @@ HPT_DEV ShadeCtx make_shade_ctx(f3 N, f3 wo_w){
 // Terms of a BSDF query that depend on the hit only (material, outgoing direction), for callers that make
 // several queries at one hit: the diffuse lobe (a per-material constant) and Lambda(wo).
 struct ShadePre { f3 diffuse; float lam_o; };
+// Per-material constants of a BSDF query, for a caller whose material table carries them (k_shade; DevMaterial::alpha and
+// ::cls, hpt_scene.h): the GGX width and the outcome of the three comparisons on the material's floats that the functions
+// below otherwise make per query.
+struct MatPre { float alpha; bool metal, smooth_dielectric, mirror; };
 
 // (wo, wi in the local frame of the hit; bsdf_eval_pdf below projects a world direction first)
 template <bool WANT_F = true, bool WANT_PDF = true>
-HPT_DEV void bsdf_eval_pdf_local(const Mat &m, f3 wo, f3 wi, f3 &f_out, float &pdf_out, const ShadePre *pre = nullptr){
+HPT_DEV void bsdf_eval_pdf_local(const Mat &m, f3 wo, f3 wi, f3 &f_out, float &pdf_out, const ShadePre *pre = nullptr, const MatPre *mp = nullptr){
     f_out = mk3(0, 0, 0); pdf_out = 0.0f;
     bool eval_zero = !WANT_F || (wo.z == 0.0f || wi.z == 0.0f);
     bool pdf_zero = !WANT_PDF || (wo.z * wi.z <= 0.0f);
     if(eval_zero && pdf_zero) return;
     if(m.eta > 0.0f && m.roughness < 0.001f) return;
     HPT_PROBE(4, 0);                                               // past the early returns: a value and/or a pdf is wanted
-    float alpha = roughness_to_alpha(m.roughness);
+    const float alpha = mp ? mp->alpha : roughness_to_alpha(m.roughness);
+    const bool metal = mp ? mp->metal : m.metallic > 0.0f;
     f3 whv = wo + wi;
     if(length3(whv) < 1e-6f) return;
     f3 wh = normalize3(whv);
@@ -211,7 +233,7 @@ HPT_DEV void bsdf_eval_pdf_local(const Mat &m, f3 wo, f3 wi, f3 &f_out, float &p
         if(wo.z * wi.z < 0.0f) diffuse = mk3(0, 0, 0);
         float G = 1.0f / (1.0f + lam_o + ggx_lambda(wi, alpha));
         f3 F;
-        if(m.metallic > 0.0f) F = fr_schlick(awo, m.base);
+        if(metal) F = fr_schlick(awo, m.base);
         else { HPT_PROBE(4, 2); float fr = fr_dielectric(dot3(wo, wh), 1.0f, m.eta); F = mk3(fr, fr, fr); }
         f3 specular = (F * D * G) / fmaxf(4.0f * awo * awi, 1e-4f);
         f_out = (wo.z * wi.z > 0.0f) ? diffuse + specular : diffuse;
@@ -222,27 +244,31 @@ HPT_DEV void bsdf_eval_pdf_local(const Mat &m, f3 wo, f3 wi, f3 &f_out, float &p
         float G1 = 1.0f / (1.0f + lam_o);
         float pdf_wh = D * G1 * fmaxf(0.0f, dot3(wo, wh)) / awo;
         float pdf_specular = pdf_wh / (4.0f * dot3(wo, wh) + 1e-7f);
-        float spec_weight = m.metallic > 0.0f ? 1.0f : 0.5f;
+        float spec_weight = metal ? 1.0f : 0.5f;
         float diff_weight = 1.0f - spec_weight;
         pdf_out = diff_weight * pdf_diffuse + spec_weight * pdf_specular;
     }
 }
 
 template <bool WANT_F = true, bool WANT_PDF = true>
-HPT_DEV void bsdf_eval_pdf(const Mat &m, const ShadeCtx &c, f3 wi_w, f3 &f_out, float &pdf_out, const ShadePre *pre = nullptr){
-    bsdf_eval_pdf_local<WANT_F, WANT_PDF>(m, c.wo, to_local(wi_w, c.T, c.B, c.N), f_out, pdf_out, pre);
+HPT_DEV void bsdf_eval_pdf(const Mat &m, const ShadeCtx &c, f3 wi_w, f3 &f_out, float &pdf_out, const ShadePre *pre = nullptr, const MatPre *mp = nullptr){
+    bsdf_eval_pdf_local<WANT_F, WANT_PDF>(m, c.wo, to_local(wi_w, c.T, c.B, c.N), f_out, pdf_out, pre, mp);
 }
 
 // BSDF sampling (geometric.cuh:486-562).  pdf <= 0 means "terminate the path" for both the
 // non-delta rejection and the reference's uninitialised total-internal-reflection return.
+// ZERO_FILL = false: wi_w and f are written only where pdf comes out positive, for a caller that reads them only then
+// (k_shade: zeros that nobody reads cost a register fill at every join of its divergent branches).
+template <bool ZERO_FILL = true>
 HPT_DEV void bsdf_sample(const Mat &m, const ShadeCtx &c, float u_rr, float u1, float u2, float cur_eta,
-                         f3 &wi_w, f3 &f, float &pdf, bool &is_delta, float &new_eta, const ShadePre *pre = nullptr){
+                         f3 &wi_w, f3 &f, float &pdf, bool &is_delta, float &new_eta, const ShadePre *pre = nullptr, const MatPre *mp = nullptr){
     is_delta = false;
     new_eta = cur_eta;
-    wi_w = mk3(0, 0, 0); f = mk3(0, 0, 0); pdf = 0.0f;
+    if(ZERO_FILL){ wi_w = mk3(0, 0, 0); f = mk3(0, 0, 0); }
+    pdf = 0.0f;
     f3 wo = c.wo;
     f3 wi;
-    if(m.eta > 0.0f && m.roughness < 0.001f && m.metallic < 0.01f){
+    if(mp ? mp->smooth_dielectric : (m.eta > 0.0f && m.roughness < 0.001f && m.metallic < 0.01f)){
         HPT_PROBE(3, 0);                                           // smooth dielectric
         is_delta = true;
         float F = fr_dielectric(wo.z, cur_eta, m.eta);
@@ -265,7 +291,7 @@ HPT_DEV void bsdf_sample(const Mat &m, const ShadeCtx &c, float u_rr, float u1, 
         wi_w = to_world(wi, c.T, c.B, c.N);
         return;
     }
-    if(m.metallic > 0.99f && m.roughness < 0.001f){
+    if(mp ? mp->mirror : (m.metallic > 0.99f && m.roughness < 0.001f)){
         HPT_PROBE(3, 1);                                           // mirror
         is_delta = true;
         wi = mk3(-wo.x, -wo.y, wo.z);
@@ -274,8 +300,8 @@ HPT_DEV void bsdf_sample(const Mat &m, const ShadeCtx &c, float u_rr, float u1, 
         wi_w = to_world(wi, c.T, c.B, c.N);
         return;
     }
-    float alpha = roughness_to_alpha(m.roughness);
-    float spec_weight = m.metallic > 0.0f ? 1.0f : 0.5f;
+    const float alpha = mp ? mp->alpha : roughness_to_alpha(m.roughness);
+    float spec_weight = (mp ? mp->metal : m.metallic > 0.0f) ? 1.0f : 0.5f;
     // both lobes start from the same disk point (geometric.cuh:205-207 and :393-396); computed once, ahead of
     // the branch the lanes of a wave split on
     float r = sqrtf(u1);
@@ -292,7 +318,7 @@ HPT_DEV void bsdf_sample(const Mat &m, const ShadeCtx &c, float u_rr, float u1, 
     }
     HPT_PROBE(3, 3);                                               // both lobes: value and pdf of the sampled direction
     wi_w = to_world(wi, c.T, c.B, c.N);
-    bsdf_eval_pdf(m, c, wi_w, f, pdf, pre);
+    bsdf_eval_pdf(m, c, wi_w, f, pdf, pre, mp);
 }
 
 // ---- primitive tests --------------------------------------------------------------------

@@ -67,8 +67,9 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
     // evaluates the first n staged records, one per lane (pt_cu.cu:136-146 parallel lights, :179-196 ball lights);
     // rec_base = first queue position of the chunk the records belong to (staged records never outlive their chunk)
     auto flush_nee = [&](uint32_t n, uint32_t rec_base){
-        bool want = false; uint32_t spath = 0u;
-        f3 c = mk3(0, 0, 0), org = mk3(0, 0, 0), dir = mk3(0, 0, 1); float dist = 0.0f;
+        bool want = false;
+        // written where `want` is set and read under it only: no initialisers, a default would be filled in at every join
+        uint32_t spath; f3 c, org, dir; float dist;
         if(lane < n){
             HPT_SECTION(2, 3);                                         // section h: staged next-event evaluation
             f3 wo_l = mk3(u2f(stage[0][lane]), u2f(stage[1][lane]), u2f(stage[2][lane]));
@@ -84,9 +85,11 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
             const DevLight &L = (sc.num_lights <= kLdsLights ? s_lights : sc.lights)[light_i & 0x7FFFFFFFu];
             Mat m; m.base = mk3(dm.base[0], dm.base[1], dm.base[2]); m.roughness = dm.roughness; m.metallic = dm.metallic; m.eta = dm.eta;
             pre.diffuse = mk3(dm.diffuse[0], dm.diffuse[1], dm.diffuse[2]);
+            MatPre mp; mp.alpha = dm.alpha; mp.metal = (dm.cls & kMatMetallic) != 0u;
+            mp.smooth_dielectric = (dm.cls & kMatSmoothDielectric) != 0u; mp.mirror = (dm.cls & kMatMirror) != 0u;
             f3 illum = mk3(L.illum[0], L.illum[1], L.illum[2]);
             f3 brdf; float pdf_bsdf;
-            bsdf_eval_pdf_local(m, wo_l, wi_l, brdf, pdf_bsdf, &pre);
+            bsdf_eval_pdf_local(m, wo_l, wi_l, brdf, pdf_bsdf, &pre, &mp);
             const float cos_surface = fmaxf(0.0f, wi_l.z);           // = max(0, dot(normal, wi)): the frame's third axis is the normal
             f3 contrib;
             if(light_i >> 31) contrib = thr * brdf * illum * mk3(1.0f, 1.0f, 1.0f) * cos_surface * (float) sc.num_lights;
@@ -151,10 +154,13 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
     for(uint32_t base = begin; base < end; base += kBlock){
         uint32_t i = base + threadIdx.x;
         bool alive = false, nee = false;
-        uint32_t path = 0;
-        // the next-event candidate of this lane's path, if it gets one (record layout: kNeeWords)
-        f3 n_wo = mk3(0, 0, 0), n_wi = mk3(0, 0, 0), n_thr = mk3(0, 0, 0), s_p1 = mk3(0, 0, 0), s_p2 = mk3(0, 0, 0);
-        float n_lam = 0.0f, n_pdf_light = 0.0f; uint32_t n_mat = 0u, n_light = 0u;
+        // `path` is read under `alive` or `nee`, which only a lane with a queue entry sets.  The next-event candidate of this
+        // lane's path, if it gets one (record layout: kNeeWords), is read under `nee`: the hit-level words are written at
+        // every surface hit, the others in both branches that set `nee` (parallel light, ball light).  None has an initialiser -- the compiler would fill all
+        // twenty-one registers with it at the head of every trip and again at the joins of the divergent branches below.
+        uint32_t path;
+        f3 n_wo, n_wi, n_thr, s_p1, s_p2;
+        float n_lam, n_pdf_light; uint32_t n_mat, n_light;
         if(i < count){
             path = queue ? queue[i] : i;
             ++iters;
@@ -181,13 +187,13 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                 int delta_count = (int) ((flags >> 16) & 0xFFu);
                 f3 pos = ro + rd * t;
                 f3 wo = rd * -1.0f;
-                f3 normal; uint32_t mat_idx = 0; bool is_light = false; uint32_t light_idx = 0;
-                bool have_frame = false; f3 frame_T = mk3(0, 0, 0), frame_B = mk3(0, 0, 0);
+                f3 normal; uint32_t mat_idx; bool is_light = false;
+                bool have_frame = false; f3 frame_T, frame_B;                 // the frame: read under have_frame
                 if(prim & kHitRoundFlag){
                     DevRound r = sc.rounds[prim & 0x7FFFFFFFu];
                     normal = normalize3(pos - mk3(r.c[0], r.c[1], r.c[2]));
                     is_light = (r.flags & 2u) != 0u;
-                    mat_idx = r.material; light_idx = r.material;
+                    mat_idx = r.material;                             // light balls: the light's index
                     if(dot3(normal, rd) > 0.0f) normal = normal * -1.0f;
                 } else {
                     // the triangle's unit normal and the local frames of both orientations were computed once
@@ -207,7 +213,7 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
 
                 if(is_light){                                          // pt_cu.cu:59-122
                     HPT_SECTION(1, 1);                                 // section b: light hit
-                    const DevLight &hl = lights[light_idx];
+                    const DevLight &hl = lights[mat_idx];
                     f3 emission = mk3(hl.illum[0], hl.illum[1], hl.illum[2]);
                     float area = 1.0f, cone_ratio = 1.0f;
                     bool valid_light = false;
@@ -249,7 +255,10 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                     ShadePre pre; pre.diffuse = mk3(dm.diffuse[0], dm.diffuse[1], dm.diffuse[2]);     // uploaded with the scene
                     // a delta lobe does not count as a bounce; any other material's path ends at max_depth, so on
                     // its last bounce the sampled direction would never be used (pt_cu.cu:37, 228-241)
-                    const bool delta_mat = (m.eta > 0.0f && m.roughness < 0.001f && m.metallic < 0.01f) || (m.metallic > 0.99f && m.roughness < 0.001f);
+                    // (the comparisons on the material's three floats come with the table: DevMaterial::cls, ::alpha)
+                    MatPre mp; mp.alpha = dm.alpha; mp.metal = (dm.cls & kMatMetallic) != 0u;
+                    mp.smooth_dielectric = (dm.cls & kMatSmoothDielectric) != 0u; mp.mirror = (dm.cls & kMatMirror) != 0u;
+                    const bool delta_mat = (dm.cls & (kMatSmoothDielectric | kMatMirror)) != 0u;
                     const bool last_bounce = !delta_mat && depth + 1 >= max_depth;
                     uint64_t rs;
                     if(PRIMARY) rs = p_rs;
@@ -257,7 +266,7 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                     ShadeCtx ctx;
                     if(have_frame){ ctx.N = normal; ctx.T = frame_T; ctx.B = frame_B; ctx.wo = to_local(wo, frame_T, frame_B, normal); }
                     else ctx = make_shade_ctx(normal, wo);
-                    pre.lam_o = ggx_lambda(ctx.wo, roughness_to_alpha(m.roughness));     // shared by the NEE and the sampled query
+                    pre.lam_o = ggx_lambda(ctx.wo, mp.alpha);     // shared by the NEE and the sampled query
                     // the hit-level words of a next-event record are set here, outside the nested branches behind the rejection
                     // loop.  (With them inside both branches hipcc 7.2's SLP vectorizer dropped the y component of the packed
                     // x/y pairs -- green = 0 in every contribution, caught by tests/test_gpu_parity.py on input.txt; the build
@@ -266,7 +275,7 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                     s_p1 = pos + normal * kEps;
 
                     // next-event estimation, pt_cu.cu:125-202
-                    if(m.eta <= 0.0f && (m.metallic < 0.99f || m.roughness > 0.01f) && sc.num_lights > 0){
+                    if((dm.cls & kMatNextEvent) != 0u && sc.num_lights > 0){
                         int l_idx = min((int) (rng_next(rs) * sc.num_lights), sc.num_lights - 1);
                         const DevLight &L = lights[l_idx];
                         if(L.is_parallel){
@@ -276,15 +285,19 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                                 nee = true;
                                 n_wi = to_local(light_dir, ctx.T, ctx.B, ctx.N);
                                 n_light = (uint32_t) l_idx | 0x80000000u;
+                                n_pdf_light = 0.0f;                // a parallel light has no area pdf: the record's word is staged all the same
                                 s_p2 = pos + light_dir * 1e4f;
                             }
                         } else {
                             f3 d_local;
+                            uint32_t rs_lo = (uint32_t) rs, rs_hi = (uint32_t) (rs >> 32);     // the stream, in halves through the tries
                             do {
                                 HPT_SECTION(1, 3);                     // section d: one try of the unit-ball rejection loop
-                                float a = rng_next(rs), b = rng_next(rs), c = rng_next(rs);
-                                d_local = mk3(a, b, c) * 2.0f - mk3(1.0f, 1.0f, 1.0f);
+                                // = mk3(a, b, c) * 2.0f - mk3(1.0f, 1.0f, 1.0f) of three rng_next draws, bit for bit
+                                const uint32_t a = rng_next_u24(rs_lo, rs_hi), b = rng_next_u24(rs_lo, rs_hi), c = rng_next_u24(rs_lo, rs_hi);
+                                d_local = mk3(ball_coordinate(a), ball_coordinate(b), ball_coordinate(c));
                             } while(dot3(d_local, d_local) >= 1.0f);
+                            rs = ((uint64_t) rs_hi << 32) | (uint64_t) rs_lo;
                             HPT_SECTION(2, 0);                         // section e: next-event geometry behind the loop
                             if(length3(d_local) > 0.001f) d_local = normalize3(d_local);
                             else d_local = mk3(0, 1, 0);
@@ -301,9 +314,8 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                                     if(dot3(mk3(L.main_dir[0], L.main_dir[1], L.main_dir[2]), wi_light * -1.0f) < L.cos_cutoff) inside_cone = false;
                                 }
                                 if(inside_cone){
-                                    float pdf_light_area = 1.0f / (sc.num_lights * L.area);
                                     nee = true;
-                                    n_pdf_light = pdf_light_area * dist2 / fmaxf(cos_light, 1e-6f);
+                                    n_pdf_light = L.pdf_area * dist2 / fmaxf(cos_light, 1e-6f);
                                     n_wi = to_local(wi_light, ctx.T, ctx.B, ctx.N);
                                     n_light = (uint32_t) l_idx;
                                     s_p2 = light_pos + d_local * kEps;
@@ -313,11 +325,12 @@ void k_shade(SceneDev sc, PathBuf pb, const uint32_t *queue, const uint32_t *qco
                     }
 
                     // BSDF sampling and path continuation, pt_cu.cu:204-241
-                    f3 wi = mk3(0, 0, 0), bsdf_val = mk3(0, 0, 0); float pdf_omega = 0.0f, new_eta = ray_eta; bool is_delta = false;
+                    // what bsdf_sample hands back is read where pdf_omega > 0 only, and it writes all of it on those paths
+                    f3 wi, bsdf_val; float pdf_omega = 0.0f, new_eta; bool is_delta;
                     if(!last_bounce){
                         HPT_SECTION(2, 1);                             // section f: direction sampling
                         float u_rr = rng_next(rs), u1 = rng_next(rs), u2 = rng_next(rs);
-                        bsdf_sample(m, ctx, u_rr, u1, u2, ray_eta, wi, bsdf_val, pdf_omega, is_delta, new_eta, &pre);
+                        bsdf_sample<false>(m, ctx, u_rr, u1, u2, ray_eta, wi, bsdf_val, pdf_omega, is_delta, new_eta, &pre, &mp);
                     }
                     if(!(pdf_omega <= 0.0f)){          // pt_cu.cu:214 (and the TIR return, defined: terminate)
                         HPT_SECTION(2, 2);                             // section g: throughput update and continuation

@@ -375,17 +375,32 @@ struct MatKey {
     bool operator<(const MatKey &o) const { return memcmp(w, o.w, sizeof w) < 0; }
 };
 
+// the record's per-material constants of the shade stage, from its roughness, metallic and eta: the class bits and the GGX
+// width, roughness_to_alpha (pt_device_math.h) operation for operation
+void material_constants(DevMaterial &d){
+    d.cls = material_class(d.roughness, d.metallic, d.eta);
+    float x = fmaxf(d.roughness, 1e-3f);
+    d.alpha = x * x;
+}
+
+// the table's stand-in entry of a scene without surfaces
+DevMaterial blank_material(){
+    DevMaterial m; memset(&m, 0, sizeof m);
+    material_constants(m);
+    return m;
+}
+
 uint32_t intern_material(const RefMat &m, std::map<MatKey, uint32_t> &table, std::vector<DevMaterial> &out){
     MatKey k; memcpy(k.w, &m, sizeof k.w);
     auto it = table.find(k);
     if(it != table.end()) return it->second;
     DevMaterial d;
     d.base[0] = m.base[0]; d.base[1] = m.base[1]; d.base[2] = m.base[2];
-    d.roughness = m.roughness; d.metallic = m.metallic; d.eta = m.eta; d.type = (uint32_t) m.type; d.pad = 0;
+    d.roughness = m.roughness; d.metallic = m.metallic; d.eta = m.eta; d.type = (uint32_t) m.type;
     // same float operations as the kernel's `m.base / kPi * (1.0f - m.metallic)` (IEEE divide, no contraction)
     const float pi = 3.14159265358979323846f;
     for(int a = 0; a < 3; ++a){ float q = m.base[a] / pi; d.diffuse[a] = q * (1.0f - m.metallic); }
-    d.pad2 = 0.0f;
+    material_constants(d);
     uint32_t idx = (uint32_t) out.size();
     out.push_back(d);
     table.emplace(k, idx);
@@ -579,6 +594,7 @@ const char *flatten_rounds_host(const void *lights_v, int nl, const void *sphere
         d.area = 4.0f * kPi * L.ball.r * L.ball.r;    // pt_cu.cu:70,179
         d.is_parallel = L.is_parallel ? 1u : 0u;
         d.cone_ratio = (1.0f - d.cos_cutoff) / 2.0f;  // pt_cu.cu:73
+        d.pdf_area = 1.0f / ((float) nl * d.area);    // k_shade's area pdf of a next-event sample, as it formed it per sample; a function of the COUNT too
         lights_out.push_back(d);
     }
     return "";
@@ -919,7 +935,7 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
     lap("triangles");
     auto t1 = std::chrono::steady_clock::now();
     hs.ms_bvh_build = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if(hs.materials.empty()){ DevMaterial m; memset(&m, 0, sizeof m); hs.materials.push_back(m); }
+    if(hs.materials.empty()) hs.materials.push_back(blank_material());
     return "";
 }
 
@@ -1040,7 +1056,7 @@ const char *build_bdpt_host_scene(const void *lights_v, int nl, const void *sphe
         out.groups.push_back(g);
         ++gi;
     }
-    if(out.materials.empty()){ DevMaterial m; memset(&m, 0, sizeof m); out.materials.push_back(m); }
+    if(out.materials.empty()) out.materials.push_back(blank_material());
     if(out.nodes.empty()){ BvhNode n; memset(&n, 0, sizeof n); out.nodes.push_back(n); }
     return "";
 }

@@ -5,7 +5,8 @@ Makefile's HIPFLAGS and counts, per kernel and per basic block, the instruction 
   copies   v_mov_b32 vA, vB -- a plain VGPR-to-VGPR copy, what a failed register coalescing leaves behind
   lane     v_readlane / v_writelane (SGPR spills to lanes of a VGPR and their reloads)
   scratch  scratch_* loads and stores (VGPR spills)
-plus the register and spill counts of the kernel's metadata.  It counts nothing else.
+plus the register and spill counts of the kernel's metadata.  It counts nothing else.  listing() keeps every block's
+instructions and the compiler's loop notes, for questions the report does not ask (tests/test_shade_isa_cpu.py).
 usage: python scripts/isa_report.py [file.hip ...] [--filter SUBSTR] [--min-valu 8] [--no-blocks] [--asm-out DIR]
        (default file: path_tracing_amd/csrc/pt_trace.hip)
        python scripts/isa_report.py --digest [file.hip ...]    one line per kernel: name, instructions, SHA-256 of its body
@@ -171,6 +172,46 @@ def parse(asm):
             cur["counts"][k] += 1
             block["counts"][k] += 1
     return kernels
+
+
+_ZERO_MOVE = re.compile(r"^v_mov_b32(_e32)?\s+v\d+,\s*0\s*$")
+
+
+def listing(asm):
+    """{kernel name: [{label, note, code[...]}]}: every basic block of every kernel with its instructions (comments cut) and
+    the compiler's loop note (the label's line and the comment lines after it)."""
+    meta = _metadata(asm)
+    out, cur, block = {}, None, None
+    lines = asm.splitlines()
+    for i, line in enumerate(lines):
+        m = re.match(r"^([A-Za-z_$][\w$.]*):", line)
+        if m and m.group(1) in meta:
+            block = {"label": "entry", "note": "", "code": []}
+            cur = out.setdefault(short_name(m.group(1)), [])
+            cur.append(block)
+            continue
+        if cur is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            cur = block = None
+            continue
+        s = line.strip()
+        lab = _LABEL.match(s)
+        ft = _FALLTHROUGH.match(s) if not lab else None
+        if lab or ft:
+            note, j = s, i + 1
+            while j < len(lines) and lines[j].strip().startswith(";"):
+                note += " " + lines[j].strip()
+                j += 1
+            if ft and ft.group(1) == "0":
+                continue
+            block = {"label": lab.group(1) if lab else "%bb." + ft.group(1), "note": note, "code": []}
+            cur.append(block)
+            continue
+        code = line.split(";", 1)[0].strip()
+        if code and code[0] != "." and not code.endswith(":"):
+            block["code"].append(code)
+    return out
 
 
 _LOCAL_LABEL = re.compile(r"(\.LBB|\.Lfunc_[A-Za-z_]*)\d+")
