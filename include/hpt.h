@@ -862,7 +862,7 @@ int hpt_bvh_refit_host(const void *lights, int num_lights, const void *spheres, 
  * those that need no scene.  A scene of zero triangles accepts all of these calls with zero counts.  A refused call leaves
  * the handle as it was.
  *
- * Out of scope: blend-weight skinning; poses for spheres and lights (hpt_scene_update_rounds is a small upload already);
+ * Out of scope: blend-weight skinning (it is "skinning" below); poses for spheres and lights (hpt_scene_update_rounds is a small upload already);
  * a non-blocking or caller-stream variant; hpt_multi_*.
  *
  * pt_cli --frames N --obj mesh.obj --spin-device DEG is --spin through these calls: hpt_scene_set_parts once (part 0:
@@ -875,6 +875,70 @@ int hpt_scene_pose(hpt_scene *scene, const float *xforms, int num_parts);
 int hpt_scene_read_triangles(hpt_scene *scene, void *triangles_out, int num_triangles);
 int hpt_pose_host(const void *triangles, int num_triangles, const int32_t *tri_part,
                   const float *xforms, int num_parts, void *triangles_out);
+
+/* ---- skinning -------------------------------------------------------------------------------------------------
+ * A pose moves rigid parts; a skin deforms: every CORNER -- one vertex of one triangle, corner 3 * i + k being v_k of input
+ * triangle i (the handle keeps nine floats per triangle, not an indexed mesh) -- follows up to HPT_SKIN_INFLUENCES bones
+ * with a weight each, blended over the rest pose on the device.  It ends in the same refit as every update, with the same
+ * guarantees as a pose: a definition the host restates byte for byte, static vertices whose bits never change, and
+ * everything downstream (the previous geometry, the motion guide, every integrator, the lazy host records) untouched.
+ *
+ * hpt_scene_set_skin takes corner_bone and corner_weight, num_triangles * 3 * 4 entries each: four (bone, weight)
+ * influences per corner, in order; num_bones lies in [1, 65536].  It captures the rest pose exactly as hpt_scene_set_parts
+ * does, uploads the influences once (24 bytes per corner: the bones as four 16-bit indices; with the rest pose 108 bytes
+ * per triangle, allocated here -- a scene that never calls it pays nothing), is blocking and runs on the null stream.  It
+ * may be called again, which gives a new table and a new rest pose.  The geometry does not change (hpt_scene_has_motion is
+ * not set).
+ *
+ * One deformer per scene: a scene holds parts or a skin.  hpt_scene_set_skin drops the parts (hpt_scene_pose is then
+ * refused as before hpt_scene_set_parts) and hpt_scene_set_parts drops the skin; the two share the rest pose.  The
+ * rest-pose rule of "poses" covers the skin: hpt_scene_update_triangles and hpt_scene_update_vertices_device set the rest
+ * pose to the geometry they leave; the influences are kept.
+ *
+ * hpt_scene_skin takes num_bones records of 12 floats, the rows (a, b, c, t) of hpt_scene_pose; num_bones must be the value
+ * given to hpt_scene_set_skin.  It is absolute, like a pose.  hpt_scene_get_update_info reports it as a pose: ms_pack is 0,
+ * ms_upload the table's upload, ms_refit the device part, the skin kernel included.  The host records are brought up to date
+ * lazily, as after a pose.
+ *
+ * The definition.  IEEE float, evaluated as written, left to right, no contraction.  A corner has the rest vertex (x, y, z)
+ * and influences (b_j, w_j), j = 0..3.  Influence j is ACTIVE if the 32 bits of w_j are not zero.  arith(r) is the three
+ * rows of record r, each ((r.a * x + r.b * y) + r.c * z) + r.t, as in a pose.  Three cases, tested in this order:
+ *   keep    every active influence's record has the identity's 48 bytes, +0 throughout -- this includes a corner with no
+ *           active influence.  The vertex keeps its bits: a -0 stays -0, a NaN keeps its payload.  Static geometry is
+ *           given four zero weights and never moves by a bit.
+ *   rigid   exactly one influence is active and its weight has the bits of 1.0f: the result is arith of that bone's
+ *           record, then the non-finite rule -- the bytes of hpt_scene_pose with that record.  A skin with one-hot
+ *           weights IS a pose, byte for byte.
+ *   blend   anything else.  For the active influences in index order p_j = arith(record[b_j]) -- plain arithmetic even
+ *           for a record that is the identity -- and per component acc = w_j * p_j for the first active influence,
+ *           acc = acc + w_j * p_j for each later one; then the non-finite rule.  Weights are not normalised and their sum
+ *           is not checked.
+ * The non-finite rule is the pose's: if any of the three results has all exponent bits set, all three words become
+ * 0x7FC00000; the triangle is dead and a later skin revives it.  An inactive influence is never evaluated: a bone whose
+ * record is NaN kills only the corners on which it has weight.  A non-finite entry of xforms is not refused.
+ *
+ * hpt_skin_host is the definition, on the host alone (no device): triangles_out gets the records of `triangles` with every
+ * corner skinned as above; it may be `triangles` itself.
+ *
+ * Refusals, HPT_ERR_INVALID with a message before anything touches the device: a null scene, or a null array with a
+ * non-zero count; a count that is not the scene's; num_bones outside [1, 65536]; a bone index outside [0, num_bones),
+ * active or not, and a weight with its sign bit set, NaN or infinite (the message names the first triangle and corner);
+ * hpt_scene_skin before hpt_scene_set_skin or with another num_bones; a null xforms; a current device other than the
+ * scene's.  hpt_skin_host makes those that need no scene.  A scene of zero triangles accepts all three calls with zero
+ * counts.  A refused call leaves the handle as it was.
+ *
+ * Out of scope: an indexed mesh (shared vertices skinned once); more than four influences; dual-quaternion blending;
+ * a non-blocking or caller-stream variant; hpt_multi_*.
+ *
+ * pt_cli --frames N --obj mesh.obj --twist-device DEG twists the OBJ about the vertical axis through its centroid: two
+ * bones, bone 0 at identity and bone 1 --spin-device's turn of f * DEG; an OBJ corner at height y has the weight
+ * t = clamp((y - ymin) / (ymax - ymin), 0, 1) on bone 1 and 1 - t on bone 0, every other corner four zero weights. */
+#define HPT_SKIN_INFLUENCES 4
+int hpt_scene_set_skin(hpt_scene *scene, const int32_t *corner_bone, const float *corner_weight,
+                       int num_triangles, int num_bones);
+int hpt_scene_skin(hpt_scene *scene, const float *xforms, int num_bones);
+int hpt_skin_host(const void *triangles, int num_triangles, const int32_t *corner_bone,
+                  const float *corner_weight, const float *xforms, int num_bones, void *triangles_out);
 
 /* ---- motion ---------------------------------------------------------------------------------------------
  * hpt_history keeps a viewer's accumulation when the camera moves, and the scene updates move the geometry in place; this

@@ -183,7 +183,7 @@ def load_library() -> C.CDLL:
                      "hpt_bvh_refit_host", "hpt_scene_keep_previous", "hpt_scene_has_motion", "hpt_render_guides_motion",
                      "hpt_render_guides_motion_device", "hpt_history_advance_motion", "hpt_history_motion_check",
                      "hpt_scene_update_vertices_device", "hpt_scene_set_parts", "hpt_scene_pose", "hpt_scene_read_triangles",
-                     "hpt_pose_host"):
+                     "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -425,6 +425,21 @@ class Scene:
             raise HptError("hpt error 1: pose: twelve floats per part")
         _check(self._lib.hpt_scene_pose(self._h, _vp(x), x.size // 12))
 
+    # -- skinning (include/hpt.h) ------------------------------------------------------------
+    def set_skin(self, corner_bone, corner_weight, num_bones):
+        """Gives every corner four (bone, weight) influences -- int32 and float32 of shape [nt, 3, 4] (or flat) -- and
+        captures the rest pose; the scene's parts, if it had any, are dropped."""
+        b, w = _skin_arrays("set_skin", corner_bone, corner_weight)
+        _check(self._lib.hpt_scene_set_skin(self._h, _vp(b), _vp(w), b.size // 12, int(num_bones)))
+
+    def skin(self, xforms):
+        """One absolute skin: [num_bones, 3, 4] (or [num_bones, 12]) float32, rows (a, b, c, t), blended over the rest pose
+        on the device; the tree is refitted.  Blocking."""
+        x = np.ascontiguousarray(xforms, np.float32)
+        if x.size % 12:
+            raise HptError("hpt error 1: skin: twelve floats per bone")
+        _check(self._lib.hpt_scene_skin(self._h, _vp(x), x.size // 12))
+
     def read_triangles(self) -> np.ndarray:
         """The records the handle holds now (layouts.TRIANGLE): the scene's non-vertex bytes with the current vertices."""
         out = np.zeros(self.num_triangles, TRIANGLE)
@@ -444,7 +459,7 @@ class Scene:
         return rc == 1
 
     def update_info(self) -> dict:
-        """The last triangle update of any kind (update_triangles, update_vertices_device, pose): dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
+        """The last triangle update of any kind (update_triangles, update_vertices_device, pose, skin): dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
         info = UpdateInfo()
         _check(self._lib.hpt_scene_get_update_info(self._h, C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_}
@@ -917,6 +932,30 @@ def pose_host(triangles, tri_part, xforms) -> np.ndarray:
         raise HptError("hpt error 1: pose_host: one part index per triangle (%d triangles, %d indices)" % (len(tr), len(tp)))
     out = np.zeros(len(tr), TRIANGLE)
     _check(load_library().hpt_pose_host(_vp(tr), len(tr), _vp(tp) if tp is not None else None, _vp(x), x.size // 12, _vp(out)))
+    return out
+
+
+def _skin_arrays(what, corner_bone, corner_weight):
+    b = np.ascontiguousarray(corner_bone, np.int32)
+    w = np.ascontiguousarray(corner_weight, np.float32)
+    if b.size % 12 or w.size != b.size:
+        raise HptError("hpt error 1: %s: four bones and four weights per corner, three corners per triangle (%d bones, %d weights)"
+                       % (what, b.size, w.size))
+    return b, w
+
+
+def skin_host(triangles, corner_bone, corner_weight, xforms) -> np.ndarray:
+    """hpt_skin_host, the definition of Scene.skin on the host (no device needed): the records with every corner skinned
+    by its four influences over xforms ([num_bones, 3, 4] float32)."""
+    tr = np.ascontiguousarray(triangles, TRIANGLE)
+    b, w = _skin_arrays("skin_host", corner_bone, corner_weight)
+    x = np.ascontiguousarray(xforms, np.float32)
+    if x.size % 12:
+        raise HptError("hpt error 1: skin_host: twelve floats per bone")
+    if b.size != len(tr) * 12:
+        raise HptError("hpt error 1: skin_host: twelve influences per triangle (%d triangles, %d influences)" % (len(tr), b.size))
+    out = np.zeros(len(tr), TRIANGLE)
+    _check(load_library().hpt_skin_host(_vp(tr), len(tr), _vp(b), _vp(w), _vp(x), x.size // 12, _vp(out)))
     return out
 
 

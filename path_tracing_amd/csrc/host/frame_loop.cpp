@@ -63,7 +63,9 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     DeviceMem d_prev_position;                                                         // --spin --reproject
     const bool posed = motion && motion->pose_at;                                      // --spin-device
     if(posed && (motion->triangles_at || !motion->parts_of)){ std::cerr << "[Error] a pose needs a part map, and excludes edited records" << std::endl; return -1; }
-    const bool spin = motion && (motion->triangles_at || posed);
+    const bool skinned = motion && motion->skin_at;                                    // --twist-device
+    if(skinned && (motion->triangles_at || posed || !motion->skin_of)){ std::cerr << "[Error] a skin needs an influence table, and excludes poses and edited records" << std::endl; return -1; }
+    const bool spin = motion && (motion->triangles_at || posed || skinned);
     if(spin && (!run.triangles || run.num_triangles < 1)){ std::cerr << "[Error] --spin: the scene has no triangles" << std::endl; return -1; }
     std::vector<unsigned char> spun;                                                   // this frame's triangle records
     std::vector<float> xforms;                                                         // this frame's pose, 12 floats per part
@@ -73,6 +75,14 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         if((int) tri_part.size() != run.num_triangles){ std::cerr << "[Error] --spin-device: one part per triangle" << std::endl; return -1; }
         if(hpt_scene_set_parts(run.scene, tri_part.data(), run.num_triangles, num_parts) != HPT_OK) return hpt_failed("hpt_scene_set_parts");
         xforms.resize((size_t) num_parts * 12);
+    }
+    if(skinned){     // once: the influence table, and the rest pose the scene captures with it
+        std::vector<int32_t> corner_bone; std::vector<float> corner_weight;
+        const int num_bones = motion->skin_of(run.triangles, run.num_triangles, corner_bone, corner_weight);
+        const size_t entries = (size_t) run.num_triangles * 3 * HPT_SKIN_INFLUENCES;
+        if(corner_bone.size() != entries || corner_weight.size() != entries){ std::cerr << "[Error] --twist-device: four influences per corner" << std::endl; return -1; }
+        if(hpt_scene_set_skin(run.scene, corner_bone.data(), corner_weight.data(), run.num_triangles, num_bones) != HPT_OK) return hpt_failed("hpt_scene_set_skin");
+        xforms.resize((size_t) num_bones * 12);
     }
     Loop L;
     if(!d_frame.alloc(values * sizeof(float)) || !d_mean.alloc(values * sizeof(float)) || !d_rgb8.alloc(values) ||
@@ -121,7 +131,10 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         const bool updated = spin && f > 0;
         if(updated){     // blocking, on the null stream: the last frame's work on the loop's stream has ended with its metrics
             if(hipError_t e = hipStreamSynchronize(L.stream)) return hip_failed("stream", e);
-            if(posed){       // twelve floats per part: no record is copied, no vertex is touched on the host
+            if(skinned){     // twelve floats per bone
+                motion->skin_at(f, xforms.data(), (int) (xforms.size() / 12));
+                if(hpt_scene_skin(run.scene, xforms.data(), (int) (xforms.size() / 12)) != HPT_OK) return hpt_failed("hpt_scene_skin");
+            } else if(posed){       // twelve floats per part: no record is copied, no vertex is touched on the host
                 motion->pose_at(f, xforms.data(), (int) (xforms.size() / 12));
                 if(hpt_scene_pose(run.scene, xforms.data(), (int) (xforms.size() / 12)) != HPT_OK) return hpt_failed("hpt_scene_pose");
             } else {

@@ -57,11 +57,18 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // copying a record: before frame 0 parts_of fills one part index per triangle from the moved scene's records and returns
 // the number of parts, which goes to hpt_scene_set_parts once; before frame f > 0 pose_at fills 12 floats per part and the
 // loop calls hpt_scene_pose (include/hpt.h, "poses").  Everything else is as with `triangles_at`.
+//
+// With `skin_at` (--twist-device; needs `skin_of`, excludes `triangles_at` and `pose_at`) the geometry deforms: before frame 0
+// skin_of fills four bones and four weights per corner from the moved scene's records and returns the number of bones, which
+// goes to hpt_scene_set_skin once; before frame f > 0 skin_at fills 12 floats per bone and the loop calls hpt_scene_skin
+// (include/hpt.h, "skinning").  Everything else is as with `triangles_at`.
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
     std::function<void(int frame, void *triangles, int count)> triangles_at;      // empty: the geometry stays
     std::function<int(const void *triangles, int count, std::vector<int32_t> &tri_part)> parts_of;
     std::function<void(int frame, float *xforms, int num_parts)> pose_at;         // empty: no poses
+    std::function<int(const void *triangles, int count, std::vector<int32_t> &corner_bone, std::vector<float> &corner_weight)> skin_of;
+    std::function<void(int frame, float *xforms, int num_bones)> skin_at;         // empty: no skins
     bool reproject = false;
     int guide_spp = 4;
     bool guided = false;

@@ -21,6 +21,9 @@
 //                     through their centroid and updates the live scene; --reproject follows them (the motion guide)
 //   --spin-device DEG --spin through hpt_scene_set_parts once and hpt_scene_pose per frame: the OBJ is one rigid part, the host
 //                     hands over twelve floats per frame and copies no record; not together with --spin
+//   --twist-device DEG with --frames and --obj: the OBJ twisted through hpt_scene_set_skin once and hpt_scene_skin per frame: two
+//                     bones, bone 0 at identity and bone 1 --spin-device's turn of f * DEG; a corner of the OBJ follows bone 1 by
+//                     its height in the mesh, so the foot stays put and the top turns; not together with --spin, --spin-device
 //   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
 //                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
 //                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
@@ -64,7 +67,7 @@ int main(int argc, char **argv){
     double until_rms = -1.0;
     std::string rms_log;
     double orbit_deg = 0.0, spin_deg = 0.0;
-    bool spin = false, spin_device = false;
+    bool spin = false, spin_device = false, twist_device = false;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
@@ -96,6 +99,7 @@ int main(int argc, char **argv){
         else if(arg == "--orbit" && i + 1 < argc){ orbit_deg = std::stod(argv[++i]); orbit = true; }
         else if(arg == "--spin" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin = true; }
         else if(arg == "--spin-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin_device = true; }
+        else if(arg == "--twist-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); twist_device = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
         else if(arg == "--temporal-variance") temporal_variance = true;
@@ -133,6 +137,10 @@ int main(int argc, char **argv){
                       << "                    hpt_scene_pose per frame): the same turn as a 3 x 4 matrix rounded to float, twelve floats per\n"
                       << "                    frame and no record copied.  The pose multiplies in float where --spin turns in double and\n"
                       << "                    rounds once, so the images differ from --spin's in the last bits.  Not together with --spin\n"
+                      << "  --twist-device <deg>  with --frames and --obj: the OBJ twisted by a two-bone skin on the device (hpt_scene_set_skin\n"
+                      << "                    once, hpt_scene_skin per frame): bone 1 is --spin-device's turn of f * deg and a corner follows it by\n"
+                      << "                    its height in the mesh, so the foot stays put and the top turns.  Not together with --spin or\n"
+                      << "                    --spin-device\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
                       << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
                       << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n"
@@ -156,6 +164,9 @@ int main(int argc, char **argv){
     }
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
     if(spin && spin_device){ std::cerr << "[Error] --spin and --spin-device exclude each other.\n"; return -1; }
+    if(twist_device && (spin || spin_device)){ std::cerr << "[Error] --twist-device and " << (spin ? "--spin" : "--spin-device") << " exclude each other.\n"; return -1; }
+    if(twist_device && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --twist-device needs --frames and --obj.\n"; return -1; }
+    if(twist_device && !std::isfinite(spin_deg)){ std::cerr << "[Error] --twist-device needs a finite angle.\n"; return -1; }
     if(spin_device && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --spin-device needs --frames and --obj.\n"; return -1; }
     if(spin_device && !std::isfinite(spin_deg)){ std::cerr << "[Error] --spin-device needs a finite angle.\n"; return -1; }
     if(spin && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --spin needs --frames and --obj.\n"; return -1; }
@@ -271,8 +282,49 @@ int main(int argc, char **argv){
                 r[8] = (float) -sn; r[10] = (float) cs; r[11] = (float) (c[2] - (-c[0] * sn + c[2] * cs));
             };
         }
+        if(twist_device){
+            // two bones: bone 0 stays at identity, bone 1 is --spin-device's turn.  A corner of the OBJ at height y follows bone 1
+            // with t = clamp((y - ymin) / (ymax - ymin), 0, 1) and bone 0 with 1 - t, in float; every other corner has four zero
+            // weights and keeps its bits
+            motion.skin_of = [&](const void *triangles, int count, std::vector<int32_t> &corner_bone, std::vector<float> &corner_weight){
+                const CudaTriangle *tr = (const CudaTriangle *) triangles;
+                corner_bone.assign((size_t) count * 12, 0);
+                corner_weight.assign((size_t) count * 12, 0.0f);
+                double c[3] = { 0.0, 0.0, 0.0 }, n = 0.0;
+                float ymin = INFINITY, ymax = -INFINITY;
+                for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                    for(const float3 *v : { &tr[i].v0, &tr[i].v1, &tr[i].v2 }){
+                        c[0] += v->x; c[1] += v->y; c[2] += v->z; n += 1.0;
+                        ymin = std::min(ymin, v->y); ymax = std::max(ymax, v->y);
+                    }
+                }
+                if(n != 0.0) for(int a = 0; a < 3; ++a) spin_centre[a] = c[a] / n;
+                for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                    const float3 *vs[3] = { &tr[i].v0, &tr[i].v1, &tr[i].v2 };
+                    for(int k = 0; k < 3; ++k){
+                        float t = ymax > ymin ? (vs[k]->y - ymin) / (ymax - ymin) : 0.0f;
+                        t = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;                  // (a NaN height: 0, the foot)
+                        const size_t at = ((size_t) i * 3 + (size_t) k) * 4;
+                        corner_bone[at + 1] = 1;
+                        corner_weight[at] = 1.0f - t; corner_weight[at + 1] = t;
+                    }
+                }
+                return 2;
+            };
+            motion.skin_at = [&](int f, float *xforms, int num_bones){
+                static const float identity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+                for(int k = 0; k < num_bones; ++k) memcpy(xforms + 12 * k, identity, sizeof identity);
+                if(num_bones < 2) return;
+                const double *c = spin_centre;
+                const double t = (double) f * spin_deg * 3.14159265358979323846 / 180.0, cs = std::cos(t), sn = std::sin(t);
+                float *r = xforms + 12;
+                r[0] = (float) cs; r[2] = (float) sn; r[3] = (float) (c[0] - (c[0] * cs + c[2] * sn));
+                r[8] = (float) -sn; r[10] = (float) cs; r[11] = (float) (c[2] - (-c[0] * sn + c[2] * cs));
+            };
+        }
         const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
-                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log, orbit || reproject || guided || spin || spin_device ? &motion : nullptr);
+                                               spl, hpt_host::g_ppm_radius, until_rms, rms_log,
+                                               orbit || reproject || guided || spin || spin_device || twist_device ? &motion : nullptr);
         if(n < 0) return -1;
         std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
     }

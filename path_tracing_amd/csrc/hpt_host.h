@@ -176,6 +176,11 @@ struct hpt_scene {
         int num_parts = 0;                           // 0: no parts
         hpt::DevBuf<float> rest_verts, xforms;       // 9 floats per triangle; 12 per part
         hpt::DevBuf<int32_t> tri_part;
+        // skinning (include/hpt.h, "skinning"), allocated by hpt_scene_set_skin: per corner four 16-bit bone indices in one
+        // 8-byte word and four weights.  A scene holds parts or a skin, never both; the two share rest_verts and xforms
+        int num_bones = 0;                           // 0: no skin
+        hpt::DevBuf<uint2> skin_bone;
+        hpt::DevBuf<float4> skin_weight;
         // an update that brought no records (device vertices, a pose) leaves the vertex bytes of geo.h_tris behind `verts`:
         // host_triangles() brings them up to date for the few readers there are
         bool h_tris_stale = false;

@@ -197,6 +197,25 @@ void pose_vertex_host(const float r[12], const float in[3], float out[3]);
 const char *pose_host_records(const void *tris, int nt, const int32_t *tri_part, const float *xforms, int num_parts, void *out,
                               char *msg, size_t msg_cap);
 
+// ---- skinning (include/hpt.h, "skinning"): four (bone, weight) influences per corner blended over a rest pose ----
+
+constexpr int kSkinInfluences = 4;
+constexpr int kMaxBones = 1 << 16;         // a bone index travels as 16 bits on the device
+// The refusals the skin calls share: "" when corner_bone and corner_weight (nt * 3 * 4 entries each) name bones of
+// [0, num_bones), active or not, carry weights that are finite with a clear sign bit, and num_bones lies in [1, kMaxBones];
+// else the message (a literal or `msg`, which names the first triangle and corner at fault).
+const char *check_skin(const int32_t *corner_bone, const float *corner_weight, int nt, int num_bones, char *msg, size_t msg_cap);
+// The definition of a skin: one corner's rest vertex under its four influences and the table xforms (12 floats per bone, the
+// rows of a pose).  An influence is active when its weight's 32 bits are not zero.  keep: every active influence's record has
+// the identity's 48 bytes (or none is active) -- the vertex keeps its bits.  rigid: one active influence of weight 1.0f -- the
+// bytes of pose_vertex_host with that record.  blend: p_j = the rows applied to the vertex, acc = w_j * p_j for the first
+// active influence and acc = acc + w_j * p_j for each later one, in index order.  A result that is not finite makes all
+// three words 0x7FC00000.  `out` may be `in`.  k_skin_verts (refit_kernels.hip) is held to these bytes.
+void skin_vertex_host(const int32_t bone[4], const float weight[4], const float *xforms, const float in[3], float out[3]);
+// records out[i] = tris[i] with its three corners skinned; out may be tris itself
+const char *skin_host_records(const void *tris, int nt, const int32_t *corner_bone, const float *corner_weight, const float *xforms,
+                              int num_bones, void *out, char *msg, size_t msg_cap);
+
 // the builder's lines the device's refit needs on the host between its launches
 float box_padding_of(const float scene_min[3], const float scene_max[3], int nt);                      // pad_abs of a scene box
 void grid_of_box(const float lo[3], const float hi[3], float qorigin[3], float qscale[3]);         // the 16-bit grid over a box

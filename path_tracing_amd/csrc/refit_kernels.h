@@ -45,4 +45,12 @@ constexpr int kPoseMaxBlocks = 2048;      // the grid's cap; a grid-stride loop 
 void launch_pose_verts(hipStream_t s, const float *rest, const int32_t *tri_part, const float *xforms, uint32_t num_parts, uint32_t num_tris,
                        float *verts);
 
+// ---- skinning (include/hpt.h, "skinning") ----
+// One lane per corner (vertex v of the 3 * num_tris): verts[v] = rest[v] under the four influences corner_bone[v] (four
+// 16-bit bone indices in one 8-byte word, influence 0 lowest) and corner_weight[v] over the table xforms (12 floats per bone),
+// to the bytes of skin_vertex_host (scene_build.cpp), which is the definition.  Tables of up to kPoseLdsParts bones are
+// staged in LDS; the grid is capped at kPoseMaxBlocks.  24 bytes of influences per corner, 148 bytes moved per triangle.
+void launch_skin_verts(hipStream_t s, const float *rest, const uint2 *corner_bone, const float4 *corner_weight, const float *xforms,
+                       uint32_t num_bones, uint32_t num_tris, float *verts);
+
 } // namespace hpt

@@ -251,7 +251,68 @@ __global__ __launch_bounds__(kRefitBlock) void k_pose_verts(const float *__restr
     }
 }
 
+// ---- skinning (include/hpt.h, "skinning") ----------------------------------------------------------------------------------
+
+// One lane per corner, the pose kernel's shape: a corner reads its four bones as one 8-byte word and its four weights as one
+// float4, then 12 bytes of the rest pose, and writes 12 bytes: 148 bytes per triangle plus the table.  The cases of the
+// definition (skin_vertex_host, scene_build.cpp), cheapest test first: four zero weights keep the vertex without a look at
+// the table; otherwise the active influences are walked in index order, which yields both the blend and whether every
+// record met was the identity (keep).  The rigid case needs no branch of its own: with one active weight of 1.0f the walk
+// computes 1.0f * p, which has p's bits for every p that is not a NaN, and a NaN leaves as the canonical one either way.
+template <bool kStaged>
+__global__ __launch_bounds__(kRefitBlock) void k_skin_verts(const float *__restrict__ rest, const uint2 *__restrict__ corner_bone,
+                                                             const float4 *__restrict__ corner_weight, const float4 *__restrict__ xforms,
+                                                             uint32_t num_bones, uint64_t num_verts, float *__restrict__ verts){
+    __shared__ float4 table[kStaged ? kPoseLdsParts * 3 : 1];
+    if(kStaged){
+        for(uint32_t i = threadIdx.x; i < num_bones * 3u && i < (uint32_t) kPoseLdsParts * 3u; i += (uint32_t) kRefitBlock) table[i] = xforms[i];
+        __syncthreads();
+    }
+    const uint64_t stride = (uint64_t) gridDim.x * (uint64_t) kRefitBlock;
+    for(uint64_t v = (uint64_t) blockIdx.x * (uint64_t) kRefitBlock + threadIdx.x; v < num_verts; v += stride){
+        const uint2 bw = corner_bone[v];
+        const float4 w4 = corner_weight[v];
+        const float x = rest[v * 3u], y = rest[v * 3u + 1u], z = rest[v * 3u + 2u];
+        const float w[4] = { w4.x, w4.y, w4.z, w4.w };
+        const uint32_t b[4] = { bw.x & 0xFFFFu, bw.x >> 16, bw.y & 0xFFFFu, bw.y >> 16 };
+        float px = x, py = y, pz = z;
+        if((__float_as_uint(w4.x) | __float_as_uint(w4.y) | __float_as_uint(w4.z) | __float_as_uint(w4.w)) != 0u){
+            bool keep = true, first = true;
+            float ax = 0.0f, ay = 0.0f, az = 0.0f;
+#pragma unroll
+            for(int j = 0; j < 4; ++j){
+                if(__float_as_uint(w[j]) == 0u || b[j] >= num_bones) continue;      // inactive: never evaluated (out of the table: refused on the host)
+                const float4 *r = kStaged ? table + (size_t) b[j] * 3 : xforms + (size_t) b[j] * 3;
+                const float4 r0 = r[0], r1 = r[1], r2 = r[2];
+                keep = keep && is_identity(r0, r1, r2);
+                const float mx = w[j] * pose_row(r0.x, r0.y, r0.z, r0.w, x, y, z);
+                const float my = w[j] * pose_row(r1.x, r1.y, r1.z, r1.w, x, y, z);
+                const float mz = w[j] * pose_row(r2.x, r2.y, r2.z, r2.w, x, y, z);
+                ax = first ? mx : ax + mx; ay = first ? my : ay + my; az = first ? mz : az + mz;
+                first = false;
+            }
+            if(!keep){
+                px = ax; py = ay; pz = az;
+                if(!(finite_f(px) && finite_f(py) && finite_f(pz))) px = py = pz = __uint_as_float(0x7FC00000u);
+            }
+        }
+        verts[v * 3u] = px; verts[v * 3u + 1u] = py; verts[v * 3u + 2u] = pz;
+    }
+}
+
 } // namespace
+
+void launch_skin_verts(hipStream_t s, const float *rest, const uint2 *corner_bone, const float4 *corner_weight, const float *xforms,
+                       uint32_t num_bones, uint32_t num_tris, float *verts){
+    if(num_tris == 0) return;
+    const uint64_t num_verts = (uint64_t) num_tris * 3u;
+    const uint64_t blocks = (num_verts + (uint64_t) kRefitBlock - 1u) / (uint64_t) kRefitBlock;
+    const dim3 grid((uint32_t) std::min<uint64_t>(blocks, (uint64_t) kPoseMaxBlocks));
+    if(num_bones <= (uint32_t) kPoseLdsParts)
+        hipLaunchKernelGGL(k_skin_verts<true>, grid, dim3(kRefitBlock), 0, s, rest, corner_bone, corner_weight, (const float4 *) xforms, num_bones, num_verts, verts);
+    else
+        hipLaunchKernelGGL(k_skin_verts<false>, grid, dim3(kRefitBlock), 0, s, rest, corner_bone, corner_weight, (const float4 *) xforms, num_bones, num_verts, verts);
+}
 
 void launch_pose_verts(hipStream_t s, const float *rest, const int32_t *tri_part, const float *xforms, uint32_t num_parts, uint32_t num_tris,
                        float *verts){

@@ -664,6 +664,97 @@ const char *pose_host_records(const void *tris_v, int nt, const int32_t *tri_par
     return "";
 }
 
+const char *check_skin(const int32_t *corner_bone, const float *corner_weight, int nt, int num_bones, char *msg, size_t msg_cap){
+    if(nt < 0) return "negative triangle count";
+    if(num_bones < 1 || num_bones > kMaxBones){ snprintf(msg, msg_cap, "the number of bones must lie in [1, %d]: %d was given", kMaxBones, num_bones); return msg; }
+    if(nt > 0 && (!corner_bone || !corner_weight)) return "null influence array";
+    for(size_t c = 0; c < (size_t) nt * 3; ++c)
+        for(int j = 0; j < kSkinInfluences; ++j){
+            const int32_t b = corner_bone[c * kSkinInfluences + j];
+            if(b < 0 || b >= num_bones){
+                snprintf(msg, msg_cap, "bone %d of triangle %zu corner %zu (influence %d) is not one of the %d bones", b, c / 3, c % 3, j, num_bones);
+                return msg;
+            }
+            uint32_t w; memcpy(&w, corner_weight + c * kSkinInfluences + j, 4);
+            if((w & 0x80000000u) || (w & 0x7F800000u) == 0x7F800000u){
+                snprintf(msg, msg_cap, "weight 0x%08X of triangle %zu corner %zu (influence %d) is negative or not finite", w, c / 3, c % 3, j);
+                return msg;
+            }
+        }
+    return "";
+}
+
+namespace {
+// arith(r, v): the rows of a pose, one operation at a time
+inline void skin_rows(const float *r, float x, float y, float z, float p[3]){
+    for(int a = 0; a < 3; ++a){
+        const float *row = r + 4 * a;
+        p[a] = ((row[0] * x + row[1] * y) + row[2] * z) + row[3];
+    }
+}
+inline void skin_finish(const float p[3], float out[3]){
+    uint32_t w[3]; memcpy(w, p, 12);
+    bool finite = true;
+    for(int a = 0; a < 3; ++a) finite = finite && (w[a] & 0x7F800000u) != 0x7F800000u;
+    if(!finite) w[0] = w[1] = w[2] = 0x7FC00000u;
+    memcpy(out, w, 12);
+}
+}
+
+void skin_vertex_host(const int32_t bone[4], const float weight[4], const float *xforms, const float in[3], float out[3]){
+    static const float kIdentity[12] = { 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f };
+    uint32_t wb[kSkinInfluences]; memcpy(wb, weight, sizeof wb);
+    int active = 0, last = -1;
+    bool all_identity = true;
+    for(int j = 0; j < kSkinInfluences; ++j){
+        if(wb[j] == 0u) continue;                          // inactive: its record is never looked at
+        ++active; last = j;
+        if(memcmp(xforms + (size_t) bone[j] * 12, kIdentity, sizeof kIdentity) != 0) all_identity = false;
+    }
+    if(all_identity){ memmove(out, in, 12); return; }      // keep: the vertex's bits
+    const float x = in[0], y = in[1], z = in[2];
+    float p[3];
+    if(active == 1 && wb[last] == 0x3F800000u){            // rigid: a pose
+        skin_rows(xforms + (size_t) bone[last] * 12, x, y, z, p);
+        skin_finish(p, out);
+        return;
+    }
+    float acc[3] = { 0.0f, 0.0f, 0.0f };
+    bool first = true;
+    for(int j = 0; j < kSkinInfluences; ++j){              // blend, index order
+        if(wb[j] == 0u) continue;
+        skin_rows(xforms + (size_t) bone[j] * 12, x, y, z, p);
+        for(int a = 0; a < 3; ++a){
+            const float m = weight[j] * p[a];
+            acc[a] = first ? m : acc[a] + m;
+        }
+        first = false;
+    }
+    skin_finish(acc, out);
+}
+
+const char *skin_host_records(const void *tris_v, int nt, const int32_t *corner_bone, const float *corner_weight, const float *xforms,
+                              int num_bones, void *out_v, char *msg, size_t msg_cap){
+    const char *err = check_skin(corner_bone, corner_weight, nt, num_bones, msg, msg_cap);
+    if(err && *err) return err;
+    if(!xforms) return "null transform array";
+    if(nt > 0 && (!tris_v || !out_v)) return "null triangle array";
+    const unsigned char *tris = (const unsigned char *) tris_v;
+    unsigned char *out = (unsigned char *) out_v;
+    parallel_chunks((size_t) nt, [&](int, size_t b0, size_t e0){
+        for(size_t i = b0; i < e0; ++i){
+            if(out != tris) memcpy(out + i * sizeof(RefTriangle), tris + i * sizeof(RefTriangle), sizeof(RefTriangle));
+            float v[9]; memcpy(v, out + i * sizeof(RefTriangle), 36);
+            for(int k = 0; k < 3; ++k){
+                const size_t at = (i * 3 + (size_t) k) * kSkinInfluences;
+                skin_vertex_host(corner_bone + at, corner_weight + at, xforms, v + 3 * k, v + 3 * k);
+            }
+            memcpy(out + i * sizeof(RefTriangle), v, 36);
+        }
+    });
+    return "";
+}
+
 const char *check_rounds_update(const void *kept_spheres_v, int kept_ns, int kept_nl, const void *lights_v, int nl, const void *spheres_v, int ns,
                                 char *msg, size_t msg_cap){
     if(nl < 0 || ns < 0) return "negative primitive count";

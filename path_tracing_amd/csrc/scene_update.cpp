@@ -3,7 +3,9 @@
 // the host's share here is the refusals, packing and uploading the vertices, and the few builder lines that sit between
 // the launches (pad_abs and the dead point from the scene box, the grid from node 0).  Poses (include/hpt.h, "poses") are two
 // more feeds into the same refit: vertices that are on the device already, and one 3 x 4 record per part applied to a rest
-// pose by k_pose_verts, to the bytes of pose_vertex_host (scene_build.cpp).  Compiled with hipcc (host code only).
+// pose by k_pose_verts, to the bytes of pose_vertex_host (scene_build.cpp).  A skin (include/hpt.h, "skinning") is a third:
+// four weighted bones per corner blended over the same rest pose by k_skin_verts, to the bytes of skin_vertex_host.
+// Compiled with hipcc (host code only).
 #include "hpt_host.h"
 
 #include <chrono>
@@ -80,10 +82,10 @@ int ensure_previous(hpt_scene *s){
 }
 
 // What an update brings: records from the host (hpt_scene_update_triangles, packed into up.h_verts by the caller), nine floats
-// per triangle on the device, or one record per part applied to the rest pose.  `kind` says which; a scene of zero triangles
-// brings null arrays.
+// per triangle on the device, one record per part applied to the rest pose, or one record per bone blended over it.  `kind`
+// says which; a scene of zero triangles brings null arrays.
 struct Feed {
-    enum Kind { Records, DeviceVerts, Pose } kind;
+    enum Kind { Records, DeviceVerts, Pose, Skin } kind;
     const void *records = nullptr; const float *d_verts = nullptr; const float *xforms = nullptr;
 };
 
@@ -93,7 +95,8 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     hpt_scene::Update &u = s->up;
     hpt_scene::Geometry &g = s->geo;
     const int nt = g.nt;
-    const bool pose = f.kind == Feed::Pose;
+    const bool pose = f.kind == Feed::Pose || f.kind == Feed::Skin;         // applied to the rest pose, which it leaves
+    const int num_records = f.kind == Feed::Skin ? u.num_bones : u.num_parts;
 
     auto t0 = std::chrono::steady_clock::now();
     if(int rc = ensure_scratch(s)) return rc;
@@ -103,15 +106,16 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
         if(nt) HIP_TRY(hipMemcpy(u.verts.get(), f.d_verts, (size_t) nt * 36, hipMemcpyDeviceToDevice));
         HIP_TRY(hipStreamSynchronize(nullptr));
     } else {
-        HIP_TRY(u.xforms.reserve((size_t) u.num_parts * 12));
-        HIP_TRY(hipMemcpy(u.xforms.get(), f.xforms, (size_t) u.num_parts * 48, hipMemcpyHostToDevice));
+        HIP_TRY(u.xforms.reserve((size_t) num_records * 12));
+        HIP_TRY(hipMemcpy(u.xforms.get(), f.xforms, (size_t) num_records * 48, hipMemcpyHostToDevice));
     }
     const double ms_upload = ms_since(t0);
 
     const uint32_t num_nodes = (uint32_t) g.sd.num_nodes;
     float4 *nodes = (float4 *) g.nodes.get();
     HIP_TRY(hipEventRecord(u.ev_a, nullptr));
-    if(pose) launch_pose_verts(nullptr, u.rest_verts.get(), u.tri_part.get(), u.xforms.get(), (uint32_t) u.num_parts, (uint32_t) nt, u.verts.get());
+    if(f.kind == Feed::Pose) launch_pose_verts(nullptr, u.rest_verts.get(), u.tri_part.get(), u.xforms.get(), (uint32_t) u.num_parts, (uint32_t) nt, u.verts.get());
+    if(f.kind == Feed::Skin) launch_skin_verts(nullptr, u.rest_verts.get(), u.skin_bone.get(), u.skin_weight.get(), u.xforms.get(), (uint32_t) u.num_bones, (uint32_t) nt, u.verts.get());
     // leaf records, slot boxes, the live triangles' box and the dead count
     HIP_TRY(hipMemsetAsync(u.result.get(), 0, 8 * sizeof(float), nullptr));
     launch_refit_tris(nullptr, u.verts.get(), (float4 *) g.tris.get(), (uint32_t) nt, (uint32_t) g.sd.num_rounds, u.slot_box.get(), u.partial.get(),
@@ -155,8 +159,8 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     float ms_refit = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms_refit, u.ev_a, u.ev_b));
 
-    // the rest-pose rule: an update that is not a pose leaves the rest pose, and every part at identity
-    if(!pose && u.num_parts && nt){
+    // the rest-pose rule: an update that is not a pose or a skin leaves the rest pose, and every part or bone at identity
+    if(!pose && (u.num_parts || u.num_bones) && nt){
         HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), (size_t) nt * 36, hipMemcpyDeviceToDevice));
         HIP_TRY(hipDeviceSynchronize());
     }
@@ -259,6 +263,7 @@ int hpt_scene_set_parts(hpt_scene *s, const int32_t *tri_part, int nt, int num_p
     hpt_scene::Update &u = s->up;
     const size_t n = (size_t) nt;
     u.num_parts = 0;                                     // (a failed allocation leaves the scene without parts)
+    u.num_bones = 0; u.skin_bone.release(); u.skin_weight.release();      // one deformer per scene: the skin goes
     HIP_TRY(u.rest_verts.reserve(std::max<size_t>(n * 9, 1)));
     HIP_TRY(u.tri_part.reserve(std::max<size_t>(n, 1)));
     if(n){
@@ -283,6 +288,54 @@ int hpt_scene_pose(hpt_scene *s, const float *xforms, int num_parts){
     if(int rc = on_scene_device(s)) return rc;
     Feed f{Feed::Pose}; f.xforms = xforms;
     return refit_from(s, f, 0.0);
+}
+
+int hpt_scene_set_skin(hpt_scene *s, const int32_t *corner_bone, const float *corner_weight, int nt, int num_bones){
+    if(int rc = check_count(s, nt)) return rc;
+    char msg[200];
+    const char *err = check_skin(corner_bone, corner_weight, nt, num_bones, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(int rc = on_scene_device(s)) return rc;
+    if(int rc = ensure_previous(s)) return rc;          // `verts` holds the current geometry from here on
+    hpt_scene::Update &u = s->up;
+    const size_t n = (size_t) nt, corners = n * 3;
+    std::vector<uint16_t> bones(corners * kSkinInfluences);                  // 16 bits per index: check_skin has bounded them
+    for(size_t i = 0; i < bones.size(); ++i) bones[i] = (uint16_t) corner_bone[i];
+    u.num_bones = 0;                                     // (a failed allocation leaves the scene without a skin)
+    u.num_parts = 0; u.tri_part.release();               // one deformer per scene: the parts go
+    HIP_TRY(u.rest_verts.reserve(std::max<size_t>(n * 9, 1)));
+    HIP_TRY(u.skin_bone.reserve(std::max<size_t>(corners, 1)));
+    HIP_TRY(u.skin_weight.reserve(std::max<size_t>(corners, 1)));
+    if(n){
+        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), n * 36, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(u.skin_bone.get(), bones.data(), corners * sizeof(uint2), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(u.skin_weight.get(), corner_weight, corners * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    u.num_bones = num_bones;
+    return HPT_OK;
+}
+
+int hpt_scene_skin(hpt_scene *s, const float *xforms, int num_bones){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(s->up.num_bones == 0) return fail(HPT_ERR_INVALID, "hpt_scene_skin before hpt_scene_set_skin: the scene has no skin");
+    if(num_bones != s->up.num_bones){
+        char msg[200];
+        snprintf(msg, sizeof msg, "a skin keeps the number of bones: the scene has %d bones, %d records were handed over", s->up.num_bones, num_bones);
+        return fail(HPT_ERR_INVALID, msg);
+    }
+    if(!xforms) return fail(HPT_ERR_INVALID, "null transform array");
+    if(int rc = on_scene_device(s)) return rc;
+    Feed f{Feed::Skin}; f.xforms = xforms;
+    return refit_from(s, f, 0.0);
+}
+
+int hpt_skin_host(const void *tris, int nt, const int32_t *corner_bone, const float *corner_weight, const float *xforms, int num_bones,
+                  void *out){
+    char msg[200];
+    const char *err = skin_host_records(tris, nt, corner_bone, corner_weight, xforms, num_bones, out, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    return HPT_OK;
 }
 
 int hpt_scene_read_triangles(hpt_scene *s, void *out, int nt){
