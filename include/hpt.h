@@ -91,7 +91,7 @@ typedef struct hpt_params {
 
 /* Statistics of the LAST render on the scene, whichever integrator it was; every render starts them from zero.
  *   always             ms_total, and the scene constants bvh_nodes, bvh_depth, n_tris, n_materials, ms_bvh_build and
- *                      ms_upload, which never change for the life of the handle
+ *                      ms_upload, which change only with hpt_scene_rebuild
  *   hpt_render_pt*     split_budget, traced_rays_last_pass, long_rays_last_pass; with COUNT_WORK samples, closest_rays,
  *                      shadow_rays, path_iters, boxes_*, tris_*, lane_steps_*, wave_steps_*, leaf_*; with TIME_KERNELS
  *                      ms_extend .. ms_other, ms_resume and the launch counts n_*
@@ -790,7 +790,8 @@ int hpt_trace_visibility(hpt_scene *scene, const float *p1, const float *p2, int
  * `new_triangles` (same count, same non-vertex bytes) and exports as hpt_bvh_export_host does.  Refitting a tree to the
  * vertices it was built from reproduces the builder's bytes.
  *
- * Out of scope: topology changes and automatic rebuilds (a caller whose geometry has moved far destroys and creates);
+ * Out of scope: topology changes and automatic rebuilds (a caller whose geometry has moved far measures the tree with
+ * hpt_scene_tree_cost and calls hpt_scene_rebuild, "tree cost" and "rebuild" below);
  * hpt_multi_* and the scene the one-shot wrappers keep, which compare bytes and rebuild as before.  Vertices handed over
  * as a device pointer and per-part transforms are "poses" below.  (pt_cli turns an OBJ's triangles between frames with
  * --spin, "motion" below, and with --spin-device, "poses".) */
@@ -1019,6 +1020,85 @@ int hpt_history_advance_motion(hpt_history *h, const void *camera, const void *d
 int hpt_history_motion_check(int W, int H, const void *camera, const void *d_frame_rgb,
                              const void *d_normal, const void *d_position, const void *d_coverage,
                              const void *d_prev_position, const hpt_history_params *p, const void *d_mean_out);
+
+/* ---- tree cost ------------------------------------------------------------------------------------------------
+ * What a refit costs is traversal work ("scene updates"), and until now the only way to see it was a slower frame.
+ * These two calls measure the tree itself: the surface-area estimate of a walk of the quantised binary tree, the 32-byte
+ * records of "the acceleration structure, exported" that the first trace launch walks (the four-wide twin's boxes come
+ * from the same float boxes; its own cost is out of scope).  hpt_scene_tree_cost reduces the tree where it lies, on the
+ * device (one streaming kernel over num_nodes * 32 bytes, 96 bytes read back); hpt_bvh_cost_host is the definition, on
+ * the host alone, over an exported tree.  The device's struct equals the host's byte for byte.
+ *
+ * For node i and child c (0 left, 1 right): code = c ? right : left; per axis a the child's planes lo and hi as unsigned
+ * integers and d_a = hi >= lo ? hi - lo : 0.
+ *   code == 0xFFFFFFFF      empty_children += 1, nothing else
+ *   bit 31 set (a leaf)     k = (code & 7) + 1;  leaf_children += 1, leaf_slots += k,
+ *                           leaf_xy += k*d_x*d_y, leaf_yz += k*d_y*d_z, leaf_zx += k*d_z*d_x
+ *                           (a dead triangle in a leaf counts: it is tested)
+ *   otherwise (inner)       inner_children += 1, inner_xy += d_x*d_y, inner_yz += d_y*d_z, inner_zx += d_z*d_x
+ * root_extent[a]: the greatest hi minus the least lo over node 0's non-empty children when hi >= lo, else 0; 0 when both
+ * children are empty.  num_nodes is the tree's.  A term is below 2^35 (8 * 65535^2) and a tree has fewer than 2^24 nodes
+ * (asserted by both calls), so no sum reaches 2^60: every integer is exact, whatever the order of the adds.
+ *
+ * The doubles, IEEE double, evaluated as written, left to right, by one function both calls share:
+ *   Axy = (double) qscale[0] * (double) qscale[1], Ayz and Azx likewise (y z, z x)
+ *   root_area = rx*ry*Axy + ry*rz*Ayz + rz*rx*Azx           the extents converted to double first
+ *   root_area > 0.0 false:  box_visits = tri_tests = sah = 0  (an empty scene, a point, a grid that is not finite)
+ *   box_visits = 1.0 + (inner_xy*Axy + inner_yz*Ayz + inner_zx*Azx) / root_area
+ *   tri_tests  = (leaf_xy*Axy + leaf_yz*Ayz + leaf_zx*Azx) / root_area
+ *   sah        = 2.0 * box_visits + tri_tests
+ * For a random line through the root's box, box_visits is the expected number of inner nodes visited (two slab tests
+ * each) and tri_tests the expected number of triangle tests.  The unit costs 2 and 1 are a convention, not a
+ * measurement: compare a tree with itself over time; the integer sums are there for any other weights.
+ *
+ * hpt_scene_tree_cost is blocking and runs on the null stream, like the updates.  Both calls return HPT_ERR_INVALID with a
+ * message, before the device is touched, for: a null scene or out; a current device other than the scene's; for the host
+ * call a null info or qnodes, qnodes_bytes below num_nodes * 32, or num_nodes < 1. */
+typedef struct hpt_tree_cost {
+    uint64_t inner_children, leaf_children, empty_children, leaf_slots;
+    uint64_t inner_xy, inner_yz, inner_zx, leaf_xy, leaf_yz, leaf_zx;
+    uint32_t root_extent[3], num_nodes;
+    double box_visits, tri_tests, sah;
+} hpt_tree_cost;
+int hpt_scene_tree_cost(hpt_scene *scene, hpt_tree_cost *out);
+int hpt_bvh_cost_host(const hpt_bvh_info *info, const void *qnodes, size_t qnodes_bytes, hpt_tree_cost *out);
+
+/* ---- rebuild -----------------------------------------------------------------------------------------------------
+ * hpt_scene_rebuild gives a live handle a new tree in place.  Afterwards the handle holds the tree that
+ * hpt_bvh_export_host(lights, spheres, T) gives, byte for byte, where the lights and spheres are the handle's current
+ * records and T is what hpt_scene_read_triangles returns at that moment.  It is blocking and runs on the null stream,
+ * like every update: the host records are brought up to date (the lazy download of hpt_scene_read_triangles), the host
+ * builder of hpt_scene_create runs on them, and the four tree arrays and the per-triangle frames go into fresh device
+ * buffers that replace the old ones only when all of that has succeeded.  A failed allocation (HPT_ERR_NOMEM) leaves the
+ * handle exactly as it was; the peak is two trees on the device.  The material table the builder interns equals the
+ * handle's (the non-vertex bytes never change); should it ever not, the call returns HPT_ERR_DEVICE with a message and the
+ * handle is as it was.  Materials, spheres and lights are not uploaded again.
+ *
+ * A rebuild is not an update.  Everything in the handle other than the tree is indexed by input triangle, and stays: the
+ * current and the previous geometry and hpt_scene_has_motion, hpt_update_info, the rest pose with the part map or skin
+ * and the last table, the groups and the bidirectional scene (which has trees of its own), the photon-mapping bounds and
+ * every hpt_sppm state, the workspaces.  Every integrator renders the same bytes after the rebuild as before: the image
+ * does not depend on the tree, only the work does.  A later update, pose or skin refits the new topology: the exported
+ * tree then equals hpt_bvh_refit_host(T, new records) with T the records at the time of the rebuild.  hpt_stats.bvh_nodes,
+ * bvh_depth and ms_bvh_build become the new tree's.
+ *
+ * hpt_scene_get_rebuild_info describes the last rebuild (zeros before the first): how many have been made, the node count
+ * and depth before and after, and the milliseconds of bringing the host records up to date, of the host builder, and of
+ * the upload with the triangle frames.
+ *
+ * hpt_scene_rebuild returns HPT_ERR_INVALID with a message, before the device is touched, for a null scene or a current
+ * device other than the scene's.  A scene of zero triangles accepts the call and counts it.
+ *
+ * Out of scope: a rebuild on the device; a rebuild off the calling thread; a partial rebuild (re-splitting subtrees); any
+ * automatic policy inside the library (pt_cli --rebuild-above R is a caller's: it rebuilds when sah exceeds R times the
+ * cost measured after the last build); hpt_multi_* and the scene the one-shot wrappers keep; the four-wide tree's cost. */
+typedef struct hpt_rebuild_info {
+    uint64_t rebuilds;
+    uint32_t nodes_before, nodes_after, depth_before, depth_after;
+    double ms_download, ms_build, ms_upload;
+} hpt_rebuild_info;
+int hpt_scene_rebuild(hpt_scene *scene);
+int hpt_scene_get_rebuild_info(const hpt_scene *scene, hpt_rebuild_info *out);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,27 @@ class UpdateInfo(C.Structure):
                 ("ms_pack", C.c_double), ("ms_upload", C.c_double), ("ms_refit", C.c_double)]
 
 
+class TreeCost(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("inner_children", "leaf_children", "empty_children", "leaf_slots", "inner_xy", "inner_yz",
+                                          "inner_zx", "leaf_xy", "leaf_yz", "leaf_zx")] + \
+               [("root_extent", C.c_uint32 * 3), ("num_nodes", C.c_uint32),
+                ("box_visits", C.c_double), ("tri_tests", C.c_double), ("sah", C.c_double)]
+
+
+class RebuildInfo(C.Structure):
+    _fields_ = [("rebuilds", C.c_uint64), ("nodes_before", C.c_uint32), ("nodes_after", C.c_uint32),
+                ("depth_before", C.c_uint32), ("depth_after", C.c_uint32),
+                ("ms_download", C.c_double), ("ms_build", C.c_double), ("ms_upload", C.c_double)]
+
+
+def _tree_cost_dict(c: TreeCost) -> dict:
+    """The fields of hpt_tree_cost (root_extent as a tuple) and, under "bytes", the struct's 120 bytes."""
+    d = {n: getattr(c, n) for n, _ in c._fields_ if n != "root_extent"}
+    d["root_extent"] = tuple(c.root_extent)
+    d["bytes"] = bytes(c)
+    return d
+
+
 # exported tree (include/hpt.h, hpt_bvh_info): 32-B quantised nodes as 8 uint32 words, 48-B triangles as 12 words
 QNODE_WORDS = 8
 TRI_WORDS = 12
@@ -183,7 +204,8 @@ def load_library() -> C.CDLL:
                      "hpt_bvh_refit_host", "hpt_scene_keep_previous", "hpt_scene_has_motion", "hpt_render_guides_motion",
                      "hpt_render_guides_motion_device", "hpt_history_advance_motion", "hpt_history_motion_check",
                      "hpt_scene_update_vertices_device", "hpt_scene_set_parts", "hpt_scene_pose", "hpt_scene_read_triangles",
-                     "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host"):
+                     "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host",
+                     "hpt_scene_tree_cost", "hpt_bvh_cost_host", "hpt_scene_rebuild", "hpt_scene_get_rebuild_info"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -462,6 +484,26 @@ class Scene:
         """The last triangle update of any kind (update_triangles, update_vertices_device, pose, skin): dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
         info = UpdateInfo()
         _check(self._lib.hpt_scene_get_update_info(self._h, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in info._fields_}
+
+    # -- tree cost and rebuild (include/hpt.h) ------------------------------------------------
+    def tree_cost(self) -> dict:
+        """The cost of the tree the device holds, reduced on the device (include/hpt.h, "tree cost"): the fields of
+        hpt_tree_cost and the struct's bytes, which equal tree_cost_host(export_bvh())'s.  Blocking."""
+        c = TreeCost()
+        _check(self._lib.hpt_scene_tree_cost(self._h, C.byref(c)))
+        return _tree_cost_dict(c)
+
+    def rebuild(self):
+        """A new tree in place, built by the host builder from the records the handle holds now (include/hpt.h, "rebuild"):
+        afterwards export_bvh() equals export_bvh_host(lights, spheres, read_triangles()).  Everything else the handle
+        keeps stays.  Blocking."""
+        _check(self._lib.hpt_scene_rebuild(self._h))
+
+    def rebuild_info(self) -> dict:
+        """The last rebuild: dict(rebuilds, nodes_before, nodes_after, depth_before, depth_after, ms_download, ms_build, ms_upload)."""
+        info = RebuildInfo()
+        _check(self._lib.hpt_scene_get_rebuild_info(self._h, C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_}
 
     # -- ray probes (tests) ---------------------------------------------------------------
@@ -904,6 +946,19 @@ def export_bvh_host(lights, spheres, triangles) -> dict:
     triangles = np.ascontiguousarray(triangles, TRIANGLE)
     return _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_export_host(
         _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), len(triangles), info, qn, qcap, tr, tcap))
+
+
+def tree_cost_host(bvh) -> dict:
+    """hpt_bvh_cost_host, the definition of Scene.tree_cost on the host (no device needed), over a tree as export_bvh_host,
+    refit_bvh_host or Scene.export_bvh return it."""
+    info = BvhInfo(int(bvh["num_nodes"]), int(bvh["num_tris"]), int(bvh["bvh_depth"]), int(bvh["num_rounds"]))
+    for a in range(3):
+        info.qorigin[a] = bvh["qorigin"][a]
+        info.qscale[a] = bvh["qscale"][a]
+    qn = np.ascontiguousarray(bvh["qnodes"], np.uint32)
+    c = TreeCost()
+    _check(load_library().hpt_bvh_cost_host(C.byref(info), _vp(qn), C.c_size_t(qn.nbytes), C.byref(c)))
+    return _tree_cost_dict(c)
 
 
 def refit_bvh_host(lights, spheres, triangles, new_triangles) -> dict:

@@ -67,6 +67,15 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     if(skinned && (motion->triangles_at || posed || !motion->skin_of)){ std::cerr << "[Error] a skin needs an influence table, and excludes poses and edited records" << std::endl; return -1; }
     const bool spin = motion && (motion->triangles_at || posed || skinned);
     if(spin && (!run.triangles || run.num_triangles < 1)){ std::cerr << "[Error] --spin: the scene has no triangles" << std::endl; return -1; }
+    const bool rebuilds = motion && motion->rebuild_above != 0.0;                      // --rebuild-above
+    if(rebuilds && !(motion->rebuild_above > 1.0)){ std::cerr << "[Error] --rebuild-above needs a ratio above 1" << std::endl; return -1; }
+    if(rebuilds && !spin){ std::cerr << "[Error] --rebuild-above needs --spin, --spin-device or --twist-device" << std::endl; return -1; }
+    double sah_base = 0.0;
+    if(rebuilds){
+        hpt_tree_cost c;
+        if(hpt_scene_tree_cost(run.scene, &c) != HPT_OK) return hpt_failed("hpt_scene_tree_cost");
+        sah_base = c.sah;
+    }
     std::vector<unsigned char> spun;                                                   // this frame's triangle records
     std::vector<float> xforms;                                                         // this frame's pose, 12 floats per part
     if(posed){       // once: the part map, and the rest pose the scene captures with it
@@ -141,6 +150,20 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
                 spun.assign((const unsigned char *) run.triangles, (const unsigned char *) run.triangles + (size_t) run.num_triangles * HPT_TRIANGLE_BYTES);
                 motion->triangles_at(f, spun.data(), run.num_triangles);
                 if(hpt_scene_update_triangles(run.scene, spun.data(), run.num_triangles) != HPT_OK) return hpt_failed("hpt_scene_update_triangles");
+            }
+            if(rebuilds){    // the caller's policy: the refitted tree against the last built one
+                hpt_tree_cost before, after;
+                if(hpt_scene_tree_cost(run.scene, &before) != HPT_OK) return hpt_failed("hpt_scene_tree_cost");
+                if(before.sah > motion->rebuild_above * sah_base){
+                    hpt_rebuild_info ri;
+                    if(hpt_scene_rebuild(run.scene) != HPT_OK) return hpt_failed("hpt_scene_rebuild");
+                    if(hpt_scene_tree_cost(run.scene, &after) != HPT_OK) return hpt_failed("hpt_scene_tree_cost");
+                    if(hpt_scene_get_rebuild_info(run.scene, &ri) != HPT_OK) return hpt_failed("hpt_scene_get_rebuild_info");
+                    char line[160];
+                    snprintf(line, sizeof line, "[Rebuild] frame %d sah %.4f -> %.4f %.3f ms", f, before.sah, after.sah, ri.ms_download + ri.ms_build + ri.ms_upload);
+                    std::cout << line << std::endl;
+                    sah_base = after.sah;
+                }
             }
         }
         const bool follow = spin && reproject;          // the motion guide every frame

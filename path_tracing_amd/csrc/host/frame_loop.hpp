@@ -62,6 +62,12 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // skin_of fills four bones and four weights per corner from the moved scene's records and returns the number of bones, which
 // goes to hpt_scene_set_skin once; before frame f > 0 skin_at fills 12 floats per bone and the loop calls hpt_scene_skin
 // (include/hpt.h, "skinning").  Everything else is as with `triangles_at`.
+//
+// With `rebuild_above` = R > 1 (--rebuild-above; needs moving geometry) the loop is the caller's policy of include/hpt.h,
+// "rebuild": the tree's sah is measured once after creation (the baseline) and after each frame's update; when it exceeds
+// R times the baseline the loop calls hpt_scene_rebuild, prints "[Rebuild] frame <f> sah <before> -> <after> <ms> ms" and takes
+// the new sah as the baseline.  The rebuild sits between the update and the motion guides; the previous geometry is untouched,
+// so a history keeps following across it.  The image does not depend on it.
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
     std::function<void(int frame, void *triangles, int count)> triangles_at;      // empty: the geometry stays
@@ -73,6 +79,7 @@ struct FrameMotion {
     int guide_spp = 4;
     bool guided = false;
     bool temporal_variance = false;
+    double rebuild_above = 0.0;           // 0: never
 };
 int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                    int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,

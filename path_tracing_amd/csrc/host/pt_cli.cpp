@@ -24,6 +24,9 @@
 //   --twist-device DEG with --frames and --obj: the OBJ twisted through hpt_scene_set_skin once and hpt_scene_skin per frame: two
 //                     bones, bone 0 at identity and bone 1 --spin-device's turn of f * DEG; a corner of the OBJ follows bone 1 by
 //                     its height in the mesh, so the foot stays put and the top turns; not together with --spin, --spin-device
+//   --rebuild-above R with --frames and --spin, --spin-device or --twist-device: measure the tree's cost (hpt_scene_tree_cost) after
+//                     each frame's update and rebuild the tree in place (hpt_scene_rebuild) when its sah exceeds R times the
+//                     cost of the last built tree; one "[Rebuild]" line per rebuild.  R must be above 1.  Same image.
 //   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
 //                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
 //                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
@@ -69,6 +72,7 @@ int main(int argc, char **argv){
     double orbit_deg = 0.0, spin_deg = 0.0;
     bool spin = false, spin_device = false, twist_device = false;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
+    bool rebuild = false; double rebuild_above = 0.0;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -100,6 +104,7 @@ int main(int argc, char **argv){
         else if(arg == "--spin" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin = true; }
         else if(arg == "--spin-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin_device = true; }
         else if(arg == "--twist-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); twist_device = true; }
+        else if(arg == "--rebuild-above" && i + 1 < argc){ rebuild_above = std::stod(argv[++i]); rebuild = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
         else if(arg == "--temporal-variance") temporal_variance = true;
@@ -141,6 +146,8 @@ int main(int argc, char **argv){
                       << "                    once, hpt_scene_skin per frame): bone 1 is --spin-device's turn of f * deg and a corner follows it by\n"
                       << "                    its height in the mesh, so the foot stays put and the top turns.  Not together with --spin or\n"
                       << "                    --spin-device\n"
+                      << "  --rebuild-above <R>  with --frames and --spin, --spin-device or --twist-device: rebuild the tree in place when its\n"
+                      << "                    cost (sah of hpt_scene_tree_cost) exceeds R times the last built tree's; R > 1\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
                       << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
                       << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n"
@@ -163,6 +170,10 @@ int main(int argc, char **argv){
         std::cerr << "[Error] --temporal-variance needs --frames N (N >= 1), --reproject and --guided.\n"; return -1;
     }
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
+    if(rebuild && !(rebuild_above > 1.0 && std::isfinite(rebuild_above))){ std::cerr << "[Error] --rebuild-above needs a finite ratio above 1.\n"; return -1; }
+    if(rebuild && (frames < 1 || !(spin || spin_device || twist_device))){
+        std::cerr << "[Error] --rebuild-above needs --frames and one of --spin, --spin-device, --twist-device.\n"; return -1;
+    }
     if(spin && spin_device){ std::cerr << "[Error] --spin and --spin-device exclude each other.\n"; return -1; }
     if(twist_device && (spin || spin_device)){ std::cerr << "[Error] --twist-device and " << (spin ? "--spin" : "--spin-device") << " exclude each other.\n"; return -1; }
     if(twist_device && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --twist-device needs --frames and --obj.\n"; return -1; }
@@ -219,6 +230,7 @@ int main(int argc, char **argv){
     if(progressive){
         hpt_host::FrameMotion motion;
         motion.reproject = reproject; motion.guide_spp = guide_spp; motion.guided = guided; motion.temporal_variance = temporal_variance;
+        motion.rebuild_above = rebuild ? rebuild_above : 0.0;
         if(orbit) motion.camera_at = [&](int f, void *camera84){
             // Rodrigues' rotation of eye - look_at about the unit up vector, in double
             const hpt_host::Camera &c = scene.camera;

@@ -1,5 +1,5 @@
 // Host side of libhpt.so, shared by its translation units (hpt_api.cpp, render_pt.cpp, render_bdpt.cpp, render_ppm.cpp,
-// denoise.cpp, hpt_multi.cpp, scene_update.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
+// denoise.cpp, hpt_multi.cpp, scene_update.cpp, scene_rebuild.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
 // Internal and host only; compiled as HIP because it includes the launch interfaces.
 #pragma once
 #include "../../include/hpt.h"
@@ -43,6 +43,7 @@ public:
     T *get() const { return p_; }
     size_t capacity() const { return cap_; }
     void release(){ if(p_) hipFree(p_); p_ = nullptr; cap_ = 0; }
+    void swap(DevBuf &o){ std::swap(p_, o.p_); std::swap(cap_, o.cap_); }
     hipError_t reserve(size_t n){
         if(n <= cap_) return hipSuccess;
         release();
@@ -185,6 +186,13 @@ struct hpt_scene {
         // host_triangles() brings them up to date for the few readers there are
         bool h_tris_stale = false;
     } up;
+
+    // tree cost and rebuild (scene_rebuild.cpp): the cost kernel's result, allocated by the first hpt_scene_tree_cost, and
+    // the description of the last rebuild
+    struct Rebuild {
+        hpt::DevBuf<unsigned long long> cost;        // kCostResultWords
+        hpt_rebuild_info info{};
+    } rb;
 
     // timing and statistics of the last render
     struct Timing {

@@ -222,6 +222,17 @@ void grid_of_box(const float lo[3], const float hi[3], float qorigin[3], float q
 
 } // namespace hpt
 
+// ---- tree cost (include/hpt.h, "tree cost") ----
+struct hpt_tree_cost;
+namespace hpt {
+// The definition's integers: the ten sums, root_extent and num_nodes of `out` over the quantised binary tree q; the doubles
+// are zeroed.  k_tree_cost (cost_kernels.hip) is held to these integers.
+void tree_cost_sums_host(const QBvhNode *q, uint32_t num_nodes, hpt_tree_cost &out);
+// The definition's doubles from the integers of `c` and the grid's scale: IEEE double, evaluated as written, left to right.
+// The one place they are composed, for the host's sums and the device's alike.
+void tree_cost_compose(const float qscale[3], hpt_tree_cost &c);
+} // namespace hpt
+
 struct hpt_scene;
 namespace hpt {
 // uploads a flattened scene to the current HIP device (hpt_api.cpp; struct hpt_scene is in hpt_host.h); the records are kept for the bidirectional path

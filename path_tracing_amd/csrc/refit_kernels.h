@@ -53,4 +53,13 @@ void launch_pose_verts(hipStream_t s, const float *rest, const int32_t *tri_part
 void launch_skin_verts(hipStream_t s, const float *rest, const uint2 *corner_bone, const float4 *corner_weight, const float *xforms,
                        uint32_t num_bones, uint32_t num_tris, float *verts);
 
+// ---- tree cost (include/hpt.h, "tree cost"; cost_kernels.hip) ----
+constexpr int kCostCounters = 10;         // the integer sums of hpt_tree_cost, in its order
+constexpr int kCostResultWords = 12;      // 64-bit words of `result`: the sums, then root_extent[3] as 32-bit words and a pad
+constexpr int kCostMaxBlocks = 256;       // the grid's cap (one workgroup per CU); a grid-stride loop covers the rest
+// One lane per node of the quantised binary tree, both children per lane: result[0 .. 9] grow by the sums (one 64-bit
+// integer atomic per workgroup and counter; zeroed by the caller) and the lane that reads node 0 stores the root's extent
+// behind them, to the integers of tree_cost_sums_host (scene_build.cpp), which is the definition.
+void launch_tree_cost(hipStream_t s, const uint4 *qnodes, uint32_t num_nodes, unsigned long long *result);
+
 } // namespace hpt

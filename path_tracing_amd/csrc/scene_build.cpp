@@ -10,6 +10,7 @@
 // Float expressions here that feed the kernels (light invariants, triangle edges) are
 // evaluated in the order written, without FMA contraction (-ffp-contract=off).
 #include "hpt_scene.h"
+#include "../../include/hpt.h"       // hpt_tree_cost
 
 #include <algorithm>
 #include <chrono>
@@ -1028,6 +1029,49 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
     hs.ms_bvh_build = std::chrono::duration<double, std::milli>(t1 - t0).count();
     if(hs.materials.empty()) hs.materials.push_back(blank_material());
     return "";
+}
+
+// ---- tree cost (include/hpt.h, "tree cost") --------------------------------------------------------------------------------
+
+void tree_cost_sums_host(const QBvhNode *q, uint32_t num_nodes, hpt_tree_cost &out){
+    memset(&out, 0, sizeof out);
+    out.num_nodes = num_nodes;
+    for(uint32_t i = 0; i < num_nodes; ++i){
+        const QBvhNode &n = q[i];
+        uint32_t rlo[3] = { 0xFFFFu, 0xFFFFu, 0xFFFFu }, rhi[3] = { 0u, 0u, 0u };
+        bool any = false;
+        for(int c = 0; c < 2; ++c){
+            const uint32_t code = c ? n.right : n.left;
+            if(code == kEmptyChild){ out.empty_children += 1; continue; }
+            uint64_t d[3];
+            for(int a = 0; a < 3; ++a){
+                const uint32_t lo = n.plane[a][0][c], hi = n.plane[a][1][c];
+                d[a] = hi >= lo ? hi - lo : 0u;
+                rlo[a] = std::min(rlo[a], lo); rhi[a] = std::max(rhi[a], hi);
+            }
+            any = true;
+            if(code & kLeafFlag){
+                const uint64_t k = (code & 7u) + 1u;
+                out.leaf_children += 1; out.leaf_slots += k;
+                out.leaf_xy += k * d[0] * d[1]; out.leaf_yz += k * d[1] * d[2]; out.leaf_zx += k * d[2] * d[0];
+            } else {
+                out.inner_children += 1;
+                out.inner_xy += d[0] * d[1]; out.inner_yz += d[1] * d[2]; out.inner_zx += d[2] * d[0];
+            }
+        }
+        if(i == 0) for(int a = 0; a < 3; ++a) out.root_extent[a] = any && rhi[a] >= rlo[a] ? rhi[a] - rlo[a] : 0u;
+    }
+}
+
+void tree_cost_compose(const float qscale[3], hpt_tree_cost &c){
+    const double Axy = (double) qscale[0] * (double) qscale[1], Ayz = (double) qscale[1] * (double) qscale[2], Azx = (double) qscale[2] * (double) qscale[0];
+    const double rx = (double) c.root_extent[0], ry = (double) c.root_extent[1], rz = (double) c.root_extent[2];
+    const double root_area = rx * ry * Axy + ry * rz * Ayz + rz * rx * Azx;
+    c.box_visits = c.tri_tests = c.sah = 0.0;
+    if(!(root_area > 0.0)) return;
+    c.box_visits = 1.0 + ((double) c.inner_xy * Axy + (double) c.inner_yz * Ayz + (double) c.inner_zx * Azx) / root_area;
+    c.tri_tests = ((double) c.leaf_xy * Axy + (double) c.leaf_yz * Ayz + (double) c.leaf_zx * Azx) / root_area;
+    c.sah = 2.0 * c.box_visits + c.tri_tests;
 }
 
 
