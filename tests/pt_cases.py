@@ -7,7 +7,7 @@ test_gpu_parity.py do not look.  A plain module: no GPU, no tests.
               x = 5000 (a grid cell of the 16-bit planes is then 0.076 wide); raw camera records with exact zeros in every
               ray (d.y == 0 in the plane y = 0 and in the floor's plane, every ray exactly (0, 0, 1)); lenses of 0.3 degrees
               from 200 units away; the two floor triangles alone (a one-node tree); cornell_random_triangles(20000) far
-              from the origin (a tree deeper than the 12 LDS levels of the resume walk); zero-area triangles and nine
+              from the origin (a tree, not a stack, deeper than the 12 LDS levels of the resume walk); zero-area triangles and nine
               identical ones (more than a leaf holds); 64 spheres and 40 light balls
   parameters  input.txt at eye depths 1, 2, 3, 16 and 40 with and without roulette; max_delta 1, 2, 3; a box of mirrors at caps
               8, 64 and 250 (the clamp: 251 and 1000 are rendered too and must give 250's image); images of 1 x 1, 7 x 3,
@@ -188,7 +188,9 @@ def floor_only_case():
 
 
 def deep_far_case():
-    """cornell_random_triangles(20000) under the far transform: a tree deeper than the 12 LDS levels of the resume walk."""
+    """cornell_random_triangles(20000) under the far transform: a tree of 17 levels (four-wide: 9).  The tree is deeper than
+    the 12 LDS levels of the resume walk, the stack is not: the host restatement of the walk (test_walk_cases_cpu.py,
+    condition (c)) finds at most 12 entries, which fills the LDS levels and stores nothing to the global ones."""
     L, sp, tr = transform_scene(*sio.cornell_random_triangles(20000), 64.0, (300.0, -200.0, 500.0))
     return _geo(L, sp, tr, _cornell_cam(32, 24, 64.0, (300.0, -200.0, 500.0)), 32, 24, 3, 2)
 

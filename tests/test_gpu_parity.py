@@ -402,9 +402,11 @@ def hpt_default_budget():
 
 def test_resume_launch_walks_deep_trees_bit_exact(hpt, sio, oracle_mod):
     """The resume launch walks the four-wide twin of the tree, 12 stack levels per lane in LDS and deeper ones in global
-    memory.  On a mesh of 30 000 triangles and on the incoherent random-triangle cloud (binary trees deeper than the 12
-    LDS levels), with the default budget and with a budget of 1 (practically every ray resumes), the image is the
-    oracle's bit for bit."""
+    memory.  On a mesh of 30 000 triangles and on the incoherent random-triangle cloud (binary trees deeper than 12
+    levels: 19 and 17), with the default budget and with a budget of 1 (practically every ray resumes), the image is the
+    oracle's bit for bit.  Deep trees, not deep stacks: a stack entry is a pending subtree, and the host restatement of
+    the walk (test_walk_cases_cpu.py, condition (c)) finds at most 9 and 11 entries of the four-wide stack on these two
+    scenes, inside the 12 LDS levels.  The global levels are covered by test_gpu_deep_stack.py."""
     for L, sp, tr in (sio.cornell_with_sphere(30000), sio.cornell_random_triangles(20000)):
         cam = sio.make_camera(sio.CORNELL_EYE, sio.CORNELL_LOOK, sio.CORNELL_UP, 50.0, 80, 64)
         bvh = hpt.export_bvh_host(L, sp, tr)
