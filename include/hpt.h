@@ -11,6 +11,21 @@
  *   image    W*H*3 float32, row-major, row 0 = top, linear RGB mean radiance
  *            (reference src/pt_cu.cu:30,248)
  *
+ * The fields of a material (base_color, roughness, metallic, eta) and of a light (pos, dir,
+ * illum, cutoff, is_parallel, light_ball.center and light_ball.r) are NOT validated: any bit
+ * pattern is accepted, and the image is what the reference's expressions give on those values,
+ * bit for bit -- NaN, infinities, negative and denormal values and -0.0 included, a zero or
+ * non-finite `dir` (normalize divides by its length all the same), a radius of 0 (the area pdf
+ * 1 / (n * 4 pi r^2) is then infinite and the sample is dropped by the colour guard), and a
+ * light whose light_ball.center differs from its pos (the closest-hit scan uses the ball; the
+ * light-hit shell test and the next-event sample use pos, as the reference does).  The
+ * per-scene tables the library derives from these fields (material class, GGX width, light
+ * area, pdf, cos(cutoff), normalised directions) are the reference's per-hit expressions on the
+ * same operands.  No call fails or faults because of such values: hpt_scene_create,
+ * hpt_scene_update_rounds and every render return HPT_OK for them.  Nothing is rejected either:
+ * a caller who wants ordinary materials checks them itself.  (tests/shade_cases.py is the table
+ * of values this is tested on; DESIGN.md, "Hostile material and light records".)
+ *
  * What each entry point replaces in the reference:
  *
  *   hpt_pt_render_wrapper     pt_render_wrapper, include/pt_cu.cuh:6-13 (defined

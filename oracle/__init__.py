@@ -75,7 +75,9 @@ def pt_render(lights, spheres, tris, camera, W, H, max_depth, spp, *, seed=1, rn
     correctly rounded.  Triangle tests and the scan are untouched, so a conservative tree still gives the scan's image.
     Replaying the reference's kernel as g++ compiles it (tests/golden/ref_pt_kernel.npz) takes rng_mode=1, trig_mode=1,
     glass_shadow_opaque=1 and both ball_draw_reversed and bsdf_draw_reversed: g++ evaluates call arguments right to left.
-    stats["max_delta_run"] is the most free delta bounces one sample took (the reference has no cap; max_delta is ours)."""
+    stats["max_delta_run"] is the most free delta bounces one sample took (the reference has no cap; max_delta is ours);
+    stats["odd_bounce_rays"] counts the bounce rays with a non-finite origin or direction or a denormal direction component
+    (read from the library after the call: the C struct's layout is unchanged)."""
     img = np.zeros((H, W, 3), np.float32)
     o = PtOpts()
     o.seed, o.rng_mode, o.trig_mode, o.sample_offset = int(seed), rng_mode, trig_mode, sample_offset
@@ -106,7 +108,11 @@ def pt_render(lights, spheres, tris, camera, W, H, max_depth, spp, *, seed=1, rn
             W, H, max_depth, spp, C.byref(o), C.byref(st), C.byref(b) if b is not None else None)
     if rc != 0:
         raise RuntimeError("oracle_pt_render failed rc=%d" % rc)
-    return img, st.as_dict()
+    stats = st.as_dict()
+    last_odd = lib().oracle_pt_last_odd_bounce_rays
+    last_odd.restype = C.c_uint64
+    stats["odd_bounce_rays"] = int(last_odd())
+    return img, stats
 
 
 def sincos_2pi(u):

@@ -23,6 +23,7 @@
 //  * uniforms are in [0,1) (cuRAND's are in (0,1]; the stream is unseeded there anyway).
 #include "ref_math.hpp"
 #include <algorithm>
+#include <atomic>
 #include <random>
 #include <vector>
 #include <omp.h>
@@ -290,6 +291,18 @@ bool visible(const Scene &sc, V3 p1, V3 p2, bool glass_opaque, OraclePtStats &st
     return true;
 }
 
+// Bounce rays (every ray after the primary one) with a non-finite origin or direction component, or a denormal direction
+// component, in the last render of this process: what k_trace's reciprocals and slab tests would meet
+// (tests/shade_cases.py records it per case).  Kept out of OraclePtStats, whose layout callers have compiled in; read
+// with oracle_pt_last_odd_bounce_rays() after the render returns (renders that overlap in time share the count).
+static std::atomic<uint64_t> g_odd_bounce_rays{0};
+
+static inline bool odd_ray(V3 o, V3 d){
+    const float c[6] = { o.x, o.y, o.z, d.x, d.y, d.z };
+    for(int k = 0; k < 6; ++k) if(!std::isfinite(c[k]) || (k >= 3 && std::fpclassify(c[k]) == FP_SUBNORMAL)) return true;
+    return false;
+}
+
 // geometric.cuh:407-413
 V3 random_in_unit_sphere(Rng &rng, bool reversed){
     V3 p;
@@ -420,6 +433,7 @@ V3 trace_sample(const Scene &sc, const RCamera &cam, int px, int py, int max_dep
             else ray_o = hit.pos + hit.normal * kEps;
             last_is_delta = true;
             if(!is_valid_color(throughput)) break;
+            if(odd_ray(ray_o, ray_d)) g_odd_bounce_rays.fetch_add(1, std::memory_order_relaxed);
             st.delta_bounces++;
             ++delta_count;
             if((uint64_t) delta_count > st.max_delta_run) st.max_delta_run = (uint64_t) delta_count;
@@ -440,6 +454,7 @@ V3 trace_sample(const Scene &sc, const RCamera &cam, int px, int py, int max_dep
         ray_d = wi;
         ray_o = hit.pos + hit.normal * kEps;
         last_is_delta = false;
+        if(odd_ray(ray_o, ray_d)) g_odd_bounce_rays.fetch_add(1, std::memory_order_relaxed);
     }
     if(!is_valid_color(final_color)) final_color = v3(0, 0, 0);
     return final_color;
@@ -485,6 +500,7 @@ int oracle_pt_render_bvh(const void *lights, int nl, const void *spheres, int ns
     if(ww <= 0 || wh <= 0) return 1;
     std::vector<OraclePtStats> tstats(nthreads);
     for(auto &s : tstats) memset(&s, 0, sizeof s);
+    g_odd_bounce_rays.store(0, std::memory_order_relaxed);
 
 #pragma omp parallel for schedule(dynamic, 16) num_threads(nthreads)
     for(int wi = 0; wi < ww * wh; ++wi){
@@ -518,6 +534,8 @@ int oracle_pt_render_bvh(const void *lights, int nl, const void *spheres, int ns
     }
     return 0;
 }
+
+uint64_t oracle_pt_last_odd_bounce_rays(void){ return g_odd_bounce_rays.load(std::memory_order_relaxed); }
 
 // ---- function-level probes (known-answer style checks of the shared math) --------------
 void oracle_sincos_2pi(const float *u, int n, float *s, float *c){

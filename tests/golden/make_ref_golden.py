@@ -1,5 +1,6 @@
 """Records what the REFERENCE'S OWN CODE computes, as data: tests/golden/ref_functions.npz, ref_rays.npz,
-ref_pt_kernel.npz and ref_cpu_bdpt.npz.
+ref_pt_kernel.npz, ref_cpu_bdpt.npz, and on the hostile material and light records of tests/shade_cases.py
+ref_hostile_functions.npz and ref_hostile_pt.npz.
 
 It drives oracle/_ref/libref_probe.so -- the reference's sources compiled in place for the host against the stand-in
 headers of oracle/shim/ (oracle/Makefile, target `ref`; driver oracle/ref_probe.cpp) -- on the inputs tests/ref_pin_cases.py
@@ -7,7 +8,7 @@ builds, and stores inputs and answers together, so that the tests read nothing b
 tree (build() makes oracle/_ref/ where the tree exists); no text of the reference and nothing compiled from it is
 written here, only numbers its functions returned.
 
-    python tests/golden/make_ref_golden.py                   # rewrite the four fixtures
+    python tests/golden/make_ref_golden.py                   # rewrite the six fixtures
     python tests/golden/make_ref_golden.py --validate-survey # also replay the survey-stage images (about two minutes)
 
 The files are written without time stamps, so a second run gives the same bytes.
@@ -29,8 +30,9 @@ for _p in (_ROOT, _TESTS):
 from path_tracing_amd import scene_io as sio              # noqa: E402
 from oracle import ref_probe as rp                        # noqa: E402
 import ref_pin_cases as rc                                # noqa: E402
+import shade_cases as shc                                 # noqa: E402
 
-FILES = ["ref_functions.npz", "ref_rays.npz", "ref_pt_kernel.npz", "ref_cpu_bdpt.npz"]
+FILES = ["ref_functions.npz", "ref_rays.npz", "ref_pt_kernel.npz", "ref_cpu_bdpt.npz", "ref_hostile_functions.npz", "ref_hostile_pt.npz"]
 MAX_BYTES = 256 * 1024
 
 
@@ -135,9 +137,30 @@ def cpu_bdpt():
     return out
 
 
+def hostile_functions():
+    """shade_cases.hostile_records(): one material field out of range per block."""
+    names, rec = shc.hostile_records()
+    return dict(records=rec, block_names=names.astype("U32"), table=rp.functions(rec))
+
+
+def hostile_pt():
+    """The PT kernel on shade_cases.FIXTURE_PT, stored as pt_kernel() stores its cases."""
+    out = dict(cases=np.array(shc.FIXTURE_PT, "U24"))
+    for case in shc.FIXTURE_PT:
+        L, sp, tr, cam, W, H, depth, spp, kw = shc.CASE_BY_NAME[case].make()
+        sp, tr = with_mtl_old(sp, tr, "opaque")
+        img = rp.pt_render(L, sp, tr, cam, W, H, depth, spp, kw["seed"])
+        out.update({case + "/lights": _raw(L), case + "/spheres": _raw(sp), case + "/tris": _raw(tr), case + "/camera": _raw(np.asarray(cam).reshape(1)),
+                    case + "/params": np.array([W, H, depth, spp, kw["seed"]], np.int64), case + "/image": img})
+        print("hostile pt %-16s mean %.5f lit %4.1f %%" % (case, np.nanmean(img), 100 * (img != 0).any(axis=2).mean()))
+    return out
+
+
 def generate() -> dict:
     """file name -> bytes"""
-    parts = {"ref_functions.npz": functions(), "ref_rays.npz": rays(), "ref_pt_kernel.npz": pt_kernel(), "ref_cpu_bdpt.npz": cpu_bdpt()}
+    parts = {"ref_functions.npz": functions(), "ref_rays.npz": rays(), "ref_pt_kernel.npz": pt_kernel(), "ref_cpu_bdpt.npz": cpu_bdpt(),
+             "ref_hostile_functions.npz": hostile_functions(), "ref_hostile_pt.npz": hostile_pt()}
+    assert list(parts) == FILES
     return {k: npz_bytes(v) for k, v in parts.items()}
 
 
