@@ -956,6 +956,81 @@ int hpt_scene_skin(hpt_scene *scene, const float *xforms, int num_bones);
 int hpt_skin_host(const void *triangles, int num_triangles, const int32_t *corner_bone,
                   const float *corner_weight, const float *xforms, int num_bones, void *triangles_out);
 
+/* ---- morph targets ---------------------------------------------------------------------------------------------
+ * The third deformer, and the one that runs before the other two: morph targets (blend shapes; glTF's `targets` and
+ * `weights`).  A target is a set of per-corner offsets, a frame carries one scalar weight per target, and the result is
+ * rest + sum of w_t * delta_t, computed on the device from a few floats per frame.  It ends in the same refit as every update,
+ * with the guarantees of a pose: a definition the host restates byte for byte, geometry no target names never moving by a bit,
+ * and everything downstream (the previous geometry, the motion guide, every integrator, the lazy host records) untouched.
+ *
+ * Targets are sparse.  Target t owns the entries target_begin[t] .. target_begin[t + 1] - 1; target_begin has num_targets + 1
+ * values.  Entry e moves corner entry_corner[e] by the three floats entry_delta[3e .. 3e + 2]; corners are numbered as in
+ * "skinning": corner 3 * i + k is v_k of input triangle i.  Within one target the corners ascend strictly, so a corner
+ * appears at most once per target and the order of the sum is fixed.  A target may be empty and num_entries may be 0.
+ *
+ * hpt_scene_set_morphs captures the rest pose exactly as hpt_scene_set_parts does, uploads the targets once, is blocking and
+ * runs on the null stream.  The geometry does not change (hpt_scene_has_motion is not set).  It may be called again, which
+ * gives new targets and a new rest pose.  On the device the targets are kept turned round, one run of entries per corner:
+ * 4 bytes per corner (12 per triangle, and 4 more) for the runs' ends and 16 bytes per entry, next to the rest pose's 36
+ * bytes per triangle and 4 bytes per target for the weights; all of it is allocated here, and a scene that never calls it
+ * pays nothing.
+ *
+ * The definition.  IEEE float, evaluated as written, no contraction.  Target t is ACTIVE if its weight is neither +0 nor -0
+ * ((bits << 1) != 0); negative weights are legitimate here, unlike in a skin.  For a corner with the rest vertex (x, y, z):
+ *   keep    no active target has an entry for the corner.  The vertex keeps its bits: a -0 stays -0, a NaN keeps its payload.
+ *           Geometry that no target names, and every corner under all-zero weights, never moves by a bit.
+ *   morph   otherwise, per component, acc starts as the rest value, and each active target that has an entry for the corner,
+ *           in ascending target order, sets acc = acc + w_t * d -- the product is rounded, then the sum.  Then the pose's
+ *           non-finite rule: if any of the three results has all exponent bits set, all three words become 0x7FC00000; the
+ *           triangle is dead and a later morph revives it.
+ * An inactive target is never evaluated: NaN deltas under a zero weight touch nothing.  Weights and deltas are not
+ * validated; any bit pattern is accepted, and the non-finite rule makes the bytes a function of the inputs alone.
+ *
+ * Composition: morph first, then the deformer.  A scene holds at most one deformer (parts or a skin, as before) and,
+ * independently, morphs.  Write R for the rest pose and M for the morphed rest pose.  hpt_scene_morph computes
+ * M = morph(R, weights); the scene's geometry then becomes the deformer's last table applied to M, and without a deformer
+ * M itself.  On a scene with morphs hpt_scene_pose and hpt_scene_skin apply their table to M instead of R; the deformer's
+ * stage is exactly its own definition with M as the rest vertex.  Every call that captures a rest pose leaves all weights
+ * at zero (M = R, the same bits) and the deformer's table at identity: hpt_scene_set_parts, hpt_scene_set_skin,
+ * hpt_scene_set_morphs, and by the rest-pose rule hpt_scene_update_triangles and hpt_scene_update_vertices_device.  Targets,
+ * the part map and the influences are kept across such a capture.  hpt_scene_set_parts and hpt_scene_set_skin still replace
+ * each other and leave the morphs alone.  On a scene without morphs every earlier call behaves and costs exactly as before.
+ * M is a buffer of its own (36 bytes per triangle) only on a scene that has both morphs and a deformer; with morphs alone
+ * the kernel writes the scene's vertices directly.
+ *
+ * hpt_scene_morph takes num_targets weights; num_targets must be the value given to hpt_scene_set_morphs.  It is absolute,
+ * blocking, runs on the null stream and ends in the same refit.  hpt_scene_get_update_info reports it as a pose: ms_pack
+ * is 0, ms_upload the weights' upload, ms_refit the device part, the morph and deformer kernels included.  The host records
+ * go stale and are refreshed lazily.  hpt_scene_rebuild keeps the targets, the weights and M.
+ *
+ * hpt_morph_host is the definition, on the host alone (no device): triangles_out gets the records of `triangles` with every
+ * corner morphed as above; it may be `triangles` itself.  It covers the morph stage only: compose it with hpt_pose_host or
+ * hpt_skin_host for the whole chain.
+ *
+ * Refusals, HPT_ERR_INVALID with a message before anything touches the device: a null scene, or a null array with a
+ * non-zero count; a triangle count that is not the scene's; num_targets outside [1, HPT_MORPH_MAX_TARGETS], or
+ * num_entries < 0; target_begin[0] != 0, a decreasing target_begin, or target_begin[num_targets] != num_entries; a corner
+ * outside [0, 3 * num_triangles), or corners not strictly ascending within a target (the message names the target and the
+ * entry); hpt_scene_morph before hpt_scene_set_morphs, with another num_targets, or with null weights; a current device
+ * other than the scene's.  hpt_morph_host makes those that need no scene.  A scene of zero triangles accepts all three calls
+ * with zero entries.  A refused call leaves the handle as it was.
+ *
+ * Out of scope: removing morphs from a scene; morphed normals (the renderer derives its normals from the triangle); more
+ * than HPT_MORPH_MAX_TARGETS targets; an indexed mesh; a non-blocking or caller-stream variant; hpt_multi_*.
+ *
+ * pt_cli --frames N --obj mesh.obj --morph-device AMP puts two targets on the OBJ's corners: with h the corner's height in
+ * the mesh normalised to [0, 1] and r the OBJ's radius about the vertical axis through its centroid, target 0 pushes the
+ * corner away from that axis by h * r / 4 and target 1 lifts it by the same amount.  The weights at frame f are
+ * AMP * (1 - cos(2 pi f / 32)) / 2 and AMP * sin(2 pi f / 32), computed in double and rounded to float.  It combines with
+ * --spin-device or --twist-device (morph, then the deformer), --reproject and --rebuild-above. */
+#define HPT_MORPH_MAX_TARGETS 4096
+int hpt_scene_set_morphs(hpt_scene *scene, const int32_t *target_begin, const int32_t *entry_corner,
+                         const float *entry_delta, int num_entries, int num_triangles, int num_targets);
+int hpt_scene_morph(hpt_scene *scene, const float *weights, int num_targets);
+int hpt_morph_host(const void *triangles, int num_triangles, const int32_t *target_begin,
+                   const int32_t *entry_corner, const float *entry_delta, int num_entries,
+                   int num_targets, const float *weights, void *triangles_out);
+
 /* ---- motion ---------------------------------------------------------------------------------------------
  * hpt_history keeps a viewer's accumulation when the camera moves, and the scene updates move the geometry in place; this
  * is what joins them.  The scene remembers one previous geometry, a fifth guide image says where each pixel's surface

@@ -204,7 +204,8 @@ def load_library() -> C.CDLL:
                      "hpt_bvh_refit_host", "hpt_scene_keep_previous", "hpt_scene_has_motion", "hpt_render_guides_motion",
                      "hpt_render_guides_motion_device", "hpt_history_advance_motion", "hpt_history_motion_check",
                      "hpt_scene_update_vertices_device", "hpt_scene_set_parts", "hpt_scene_pose", "hpt_scene_read_triangles",
-                     "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host",
+                     "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host", "hpt_scene_set_morphs", "hpt_scene_morph",
+                     "hpt_morph_host",
                      "hpt_scene_tree_cost", "hpt_bvh_cost_host", "hpt_scene_rebuild", "hpt_scene_get_rebuild_info"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
@@ -462,6 +463,20 @@ class Scene:
             raise HptError("hpt error 1: skin: twelve floats per bone")
         _check(self._lib.hpt_scene_skin(self._h, _vp(x), x.size // 12))
 
+    # -- morph targets (include/hpt.h) --------------------------------------------------------
+    def set_morphs(self, target_begin, entry_corner, entry_delta):
+        """Gives the scene sparse morph targets -- target t owns entries target_begin[t] .. target_begin[t + 1] - 1, entry e
+        moves corner entry_corner[e] by entry_delta[e] ([num_entries, 3] float32 or flat) -- and captures the rest pose; parts
+        or a skin, if the scene has them, stay."""
+        tb, ec, ed = _morph_arrays("set_morphs", target_begin, entry_corner, entry_delta)
+        _check(self._lib.hpt_scene_set_morphs(self._h, _vp(tb), _vp(ec), _vp(ed), ec.size, self.num_triangles, tb.size - 1))
+
+    def morph(self, weights):
+        """One absolute morph: one float32 weight per target, summed over the rest pose on the device; the scene's deformer,
+        if it has one, is then applied with its last table, and the tree is refitted.  Blocking."""
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        _check(self._lib.hpt_scene_morph(self._h, _vp(w), w.size))
+
     def read_triangles(self) -> np.ndarray:
         """The records the handle holds now (layouts.TRIANGLE): the scene's non-vertex bytes with the current vertices."""
         out = np.zeros(self.num_triangles, TRIANGLE)
@@ -481,7 +496,7 @@ class Scene:
         return rc == 1
 
     def update_info(self) -> dict:
-        """The last triangle update of any kind (update_triangles, update_vertices_device, pose, skin): dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
+        """The last triangle update of any kind (update_triangles, update_vertices_device, pose, skin, morph): dict(updates, live_tris, dead_tris, ms_pack, ms_upload, ms_refit)."""
         info = UpdateInfo()
         _check(self._lib.hpt_scene_get_update_info(self._h, C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_}
@@ -1011,6 +1026,29 @@ def skin_host(triangles, corner_bone, corner_weight, xforms) -> np.ndarray:
         raise HptError("hpt error 1: skin_host: twelve influences per triangle (%d triangles, %d influences)" % (len(tr), b.size))
     out = np.zeros(len(tr), TRIANGLE)
     _check(load_library().hpt_skin_host(_vp(tr), len(tr), _vp(b), _vp(w), _vp(x), x.size // 12, _vp(out)))
+    return out
+
+
+def _morph_arrays(what, target_begin, entry_corner, entry_delta):
+    tb = np.ascontiguousarray(target_begin, np.int32).reshape(-1)
+    ec = np.ascontiguousarray(entry_corner, np.int32).reshape(-1)
+    ed = np.ascontiguousarray(entry_delta, np.float32).reshape(-1)
+    if tb.size < 1 or ed.size != ec.size * 3:
+        raise HptError("hpt error 1: %s: num_targets + 1 values of target_begin and three floats per entry (%d values, %d corners, %d floats)"
+                       % (what, tb.size, ec.size, ed.size))
+    return tb, ec, ed
+
+
+def morph_host(triangles, target_begin, entry_corner, entry_delta, weights) -> np.ndarray:
+    """hpt_morph_host, the definition of Scene.morph on the host (no device needed): the records with every corner moved by
+    the weighted deltas of the active targets that name it.  The morph stage only: compose with pose_host or skin_host."""
+    tr = np.ascontiguousarray(triangles, TRIANGLE)
+    tb, ec, ed = _morph_arrays("morph_host", target_begin, entry_corner, entry_delta)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.size != tb.size - 1:
+        raise HptError("hpt error 1: morph_host: one weight per target (%d targets, %d weights)" % (tb.size - 1, w.size))
+    out = np.zeros(len(tr), TRIANGLE)
+    _check(load_library().hpt_morph_host(_vp(tr), len(tr), _vp(tb), _vp(ec), _vp(ed), ec.size, tb.size - 1, _vp(w), _vp(out)))
     return out
 
 

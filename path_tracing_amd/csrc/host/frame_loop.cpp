@@ -65,11 +65,13 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     if(posed && (motion->triangles_at || !motion->parts_of)){ std::cerr << "[Error] a pose needs a part map, and excludes edited records" << std::endl; return -1; }
     const bool skinned = motion && motion->skin_at;                                    // --twist-device
     if(skinned && (motion->triangles_at || posed || !motion->skin_of)){ std::cerr << "[Error] a skin needs an influence table, and excludes poses and edited records" << std::endl; return -1; }
-    const bool spin = motion && (motion->triangles_at || posed || skinned);
+    const bool morphed = motion && motion->morph_at;                                   // --morph-device
+    if(morphed && (motion->triangles_at || !motion->morphs_of)){ std::cerr << "[Error] a morph needs its targets, and excludes edited records" << std::endl; return -1; }
+    const bool spin = motion && (motion->triangles_at || posed || skinned || morphed);
     if(spin && (!run.triangles || run.num_triangles < 1)){ std::cerr << "[Error] --spin: the scene has no triangles" << std::endl; return -1; }
     const bool rebuilds = motion && motion->rebuild_above != 0.0;                      // --rebuild-above
     if(rebuilds && !(motion->rebuild_above > 1.0)){ std::cerr << "[Error] --rebuild-above needs a ratio above 1" << std::endl; return -1; }
-    if(rebuilds && !spin){ std::cerr << "[Error] --rebuild-above needs --spin, --spin-device or --twist-device" << std::endl; return -1; }
+    if(rebuilds && !spin){ std::cerr << "[Error] --rebuild-above needs --spin, --spin-device, --twist-device or --morph-device" << std::endl; return -1; }
     double sah_base = 0.0;
     if(rebuilds){
         hpt_tree_cost c;
@@ -92,6 +94,15 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         if(corner_bone.size() != entries || corner_weight.size() != entries){ std::cerr << "[Error] --twist-device: four influences per corner" << std::endl; return -1; }
         if(hpt_scene_set_skin(run.scene, corner_bone.data(), corner_weight.data(), run.num_triangles, num_bones) != HPT_OK) return hpt_failed("hpt_scene_set_skin");
         xforms.resize((size_t) num_bones * 12);
+    }
+    std::vector<float> weights;                                                        // this frame's morph, one float per target
+    if(morphed){     // once: the targets, beside the deformer if there is one; the scene captures the rest pose again
+        std::vector<int32_t> target_begin, entry_corner; std::vector<float> entry_delta;
+        const int num_targets = motion->morphs_of(run.triangles, run.num_triangles, target_begin, entry_corner, entry_delta);
+        if((int) target_begin.size() != num_targets + 1 || entry_delta.size() != entry_corner.size() * 3){ std::cerr << "[Error] --morph-device: malformed targets" << std::endl; return -1; }
+        if(hpt_scene_set_morphs(run.scene, target_begin.data(), entry_corner.data(), entry_delta.data(), (int) entry_corner.size(), run.num_triangles,
+                                num_targets) != HPT_OK) return hpt_failed("hpt_scene_set_morphs");
+        weights.resize((size_t) num_targets);
     }
     Loop L;
     if(!d_frame.alloc(values * sizeof(float)) || !d_mean.alloc(values * sizeof(float)) || !d_rgb8.alloc(values) ||
@@ -140,13 +151,17 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
         const bool updated = spin && f > 0;
         if(updated){     // blocking, on the null stream: the last frame's work on the loop's stream has ended with its metrics
             if(hipError_t e = hipStreamSynchronize(L.stream)) return hip_failed("stream", e);
+            if(morphed){     // one float per target; morph first, then the deformer over the morphed rest pose
+                motion->morph_at(f, weights.data(), (int) weights.size());
+                if(hpt_scene_morph(run.scene, weights.data(), (int) weights.size()) != HPT_OK) return hpt_failed("hpt_scene_morph");
+            }
             if(skinned){     // twelve floats per bone
                 motion->skin_at(f, xforms.data(), (int) (xforms.size() / 12));
                 if(hpt_scene_skin(run.scene, xforms.data(), (int) (xforms.size() / 12)) != HPT_OK) return hpt_failed("hpt_scene_skin");
             } else if(posed){       // twelve floats per part: no record is copied, no vertex is touched on the host
                 motion->pose_at(f, xforms.data(), (int) (xforms.size() / 12));
                 if(hpt_scene_pose(run.scene, xforms.data(), (int) (xforms.size() / 12)) != HPT_OK) return hpt_failed("hpt_scene_pose");
-            } else {
+            } else if(!morphed){
                 spun.assign((const unsigned char *) run.triangles, (const unsigned char *) run.triangles + (size_t) run.num_triangles * HPT_TRIANGLE_BYTES);
                 motion->triangles_at(f, spun.data(), run.num_triangles);
                 if(hpt_scene_update_triangles(run.scene, spun.data(), run.num_triangles) != HPT_OK) return hpt_failed("hpt_scene_update_triangles");

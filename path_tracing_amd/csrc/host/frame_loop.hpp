@@ -68,6 +68,11 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // R times the baseline the loop calls hpt_scene_rebuild, prints "[Rebuild] frame <f> sah <before> -> <after> <ms> ms" and takes
 // the new sah as the baseline.  The rebuild sits between the update and the motion guides; the previous geometry is untouched,
 // so a history keeps following across it.  The image does not depend on it.
+//
+// With `morph_at` (--morph-device; needs `morphs_of`, excludes `triangles_at`, combines with `pose_at` or `skin_at`) the geometry
+// is morphed first: before frame 0 morphs_of fills the sparse targets from the moved scene's records and returns their number,
+// which goes to hpt_scene_set_morphs once; before frame f > 0 morph_at fills one weight per target and the loop calls
+// hpt_scene_morph, then the deformer's call if there is one (include/hpt.h, "morph targets").
 struct FrameMotion {
     std::function<void(int frame, void *camera84)> camera_at;     // fills a CudaCamera (84 bytes); empty: `camera` every frame
     std::function<void(int frame, void *triangles, int count)> triangles_at;      // empty: the geometry stays
@@ -75,6 +80,9 @@ struct FrameMotion {
     std::function<void(int frame, float *xforms, int num_parts)> pose_at;         // empty: no poses
     std::function<int(const void *triangles, int count, std::vector<int32_t> &corner_bone, std::vector<float> &corner_weight)> skin_of;
     std::function<void(int frame, float *xforms, int num_bones)> skin_at;         // empty: no skins
+    std::function<int(const void *triangles, int count, std::vector<int32_t> &target_begin, std::vector<int32_t> &entry_corner,
+                      std::vector<float> &entry_delta)> morphs_of;
+    std::function<void(int frame, float *weights, int num_targets)> morph_at;     // empty: no morphs
     bool reproject = false;
     int guide_spp = 4;
     bool guided = false;

@@ -27,6 +27,10 @@
 //   --rebuild-above R with --frames and --spin, --spin-device or --twist-device: measure the tree's cost (hpt_scene_tree_cost) after
 //                     each frame's update and rebuild the tree in place (hpt_scene_rebuild) when its sah exceeds R times the
 //                     cost of the last built tree; one "[Rebuild]" line per rebuild.  R must be above 1.  Same image.
+//   --morph-device AMP with --frames and --obj: the OBJ morphed through hpt_scene_set_morphs once and hpt_scene_morph per frame: two
+//                     targets on the OBJ's corners, an outward push and a lift that both grow with the corner's height in the mesh,
+//                     under weights that swing with the frame; combines with --spin-device or --twist-device (morph, then the
+//                     deformer); not together with --spin
 //   --reproject       with --frames: keep the accumulated frames across camera moves (hpt_history): frame 0 and every moved
 //                     frame render --guide-spp guide samples, and each pixel carries its mean and sample count over from
 //                     where its surface point was a frame ago; the frame's line ends in "kept <share> %".
@@ -70,7 +74,8 @@ int main(int argc, char **argv){
     double until_rms = -1.0;
     std::string rms_log;
     double orbit_deg = 0.0, spin_deg = 0.0;
-    bool spin = false, spin_device = false, twist_device = false;
+    bool spin = false, spin_device = false, twist_device = false, morph_device = false;
+    double morph_amp = 0.0;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     bool rebuild = false; double rebuild_above = 0.0;
     for(int i = 1; i < argc; ++i){
@@ -105,6 +110,7 @@ int main(int argc, char **argv){
         else if(arg == "--spin-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin_device = true; }
         else if(arg == "--twist-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); twist_device = true; }
         else if(arg == "--rebuild-above" && i + 1 < argc){ rebuild_above = std::stod(argv[++i]); rebuild = true; }
+        else if(arg == "--morph-device" && i + 1 < argc){ morph_amp = std::stod(argv[++i]); morph_device = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
         else if(arg == "--temporal-variance") temporal_variance = true;
@@ -148,6 +154,11 @@ int main(int argc, char **argv){
                       << "                    --spin-device\n"
                       << "  --rebuild-above <R>  with --frames and --spin, --spin-device or --twist-device: rebuild the tree in place when its\n"
                       << "                    cost (sah of hpt_scene_tree_cost) exceeds R times the last built tree's; R > 1\n"
+                      << "  --morph-device <amp>  with --frames and --obj: the OBJ morphed by two targets on the device (hpt_scene_set_morphs once,\n"
+                      << "                    hpt_scene_morph per frame): target 0 pushes a corner away from the vertical axis through the centroid,\n"
+                      << "                    target 1 lifts it, both by the corner's height in the mesh times a quarter of the OBJ's radius; the\n"
+                      << "                    weights at frame f are amp * (1 - cos(2 pi f / 32)) / 2 and amp * sin(2 pi f / 32).  Combines with\n"
+                      << "                    --spin-device or --twist-device (morph, then the deformer).  Not together with --spin\n"
                       << "  --reproject       with --frames: keep the accumulation across camera moves by reprojecting it through\n"
                       << "                    --guide-spp guide samples per moved frame; prints the share of pixels kept\n"
                       << "  --guided          with --frames: present the mean filtered under its per-pixel variance (needs --guide-spp >= 1)\n"
@@ -171,9 +182,12 @@ int main(int argc, char **argv){
     }
     if((orbit || reproject) && frames < 1){ std::cerr << "[Error] --orbit and --reproject need --frames N (N >= 1).\n"; return -1; }
     if(rebuild && !(rebuild_above > 1.0 && std::isfinite(rebuild_above))){ std::cerr << "[Error] --rebuild-above needs a finite ratio above 1.\n"; return -1; }
-    if(rebuild && (frames < 1 || !(spin || spin_device || twist_device))){
-        std::cerr << "[Error] --rebuild-above needs --frames and one of --spin, --spin-device, --twist-device.\n"; return -1;
+    if(rebuild && (frames < 1 || !(spin || spin_device || twist_device || morph_device))){
+        std::cerr << "[Error] --rebuild-above needs --frames and one of --spin, --spin-device, --twist-device, --morph-device.\n"; return -1;
     }
+    if(morph_device && spin){ std::cerr << "[Error] --morph-device and --spin exclude each other.\n"; return -1; }
+    if(morph_device && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --morph-device needs --frames and --obj.\n"; return -1; }
+    if(morph_device && !std::isfinite(morph_amp)){ std::cerr << "[Error] --morph-device needs a finite amplitude.\n"; return -1; }
     if(spin && spin_device){ std::cerr << "[Error] --spin and --spin-device exclude each other.\n"; return -1; }
     if(twist_device && (spin || spin_device)){ std::cerr << "[Error] --twist-device and " << (spin ? "--spin" : "--spin-device") << " exclude each other.\n"; return -1; }
     if(twist_device && (frames < 1 || obj_file.empty())){ std::cerr << "[Error] --twist-device needs --frames and --obj.\n"; return -1; }
@@ -334,9 +348,54 @@ int main(int argc, char **argv){
                 r[8] = (float) -sn; r[10] = (float) cs; r[11] = (float) (c[2] - (-c[0] * sn + c[2] * cs));
             };
         }
+        if(morph_device){
+            // two targets over the OBJ's corners, in corner order.  h = clamp((y - ymin) / (ymax - ymin), 0, 1) is a corner's height
+            // in the mesh and r the largest distance of a corner from the vertical axis through the centroid, in double; target 0
+            // moves the corner away from that axis by h * r / 4, target 1 lifts it by the same amount; rounded to float once
+            motion.morphs_of = [&](const void *triangles, int count, std::vector<int32_t> &target_begin, std::vector<int32_t> &entry_corner,
+                                   std::vector<float> &entry_delta){
+                const CudaTriangle *tr = (const CudaTriangle *) triangles;
+                double c[3] = { 0.0, 0.0, 0.0 }, n = 0.0, ymin = INFINITY, ymax = -INFINITY, radius = 0.0;
+                for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                    for(const float3 *v : { &tr[i].v0, &tr[i].v1, &tr[i].v2 }){
+                        c[0] += v->x; c[1] += v->y; c[2] += v->z; n += 1.0;
+                        ymin = std::min(ymin, (double) v->y); ymax = std::max(ymax, (double) v->y);
+                    }
+                }
+                if(n != 0.0) for(double &x : c) x /= n;
+                for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                    for(const float3 *v : { &tr[i].v0, &tr[i].v1, &tr[i].v2 }) radius = std::max(radius, std::hypot(v->x - c[0], v->z - c[2]));
+                }
+                std::vector<float> lift;
+                entry_corner.clear(); entry_delta.clear();
+                for(int i = 0; i < count; ++i) if(tr[i].id >= first_obj_id){
+                    const float3 *vs[3] = { &tr[i].v0, &tr[i].v1, &tr[i].v2 };
+                    for(int k = 0; k < 3; ++k){
+                        double h = ymax > ymin ? (vs[k]->y - ymin) / (ymax - ymin) : 0.0;
+                        h = h > 0.0 ? (h < 1.0 ? h : 1.0) : 0.0;                      // (a NaN height: 0, the foot)
+                        const double x = vs[k]->x - c[0], z = vs[k]->z - c[2], d = std::hypot(x, z), by = h * radius / 4.0;
+                        entry_corner.push_back(i * 3 + k);
+                        entry_delta.push_back(d > 0.0 ? (float) (x / d * by) : 0.0f);
+                        entry_delta.push_back(0.0f);
+                        entry_delta.push_back(d > 0.0 ? (float) (z / d * by) : 0.0f);
+                        lift.push_back((float) by);
+                    }
+                }
+                const size_t per_target = entry_corner.size();
+                entry_corner.insert(entry_corner.end(), entry_corner.begin(), entry_corner.begin() + (long) per_target);
+                for(float by : lift){ entry_delta.push_back(0.0f); entry_delta.push_back(by); entry_delta.push_back(0.0f); }
+                target_begin = { 0, (int32_t) per_target, (int32_t) (2 * per_target) };
+                return 2;
+            };
+            motion.morph_at = [&](int f, float *weights, int num_targets){
+                const double t = 2.0 * 3.14159265358979323846 * (double) f / 32.0;
+                if(num_targets > 0) weights[0] = (float) (morph_amp * (1.0 - std::cos(t)) / 2.0);
+                if(num_targets > 1) weights[1] = (float) (morph_amp * std::sin(t));
+            };
+        }
         const int n = hpt_host::run_frame_loop(mode, &cam, &frame_results[0].x, presented, LIGHT_DEPTH, max_depth, W, H, frames, frame_spp,
                                                spl, hpt_host::g_ppm_radius, until_rms, rms_log,
-                                               orbit || reproject || guided || spin || spin_device || twist_device ? &motion : nullptr);
+                                               orbit || reproject || guided || spin || spin_device || twist_device || morph_device ? &motion : nullptr);
         if(n < 0) return -1;
         std::cout << "[Render] " << n << " frames of " << frame_spp << " spp";
     }

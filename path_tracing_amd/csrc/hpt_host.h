@@ -182,6 +182,16 @@ struct hpt_scene {
         int num_bones = 0;                           // 0: no skin
         hpt::DevBuf<uint2> skin_bone;
         hpt::DevBuf<float4> skin_weight;
+        // morph targets (include/hpt.h, "morph targets"), allocated by hpt_scene_set_morphs: the targets turned round into one
+        // run of 16-byte entries per corner (transpose_morphs, scene_build.cpp) and the weights of the last morph.  Morphs sit
+        // beside the deformer, not in its place: with both, a morph writes the morphed rest pose into morph_verts and the
+        // deformer reads that instead of rest_verts; with morphs alone the morph writes `verts` and morph_verts stays empty.
+        // deformer_identity: no pose or skin since the rest pose was last captured, so the deformer's table is the identity
+        int num_targets = 0;                         // 0: no morphs
+        hpt::DevBuf<uint32_t> morph_begin;           // 3 * nt + 1
+        hpt::DevBuf<uint4> morph_entries;
+        hpt::DevBuf<float> morph_weights, morph_verts;      // one per target; 9 floats per triangle
+        bool deformer_identity = true;
         // an update that brought no records (device vertices, a pose) leaves the vertex bytes of geo.h_tris behind `verts`:
         // host_triangles() brings them up to date for the few readers there are
         bool h_tris_stale = false;

@@ -216,6 +216,31 @@ void skin_vertex_host(const int32_t bone[4], const float weight[4], const float 
 const char *skin_host_records(const void *tris, int nt, const int32_t *corner_bone, const float *corner_weight, const float *xforms,
                               int num_bones, void *out, char *msg, size_t msg_cap);
 
+// ---- morph targets (include/hpt.h, "morph targets"): weighted per-corner deltas summed over a rest pose ----
+
+constexpr int kMaxMorphTargets = 4096;     // the weights of one morph fit the 16 KB of LDS k_morph_verts stages them in
+// One entry of the table as the device walks it: which target, and its delta for the corner the entry belongs to.
+struct MorphEntry { uint32_t target; float dx, dy, dz; };
+static_assert(sizeof(MorphEntry) == 16, "one 16-byte load per entry");
+// The refusals the morph calls share: "" when num_targets lies in [1, kMaxMorphTargets], target_begin (num_targets + 1 values)
+// starts at 0, never decreases and ends at num_entries, and within every target the corners lie in [0, 3 * nt) and ascend
+// strictly; else the message (a literal or `msg`, which names the target and the entry at fault).
+const char *check_morphs(const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta, int num_entries, int nt,
+                         int num_targets, char *msg, size_t msg_cap);
+// The caller's targets (checked by check_morphs) turned round for a lane per corner: corner c owns entries
+// corner_begin[c] .. corner_begin[c + 1] - 1, in ascending target order, which is the order of the definition's sum.
+void transpose_morphs(const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta, int nt, int num_targets,
+                      std::vector<uint32_t> &corner_begin, std::vector<MorphEntry> &entries);
+// The definition of a morph for one corner, over the corner's own entries: a target is active when its weight is neither +0
+// nor -0.  keep: no entry's target is active -- the vertex keeps its bits.  Otherwise per component acc = the rest value, and
+// acc = acc + w * d for every active entry in order, the product rounded before the sum; a result that is not finite makes
+// all three words 0x7FC00000.  `out` may be `in`.  k_morph_verts (refit_kernels.hip) is held to these bytes.
+void morph_vertex_host(const MorphEntry *entries, size_t count, const float *weights, const float in[3], float out[3]);
+// records out[i] = tris[i] with every corner morphed, from the caller's layout (no transposition: target after target, which
+// gives each corner the same sum in the same order); out may be tris itself
+const char *morph_host_records(const void *tris, int nt, const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta,
+                               int num_entries, int num_targets, const float *weights, void *out, char *msg, size_t msg_cap);
+
 // the builder's lines the device's refit needs on the host between its launches
 float box_padding_of(const float scene_min[3], const float scene_max[3], int nt);                      // pad_abs of a scene box
 void grid_of_box(const float lo[3], const float hi[3], float qorigin[3], float qscale[3]);         // the 16-bit grid over a box

@@ -53,6 +53,17 @@ void launch_pose_verts(hipStream_t s, const float *rest, const int32_t *tri_part
 void launch_skin_verts(hipStream_t s, const float *rest, const uint2 *corner_bone, const float4 *corner_weight, const float *xforms,
                        uint32_t num_bones, uint32_t num_tris, float *verts);
 
+// ---- morph targets (include/hpt.h, "morph targets") ----
+constexpr int kMorphMaxTargets = 4096;    // HPT_MORPH_MAX_TARGETS: one morph's weights are 16 KB of LDS
+// One lane per corner: verts[v] = rest[v] plus the weighted deltas of the corner's entries, entries[corner_begin[v]] ..
+// entries[corner_begin[v + 1] - 1] (16 bytes each: the target's index, then dx, dy, dz as float bits; sorted by corner, then
+// target), to the bytes of morph_vertex_host (scene_build.cpp), which is the definition: an entry whose target has the
+// weight +0 or -0 is skipped, a corner with no active entry keeps its bits, a result that is not finite becomes three
+// canonical NaNs.  corner_begin holds 3 * num_tris + 1 values; the grid is capped at kPoseMaxBlocks.  4 bytes per corner
+// and 16 per entry, next to the 24 bytes of vertices read and written.
+void launch_morph_verts(hipStream_t s, const float *rest, const uint32_t *corner_begin, const uint4 *entries, const float *weights,
+                        uint32_t num_targets, uint32_t num_tris, float *verts);
+
 // ---- tree cost (include/hpt.h, "tree cost"; cost_kernels.hip) ----
 constexpr int kCostCounters = 10;         // the integer sums of hpt_tree_cost, in its order
 constexpr int kCostResultWords = 12;      // 64-bit words of `result`: the sums, then root_extent[3] as 32-bit words and a pad

@@ -300,7 +300,59 @@ __global__ __launch_bounds__(kRefitBlock) void k_skin_verts(const float *__restr
     }
 }
 
+// ---- morph targets (include/hpt.h, "morph targets") -----------------------------------------------------------------------
+
+// one entry of a corner's run: acc = acc + w * d if the entry's target is active; says whether it was
+__device__ __forceinline__ bool morph_step(const uint4 &m, const float *table, uint32_t num_targets, float &px, float &py, float &pz){
+    if(m.x >= num_targets) return false;                    // (refused on the host: never out of the table)
+    const float w = table[m.x];
+    if((__float_as_uint(w) << 1) == 0u) return false;       // inactive: never evaluated
+    const float mx = w * __uint_as_float(m.y), my = w * __uint_as_float(m.z), mz = w * __uint_as_float(m.w);
+    px = px + mx; py = py + my; pz = pz + mz;
+    return true;
+}
+
+// One lane per corner, the skin kernel's shape.  A corner reads the two ends of its run in corner_begin and 12 bytes of the
+// rest pose, then its 16-byte entries {target, dx, dy, dz}, four loads at a time; the entries are sorted by corner, then target, so the walk
+// is the definition's sum in the definition's order (morph_vertex_host, scene_build.cpp) and neighbouring lanes start on
+// neighbouring entries.  The weights, 4 bytes per target, are staged in LDS once per workgroup.  A weight of +0 or -0 skips
+// the entry without a look at its delta; a corner on which nothing was active stores the bits it loaded.  The file is
+// compiled without contraction, so w * d is rounded before it is added.
+__global__ __launch_bounds__(kRefitBlock) void k_morph_verts(const float *__restrict__ rest, const uint32_t *__restrict__ corner_begin,
+                                                              const uint4 *__restrict__ entries, const float *__restrict__ weights,
+                                                              uint32_t num_targets, uint64_t num_verts, float *__restrict__ verts){
+    __shared__ float table[kMorphMaxTargets];
+    for(uint32_t i = threadIdx.x; i < num_targets && i < (uint32_t) kMorphMaxTargets; i += (uint32_t) kRefitBlock) table[i] = weights[i];
+    __syncthreads();
+    const uint64_t stride = (uint64_t) gridDim.x * (uint64_t) kRefitBlock;
+    for(uint64_t v = (uint64_t) blockIdx.x * (uint64_t) kRefitBlock + threadIdx.x; v < num_verts; v += stride){
+        const uint32_t e0 = corner_begin[v], e1 = corner_begin[v + 1u];
+        float px = rest[v * 3u], py = rest[v * 3u + 1u], pz = rest[v * 3u + 2u];
+        bool any = false;
+        uint32_t e = e0;
+        for(; e + 4u <= e1; e += 4u){                       // four loads in flight, then the four steps in order
+            const uint4 m0 = entries[e], m1 = entries[e + 1u], m2 = entries[e + 2u], m3 = entries[e + 3u];
+            any |= morph_step(m0, table, num_targets, px, py, pz);
+            any |= morph_step(m1, table, num_targets, px, py, pz);
+            any |= morph_step(m2, table, num_targets, px, py, pz);
+            any |= morph_step(m3, table, num_targets, px, py, pz);
+        }
+        for(; e < e1; ++e) any |= morph_step(entries[e], table, num_targets, px, py, pz);
+        if(any && !(finite_f(px) && finite_f(py) && finite_f(pz))) px = py = pz = __uint_as_float(0x7FC00000u);
+        verts[v * 3u] = px; verts[v * 3u + 1u] = py; verts[v * 3u + 2u] = pz;
+    }
+}
+
 } // namespace
+
+void launch_morph_verts(hipStream_t s, const float *rest, const uint32_t *corner_begin, const uint4 *entries, const float *weights,
+                        uint32_t num_targets, uint32_t num_tris, float *verts){
+    if(num_tris == 0) return;
+    const uint64_t num_verts = (uint64_t) num_tris * 3u;
+    const uint64_t blocks = (num_verts + (uint64_t) kRefitBlock - 1u) / (uint64_t) kRefitBlock;
+    const dim3 grid((uint32_t) std::min<uint64_t>(blocks, (uint64_t) kPoseMaxBlocks));
+    hipLaunchKernelGGL(k_morph_verts, grid, dim3(kRefitBlock), 0, s, rest, corner_begin, entries, weights, num_targets, num_verts, verts);
+}
 
 void launch_skin_verts(hipStream_t s, const float *rest, const uint2 *corner_bone, const float4 *corner_weight, const float *xforms,
                        uint32_t num_bones, uint32_t num_tris, float *verts){

@@ -756,6 +756,120 @@ const char *skin_host_records(const void *tris_v, int nt, const int32_t *corner_
     return "";
 }
 
+const char *check_morphs(const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta, int num_entries, int nt,
+                         int num_targets, char *msg, size_t msg_cap){
+    if(nt < 0) return "negative triangle count";
+    if(num_targets < 1 || num_targets > kMaxMorphTargets){
+        snprintf(msg, msg_cap, "the number of morph targets must lie in [1, %d]: %d was given", kMaxMorphTargets, num_targets);
+        return msg;
+    }
+    if(num_entries < 0) return "negative morph entry count";
+    if(!target_begin) return "null target_begin array";
+    if(num_entries > 0 && (!entry_corner || !entry_delta)) return "null morph entry array";
+    if(target_begin[0] != 0){ snprintf(msg, msg_cap, "target_begin[0] must be 0: it is %d", target_begin[0]); return msg; }
+    for(int t = 0; t < num_targets; ++t)
+        if(target_begin[t + 1] < target_begin[t]){
+            snprintf(msg, msg_cap, "target_begin decreases at target %d: %d follows %d", t, target_begin[t + 1], target_begin[t]);
+            return msg;
+        }
+    if(target_begin[num_targets] != num_entries){
+        snprintf(msg, msg_cap, "target_begin[%d] must be the number of entries, %d: it is %d", num_targets, num_entries, target_begin[num_targets]);
+        return msg;
+    }
+    const int64_t corners = (int64_t) nt * 3;
+    for(int t = 0; t < num_targets; ++t)
+        for(int32_t e = target_begin[t]; e < target_begin[t + 1]; ++e){
+            const int32_t c = entry_corner[e];
+            if(c < 0 || (int64_t) c >= corners){
+                snprintf(msg, msg_cap, "corner %d of target %d (entry %d) is not one of the %lld corners", c, t, e, (long long) corners);
+                return msg;
+            }
+            if(e > target_begin[t] && c <= entry_corner[e - 1]){
+                snprintf(msg, msg_cap, "the corners of target %d are not strictly ascending: entry %d names corner %d after corner %d", t, e, c, entry_corner[e - 1]);
+                return msg;
+            }
+        }
+    return "";
+}
+
+void transpose_morphs(const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta, int nt, int num_targets,
+                      std::vector<uint32_t> &corner_begin, std::vector<MorphEntry> &entries){
+    const size_t corners = (size_t) nt * 3, n = (size_t) target_begin[num_targets];
+    corner_begin.assign(corners + 1, 0u);
+    entries.resize(n);
+    for(size_t e = 0; e < n; ++e) corner_begin[(size_t) entry_corner[e] + 1] += 1u;
+    for(size_t c = 0; c < corners; ++c) corner_begin[c + 1] += corner_begin[c];
+    std::vector<uint32_t> next(corner_begin.begin(), corner_begin.end() - 1);
+    for(int t = 0; t < num_targets; ++t)               // ascending targets: a corner's entries come out in target order
+        for(int32_t e = target_begin[t]; e < target_begin[t + 1]; ++e){
+            MorphEntry &m = entries[next[(size_t) entry_corner[e]]++];
+            m.target = (uint32_t) t;
+            memcpy(&m.dx, entry_delta + (size_t) e * 3, 12);
+        }
+}
+
+namespace {
+inline bool morph_active(float w){ uint32_t b; memcpy(&b, &w, 4); return (b << 1) != 0u; }
+}
+
+void morph_vertex_host(const MorphEntry *entries, size_t count, const float *weights, const float in[3], float out[3]){
+    float acc[3]; memcpy(acc, in, 12);
+    bool any = false;
+    for(size_t e = 0; e < count; ++e){
+        const float w = weights[entries[e].target];
+        if(!morph_active(w)) continue;                     // inactive: its deltas are never looked at
+        const float d[3] = { entries[e].dx, entries[e].dy, entries[e].dz };
+        for(int a = 0; a < 3; ++a){
+            const float m = w * d[a];
+            acc[a] = acc[a] + m;
+        }
+        any = true;
+    }
+    if(!any){ memmove(out, in, 12); return; }             // keep: the vertex's bits
+    skin_finish(acc, out);
+}
+
+const char *morph_host_records(const void *tris_v, int nt, const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta,
+                               int num_entries, int num_targets, const float *weights, void *out_v, char *msg, size_t msg_cap){
+    const char *err = check_morphs(target_begin, entry_corner, entry_delta, num_entries, nt, num_targets, msg, msg_cap);
+    if(err && *err) return err;
+    if(!weights) return "null weight array";
+    if(nt > 0 && (!tris_v || !out_v)) return "null triangle array";
+    const unsigned char *tris = (const unsigned char *) tris_v;
+    unsigned char *out = (unsigned char *) out_v;
+    // the definition as the caller's layout has it: target after target, ascending, each over its own ascending corners; a
+    // chunk of triangles finds its run of a target's entries by bisection
+    parallel_chunks((size_t) nt, [&](int, size_t b0, size_t e0){
+        if(out != tris) memcpy(out + b0 * sizeof(RefTriangle), tris + b0 * sizeof(RefTriangle), (e0 - b0) * sizeof(RefTriangle));
+        std::vector<unsigned char> touched((e0 - b0) * 3, 0);
+        const int32_t c0 = (int32_t) (b0 * 3), c1 = (int32_t) (e0 * 3);
+        for(int t = 0; t < num_targets; ++t){
+            const float w = weights[t];
+            if(!morph_active(w)) continue;
+            const int32_t *first = entry_corner + target_begin[t], *last = entry_corner + target_begin[t + 1];
+            for(const int32_t *p = std::lower_bound(first, last, c0); p < last && *p < c1; ++p){
+                const size_t c = (size_t) *p;
+                unsigned char *at = out + (c / 3) * sizeof(RefTriangle) + (c % 3) * 12;
+                const float *d = entry_delta + (size_t) (p - entry_corner) * 3;
+                float acc[3]; memcpy(acc, at, 12);
+                for(int a = 0; a < 3; ++a){
+                    const float m = w * d[a];
+                    acc[a] = acc[a] + m;
+                }
+                memcpy(at, acc, 12);
+                touched[c - (size_t) c0] = 1;
+            }
+        }
+        for(size_t c = 0; c < touched.size(); ++c) if(touched[c]){
+            unsigned char *at = out + (((size_t) c0 + c) / 3) * sizeof(RefTriangle) + (((size_t) c0 + c) % 3) * 12;
+            float acc[3]; memcpy(acc, at, 12);
+            skin_finish(acc, acc);
+            memcpy(at, acc, 12);
+        }
+    });
+    return "";
+}
+
 const char *check_rounds_update(const void *kept_spheres_v, int kept_ns, int kept_nl, const void *lights_v, int nl, const void *spheres_v, int ns,
                                 char *msg, size_t msg_cap){
     if(nl < 0 || ns < 0) return "negative primitive count";

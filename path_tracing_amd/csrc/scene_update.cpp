@@ -4,7 +4,10 @@
 // the launches (pad_abs and the dead point from the scene box, the grid from node 0).  Poses (include/hpt.h, "poses") are two
 // more feeds into the same refit: vertices that are on the device already, and one 3 x 4 record per part applied to a rest
 // pose by k_pose_verts, to the bytes of pose_vertex_host (scene_build.cpp).  A skin (include/hpt.h, "skinning") is a third:
-// four weighted bones per corner blended over the same rest pose by k_skin_verts, to the bytes of skin_vertex_host.
+// four weighted bones per corner blended over the same rest pose by k_skin_verts, to the bytes of skin_vertex_host.  Morph
+// targets (include/hpt.h, "morph targets") are a fourth, and the only one that composes: k_morph_verts sums weighted deltas
+// over the rest pose to the bytes of morph_vertex_host, and where the scene has parts or a skin as well the deformer then
+// runs over that morphed rest pose with the table it was last given.
 // Compiled with hipcc (host code only).
 #include "hpt_host.h"
 
@@ -82,12 +85,25 @@ int ensure_previous(hpt_scene *s){
 }
 
 // What an update brings: records from the host (hpt_scene_update_triangles, packed into up.h_verts by the caller), nine floats
-// per triangle on the device, one record per part applied to the rest pose, or one record per bone blended over it.  `kind`
-// says which; a scene of zero triangles brings null arrays.
+// per triangle on the device, one record per part applied to the rest pose, one record per bone blended over it, or one
+// weight per morph target.  `kind` says which; a scene of zero triangles brings null arrays.
 struct Feed {
-    enum Kind { Records, DeviceVerts, Pose, Skin } kind;
-    const void *records = nullptr; const float *d_verts = nullptr; const float *xforms = nullptr;
+    enum Kind { Records, DeviceVerts, Pose, Skin, Morph } kind;
+    const void *records = nullptr; const float *d_verts = nullptr; const float *xforms = nullptr; const float *weights = nullptr;
 };
+
+// Every call that captures a rest pose ends here: R = the geometry `verts` holds, all morph weights at zero -- so M, which is
+// held only where the scene has morphs and a deformer (`both`), has R's bits -- and the deformer's table at identity.
+int capture_rest(hpt_scene::Update &u, size_t nt, bool both){
+    HIP_TRY(u.rest_verts.reserve(std::max<size_t>(nt * 9, 1)));
+    if(both) HIP_TRY(u.morph_verts.reserve(std::max<size_t>(nt * 9, 1)));
+    if(nt){
+        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), nt * 36, hipMemcpyDeviceToDevice));
+        if(both) HIP_TRY(hipMemcpy(u.morph_verts.get(), u.verts.get(), nt * 36, hipMemcpyDeviceToDevice));
+    }
+    u.deformer_identity = true;
+    return HPT_OK;
+}
 
 // The part every triangle update shares: the feed into `verts`, the refit's launches, and the bookkeeping.  With host records
 // it enqueues what hpt_scene_update_triangles always has.
@@ -95,7 +111,8 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     hpt_scene::Update &u = s->up;
     hpt_scene::Geometry &g = s->geo;
     const int nt = g.nt;
-    const bool pose = f.kind == Feed::Pose || f.kind == Feed::Skin;         // applied to the rest pose, which it leaves
+    const bool pose = f.kind == Feed::Pose || f.kind == Feed::Skin || f.kind == Feed::Morph;      // applied to the rest pose, which it leaves
+    const bool deformer = u.num_parts || u.num_bones;
     const int num_records = f.kind == Feed::Skin ? u.num_bones : u.num_parts;
 
     auto t0 = std::chrono::steady_clock::now();
@@ -105,6 +122,8 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     } else if(f.kind == Feed::DeviceVerts){
         if(nt) HIP_TRY(hipMemcpy(u.verts.get(), f.d_verts, (size_t) nt * 36, hipMemcpyDeviceToDevice));
         HIP_TRY(hipStreamSynchronize(nullptr));
+    } else if(f.kind == Feed::Morph){
+        HIP_TRY(hipMemcpy(u.morph_weights.get(), f.weights, (size_t) u.num_targets * sizeof(float), hipMemcpyHostToDevice));
     } else {
         HIP_TRY(u.xforms.reserve((size_t) num_records * 12));
         HIP_TRY(hipMemcpy(u.xforms.get(), f.xforms, (size_t) num_records * 48, hipMemcpyHostToDevice));
@@ -114,8 +133,19 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     const uint32_t num_nodes = (uint32_t) g.sd.num_nodes;
     float4 *nodes = (float4 *) g.nodes.get();
     HIP_TRY(hipEventRecord(u.ev_a, nullptr));
-    if(f.kind == Feed::Pose) launch_pose_verts(nullptr, u.rest_verts.get(), u.tri_part.get(), u.xforms.get(), (uint32_t) u.num_parts, (uint32_t) nt, u.verts.get());
-    if(f.kind == Feed::Skin) launch_skin_verts(nullptr, u.rest_verts.get(), u.skin_bone.get(), u.skin_weight.get(), u.xforms.get(), (uint32_t) u.num_bones, (uint32_t) nt, u.verts.get());
+    // morph first, then the deformer: with morphs the deformer's rest vertex is M, which a morph has written just before (or
+    // some time ago, or a capture has set to R); a morph on a scene whose deformer was never given a table hands M on as it is
+    const float *rest = u.num_targets && deformer ? u.morph_verts.get() : u.rest_verts.get();
+    bool run_parts = f.kind == Feed::Pose, run_skin = f.kind == Feed::Skin;
+    if(f.kind == Feed::Morph){
+        launch_morph_verts(nullptr, u.rest_verts.get(), u.morph_begin.get(), u.morph_entries.get(), u.morph_weights.get(), (uint32_t) u.num_targets,
+                           (uint32_t) nt, deformer ? u.morph_verts.get() : u.verts.get());
+        if(deformer && u.deformer_identity){
+            if(nt) HIP_TRY(hipMemcpyAsync(u.verts.get(), u.morph_verts.get(), (size_t) nt * 36, hipMemcpyDeviceToDevice, nullptr));
+        } else { run_parts = u.num_parts != 0; run_skin = u.num_bones != 0; }
+    }
+    if(run_parts) launch_pose_verts(nullptr, rest, u.tri_part.get(), u.xforms.get(), (uint32_t) u.num_parts, (uint32_t) nt, u.verts.get());
+    if(run_skin) launch_skin_verts(nullptr, rest, u.skin_bone.get(), u.skin_weight.get(), u.xforms.get(), (uint32_t) u.num_bones, (uint32_t) nt, u.verts.get());
     // leaf records, slot boxes, the live triangles' box and the dead count
     HIP_TRY(hipMemsetAsync(u.result.get(), 0, 8 * sizeof(float), nullptr));
     launch_refit_tris(nullptr, u.verts.get(), (float4 *) g.tris.get(), (uint32_t) nt, (uint32_t) g.sd.num_rounds, u.slot_box.get(), u.partial.get(),
@@ -159,11 +189,13 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     float ms_refit = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms_refit, u.ev_a, u.ev_b));
 
-    // the rest-pose rule: an update that is not a pose or a skin leaves the rest pose, and every part or bone at identity
-    if(!pose && (u.num_parts || u.num_bones) && nt){
-        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), (size_t) nt * 36, hipMemcpyDeviceToDevice));
+    // the rest-pose rule: an update that is not a pose, a skin or a morph leaves the rest pose, every part or bone at identity
+    // and every morph weight at zero
+    if(!pose && (deformer || u.num_targets)){
+        if(int rc = capture_rest(u, (size_t) nt, deformer && u.num_targets)) return rc;
         HIP_TRY(hipDeviceSynchronize());
     }
+    if(f.kind == Feed::Pose || f.kind == Feed::Skin) u.deformer_identity = false;
     if(f.kind == Feed::Records){
         if(nt) g.h_tris.assign((const unsigned char *) f.records, (const unsigned char *) f.records + (size_t) nt * HPT_TRIANGLE_BYTES);
         u.h_tris_stale = false;
@@ -264,10 +296,9 @@ int hpt_scene_set_parts(hpt_scene *s, const int32_t *tri_part, int nt, int num_p
     const size_t n = (size_t) nt;
     u.num_parts = 0;                                     // (a failed allocation leaves the scene without parts)
     u.num_bones = 0; u.skin_bone.release(); u.skin_weight.release();      // one deformer per scene: the skin goes
-    HIP_TRY(u.rest_verts.reserve(std::max<size_t>(n * 9, 1)));
+    if(int rc = capture_rest(u, n, u.num_targets != 0)) return rc;
     HIP_TRY(u.tri_part.reserve(std::max<size_t>(n, 1)));
     if(n){
-        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), n * 36, hipMemcpyDeviceToDevice));
         if(tri_part) HIP_TRY(hipMemcpy(u.tri_part.get(), tri_part, n * sizeof(int32_t), hipMemcpyHostToDevice));
         else HIP_TRY(hipMemset(u.tri_part.get(), 0, n * sizeof(int32_t)));
     }
@@ -303,11 +334,10 @@ int hpt_scene_set_skin(hpt_scene *s, const int32_t *corner_bone, const float *co
     for(size_t i = 0; i < bones.size(); ++i) bones[i] = (uint16_t) corner_bone[i];
     u.num_bones = 0;                                     // (a failed allocation leaves the scene without a skin)
     u.num_parts = 0; u.tri_part.release();               // one deformer per scene: the parts go
-    HIP_TRY(u.rest_verts.reserve(std::max<size_t>(n * 9, 1)));
+    if(int rc = capture_rest(u, n, u.num_targets != 0)) return rc;
     HIP_TRY(u.skin_bone.reserve(std::max<size_t>(corners, 1)));
     HIP_TRY(u.skin_weight.reserve(std::max<size_t>(corners, 1)));
     if(n){
-        HIP_TRY(hipMemcpy(u.rest_verts.get(), u.verts.get(), n * 36, hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(u.skin_bone.get(), bones.data(), corners * sizeof(uint2), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(u.skin_weight.get(), corner_weight, corners * sizeof(float4), hipMemcpyHostToDevice));
     }
@@ -334,6 +364,52 @@ int hpt_skin_host(const void *tris, int nt, const int32_t *corner_bone, const fl
                   void *out){
     char msg[200];
     const char *err = skin_host_records(tris, nt, corner_bone, corner_weight, xforms, num_bones, out, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    return HPT_OK;
+}
+
+int hpt_scene_set_morphs(hpt_scene *s, const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta, int num_entries,
+                         int nt, int num_targets){
+    if(int rc = check_count(s, nt)) return rc;
+    char msg[200];
+    const char *err = check_morphs(target_begin, entry_corner, entry_delta, num_entries, nt, num_targets, msg, sizeof msg);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(int rc = on_scene_device(s)) return rc;
+    if(int rc = ensure_previous(s)) return rc;          // `verts` holds the current geometry from here on
+    hpt_scene::Update &u = s->up;
+    std::vector<uint32_t> corner_begin; std::vector<MorphEntry> entries;
+    transpose_morphs(target_begin, entry_corner, entry_delta, nt, num_targets, corner_begin, entries);
+    u.num_targets = 0;                                   // (a failed allocation leaves the scene without morphs)
+    HIP_TRY(u.morph_begin.reserve(corner_begin.size()));
+    HIP_TRY(u.morph_entries.reserve(std::max<size_t>(entries.size(), 1)));
+    HIP_TRY(u.morph_weights.reserve((size_t) num_targets));
+    if(int rc = capture_rest(u, (size_t) nt, u.num_parts || u.num_bones)) return rc;
+    HIP_TRY(hipMemcpy(u.morph_begin.get(), corner_begin.data(), corner_begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if(!entries.empty()) HIP_TRY(hipMemcpy(u.morph_entries.get(), entries.data(), entries.size() * sizeof(MorphEntry), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(u.morph_weights.get(), 0, (size_t) num_targets * sizeof(float)));
+    HIP_TRY(hipDeviceSynchronize());
+    u.num_targets = num_targets;
+    return HPT_OK;
+}
+
+int hpt_scene_morph(hpt_scene *s, const float *weights, int num_targets){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(s->up.num_targets == 0) return fail(HPT_ERR_INVALID, "hpt_scene_morph before hpt_scene_set_morphs: the scene has no morph targets");
+    if(num_targets != s->up.num_targets){
+        char msg[200];
+        snprintf(msg, sizeof msg, "a morph keeps the number of targets: the scene has %d targets, %d weights were handed over", s->up.num_targets, num_targets);
+        return fail(HPT_ERR_INVALID, msg);
+    }
+    if(!weights) return fail(HPT_ERR_INVALID, "null weight array");
+    if(int rc = on_scene_device(s)) return rc;
+    Feed f{Feed::Morph}; f.weights = weights;
+    return refit_from(s, f, 0.0);
+}
+
+int hpt_morph_host(const void *tris, int nt, const int32_t *target_begin, const int32_t *entry_corner, const float *entry_delta, int num_entries,
+                   int num_targets, const float *weights, void *out){
+    char msg[200];
+    const char *err = morph_host_records(tris, nt, target_begin, entry_corner, entry_delta, num_entries, num_targets, weights, out, msg, sizeof msg);
     if(err && *err) return fail(HPT_ERR_INVALID, err);
     return HPT_OK;
 }
