@@ -1179,7 +1179,7 @@ int hpt_bvh_cost_host(const hpt_bvh_info *info, const void *qnodes, size_t qnode
  * hpt_scene_rebuild returns HPT_ERR_INVALID with a message, before the device is touched, for a null scene or a current
  * device other than the scene's.  A scene of zero triangles accepts the call and counts it.
  *
- * Out of scope: a rebuild on the device; a rebuild off the calling thread; a partial rebuild (re-splitting subtrees); any
+ * Out of scope: a rebuild off the calling thread; a partial rebuild (re-splitting subtrees); any
  * automatic policy inside the library (pt_cli --rebuild-above R is a caller's: it rebuilds when sah exceeds R times the
  * cost measured after the last build); hpt_multi_* and the scene the one-shot wrappers keep; the four-wide tree's cost. */
 typedef struct hpt_rebuild_info {
@@ -1189,6 +1189,70 @@ typedef struct hpt_rebuild_info {
 } hpt_rebuild_info;
 int hpt_scene_rebuild(hpt_scene *scene);
 int hpt_scene_get_rebuild_info(const hpt_scene *scene, hpt_rebuild_info *out);
+
+/* ---- device builds -----------------------------------------------------------------------------------------------
+ * hpt_scene_rebuild_device gives a live handle a new tree built on the device from the vertices the device holds now: no
+ * download, no host builder, no upload.  It is blocking and runs on the null stream, like every update.  The tree is a
+ * linear BVH in Morton order; hpt_bvh_device_build_host is its definition, on the host alone, and the device is held to
+ * its bytes (hpt_scene_export_bvh afterwards equals it: info, qnodes, tris).
+ *
+ * Keys.  Liveness and the box [mn, mx] of a triangle are those of "scene updates" (a non-finite edge: dead).  The cells
+ * lie on the box [lo, hi] of the live triangles: per axis ext = hi - lo and scale = 2097152.0f / ext in float, 0 where
+ * ext > 0 is false.  A live triangle's centroid is c = 0.5f * (mn + mx) per axis, f = (c - lo) * scale, one float
+ * operation at a time, and its cell is f >= 1.0f ? (f < 2097152.0f ? (uint32) f : 2097151) : 0 -- comparisons first, so a
+ * NaN lands in cell 0 and nothing out of range is converted.  A key is 64 bits: bit k of the x cell is bit 3k + 2, of the
+ * y cell bit 3k + 1, of the z cell bit 3k (k = 0 .. 20); bit 63 is clear.  A dead triangle has the key of all ones.
+ * Order.  Ascending by key, ties by input index.  The sorted position is the leaf slot; nothing re-sorts inside a leaf.
+ * Topology.  The binary radix tree (Karras 2012) over the sorted pairs: delta(i, j) is the number of leading bits the keys
+ * at positions i and j share, and 64 plus the number of leading bits the 32-bit positions share where the keys are equal.
+ * A child whose range holds 2 triangles or fewer is the leaf code 0x80000000 | first << 3 | count - 1.  Zero triangles
+ * give a root with two empty children, one or two a root with that leaf and an empty right child, as hpt_scene_create does.
+ * Numbering.  Breadth-first, as hpt_scene_create: level by level, within a level the inner children in order, left before
+ * right.  bvh_depth is the number of levels (0 for an empty scene).
+ * Boxes.  Every leaf record, node box, the padding, the grid and qnodes are those of a refit ("scene updates") on this
+ * topology; each record carries the ordinal, material and flags of its triangle.
+ * The four-wide twin.  The greedy collapse of hpt_scene_create over the float boxes that refit wrote: a node's children
+ * are the binary node's (left, then right); while there are fewer than four and an inner one among them, the inner child
+ * of the largest half area dx*dy + dy*dz + dz*dx (strict >, first found) is replaced by the last child and its own two
+ * are appended.  Wide nodes are numbered breadth-first the same way; wide_depth is their number of levels.
+ *
+ * The depth of a radix tree is the data's.  When the tree has more than 30 levels, or its four-wide twin is too deep for
+ * the resume launch's stack, nothing is swapped: the call runs hpt_scene_rebuild instead, returns its code, and reports
+ * fell_back = 1 (hpt_rebuild_info counts that host rebuild; it counts host rebuilds only).  Before the swap the new qnodes
+ * are measured by the kernel of "tree cost": leaf_slots must equal the triangle count and inner_children + 1 the node
+ * count, else the call returns HPT_ERR_DEVICE with a message and the handle is as it was.  A failed allocation
+ * (HPT_ERR_NOMEM) leaves the handle as it was too.  A scene that was never updated gets its device vertices here, exactly
+ * as from a first update.
+ *
+ * A device build is not an update: everything "rebuild" above lists as kept is kept, and every integrator renders the
+ * same bytes afterwards.  A later update, pose, skin or morph refits the new topology (the export then equals
+ * hpt_bvh_device_build_host with new_triangles).  hpt_stats.bvh_nodes, bvh_depth and ms_bvh_build become the new tree's.
+ *
+ * hpt_scene_get_device_build_info describes the last call (zeros before the first): how many calls have succeeded, fallen
+ * back ones included; whether the last fell back; node count and depth before and after; wide_depth; and the milliseconds
+ * between HIP events of the keys and the sort, of the radix tree with the numbering and the permutation, of the refit, and
+ * of the collapse with the wide boxes and the frames (zeros after a fallback).  The numbering reads 4 bytes back per level.
+ * hpt_bvh_device_build_host fills the fields that describe the tree (builds = 1, fell_back as the device would decide,
+ * the after-counts, wide_depth) and zeros the rest; its info may report a bvh_depth above 30.  Its conventions are those
+ * of hpt_bvh_refit_host: it builds from `triangles`, refits that topology to new_triangles when they are given (NULL: no
+ * refit), and exports as hpt_bvh_export_host does.
+ *
+ * hpt_scene_rebuild_device returns HPT_ERR_INVALID with a message, before the device is touched, for a null scene or a
+ * current device other than the scene's.  A scene of zero triangles accepts the call and counts it.
+ *
+ * Out of scope: a tree of the host builder's quality (PLOC, treelet optimisation, spatial splits); building at
+ * hpt_scene_create; hpt_multi_* and the scene the one-shot wrappers keep; a caller-stream or non-blocking variant;
+ * exporting the four-wide tree; any automatic policy inside the library (pt_cli --rebuild-device is a caller's). */
+typedef struct hpt_device_build_info {
+    uint64_t builds;
+    uint32_t fell_back, nodes_before, nodes_after, depth_before, depth_after, wide_depth;
+    double ms_sort, ms_topology, ms_refit, ms_collapse;
+} hpt_device_build_info;
+int hpt_scene_rebuild_device(hpt_scene *scene);
+int hpt_scene_get_device_build_info(const hpt_scene *scene, hpt_device_build_info *out);
+int hpt_bvh_device_build_host(const void *lights, int num_lights, const void *spheres, int num_spheres, const void *triangles,
+                              const void *new_triangles, int num_triangles, hpt_bvh_info *info, hpt_device_build_info *binfo,
+                              void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,12 @@ class RebuildInfo(C.Structure):
                 ("ms_download", C.c_double), ("ms_build", C.c_double), ("ms_upload", C.c_double)]
 
 
+class DeviceBuildInfo(C.Structure):
+    _fields_ = [("builds", C.c_uint64), ("fell_back", C.c_uint32), ("nodes_before", C.c_uint32), ("nodes_after", C.c_uint32),
+                ("depth_before", C.c_uint32), ("depth_after", C.c_uint32), ("wide_depth", C.c_uint32),
+                ("ms_sort", C.c_double), ("ms_topology", C.c_double), ("ms_refit", C.c_double), ("ms_collapse", C.c_double)]
+
+
 def _tree_cost_dict(c: TreeCost) -> dict:
     """The fields of hpt_tree_cost (root_extent as a tuple) and, under "bytes", the struct's 120 bytes."""
     d = {n: getattr(c, n) for n, _ in c._fields_ if n != "root_extent"}
@@ -206,7 +212,8 @@ def load_library() -> C.CDLL:
                      "hpt_scene_update_vertices_device", "hpt_scene_set_parts", "hpt_scene_pose", "hpt_scene_read_triangles",
                      "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host", "hpt_scene_set_morphs", "hpt_scene_morph",
                      "hpt_morph_host",
-                     "hpt_scene_tree_cost", "hpt_bvh_cost_host", "hpt_scene_rebuild", "hpt_scene_get_rebuild_info"):
+                     "hpt_scene_tree_cost", "hpt_bvh_cost_host", "hpt_scene_rebuild", "hpt_scene_get_rebuild_info",
+                     "hpt_scene_rebuild_device", "hpt_scene_get_device_build_info", "hpt_bvh_device_build_host"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -519,6 +526,19 @@ class Scene:
         """The last rebuild: dict(rebuilds, nodes_before, nodes_after, depth_before, depth_after, ms_download, ms_build, ms_upload)."""
         info = RebuildInfo()
         _check(self._lib.hpt_scene_get_rebuild_info(self._h, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in info._fields_}
+
+    def rebuild_device(self):
+        """A new tree in place, built on the device from the vertices the device holds (include/hpt.h, "device builds"):
+        afterwards export_bvh() equals device_build_bvh_host(lights, spheres, read_triangles()).  A tree too deep for the
+        traversal falls back to rebuild() (device_build_info()["fell_back"]).  Everything else the handle keeps stays.  Blocking."""
+        _check(self._lib.hpt_scene_rebuild_device(self._h))
+
+    def device_build_info(self) -> dict:
+        """The last rebuild_device: dict(builds, fell_back, nodes_before, nodes_after, depth_before, depth_after, wide_depth,
+        ms_sort, ms_topology, ms_refit, ms_collapse)."""
+        info = DeviceBuildInfo()
+        _check(self._lib.hpt_scene_get_device_build_info(self._h, C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_}
 
     # -- ray probes (tests) ---------------------------------------------------------------
@@ -988,6 +1008,26 @@ def refit_bvh_host(lights, spheres, triangles, new_triangles) -> dict:
         raise HptError("hpt error 1: an update keeps the triangle count: %d triangles, %d were handed over" % (len(triangles), len(new_triangles)))
     return _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_refit_host(
         _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), _vp(new_triangles), len(triangles), info, qn, qcap, tr, tcap))
+
+
+def device_build_bvh_host(lights, spheres, triangles, new_triangles=None) -> dict:
+    """hpt_bvh_device_build_host, the definition of Scene.rebuild_device on the host (no device needed): the Morton-order
+    linear BVH over `triangles`, refitted to new_triangles when they are given.  The keys of export_bvh_host and, under
+    "build", the fields of hpt_device_build_info that describe the tree (bvh_depth may exceed 30: the device falls back then)."""
+    lib = load_library()
+    lights = np.ascontiguousarray(lights, LIGHT)
+    spheres = np.ascontiguousarray(spheres, SPHERE)
+    triangles = np.ascontiguousarray(triangles, TRIANGLE)
+    if new_triangles is not None:
+        new_triangles = np.ascontiguousarray(new_triangles, TRIANGLE)
+        if len(new_triangles) != len(triangles):
+            raise HptError("hpt error 1: an update keeps the triangle count: %d triangles, %d were handed over" % (len(triangles), len(new_triangles)))
+    binfo = DeviceBuildInfo()
+    out = _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_device_build_host(
+        _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), _vp(new_triangles) if new_triangles is not None else None,
+        len(triangles), info, C.byref(binfo), qn, qcap, tr, tcap))
+    out["build"] = {n: getattr(binfo, n) for n, _ in binfo._fields_}
+    return out
 
 
 def pose_host(triangles, tri_part, xforms) -> np.ndarray:

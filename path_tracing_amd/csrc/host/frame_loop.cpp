@@ -72,6 +72,18 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     const bool rebuilds = motion && motion->rebuild_above != 0.0;                      // --rebuild-above
     if(rebuilds && !(motion->rebuild_above > 1.0)){ std::cerr << "[Error] --rebuild-above needs a ratio above 1" << std::endl; return -1; }
     if(rebuilds && !spin){ std::cerr << "[Error] --rebuild-above needs --spin, --spin-device, --twist-device or --morph-device" << std::endl; return -1; }
+    const bool device_builds = motion && motion->rebuild_device;                       // --rebuild-device
+    if(device_builds && !spin){ std::cerr << "[Error] --rebuild-device needs --spin, --spin-device, --twist-device or --morph-device" << std::endl; return -1; }
+    // a device build, with the time of its four phases (the host builder's when it fell back)
+    auto device_build = [&](double &ms, bool &fell_back) -> int {
+        hpt_device_build_info di; hpt_rebuild_info ri;
+        if(hpt_scene_rebuild_device(run.scene) != HPT_OK) return hpt_failed("hpt_scene_rebuild_device");
+        if(hpt_scene_get_device_build_info(run.scene, &di) != HPT_OK) return hpt_failed("hpt_scene_get_device_build_info");
+        if(hpt_scene_get_rebuild_info(run.scene, &ri) != HPT_OK) return hpt_failed("hpt_scene_get_rebuild_info");
+        fell_back = di.fell_back != 0;
+        ms = fell_back ? ri.ms_download + ri.ms_build + ri.ms_upload : di.ms_sort + di.ms_topology + di.ms_refit + di.ms_collapse;
+        return 0;
+    };
     double sah_base = 0.0;
     if(rebuilds){
         hpt_tree_cost c;
@@ -171,14 +183,27 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
                 if(hpt_scene_tree_cost(run.scene, &before) != HPT_OK) return hpt_failed("hpt_scene_tree_cost");
                 if(before.sah > motion->rebuild_above * sah_base){
                     hpt_rebuild_info ri;
-                    if(hpt_scene_rebuild(run.scene) != HPT_OK) return hpt_failed("hpt_scene_rebuild");
+                    double ms = 0.0; bool fell_back = false;
+                    if(device_builds){ if(int e = device_build(ms, fell_back)) return e; }
+                    else {
+                        if(hpt_scene_rebuild(run.scene) != HPT_OK) return hpt_failed("hpt_scene_rebuild");
+                        if(hpt_scene_get_rebuild_info(run.scene, &ri) != HPT_OK) return hpt_failed("hpt_scene_get_rebuild_info");
+                        ms = ri.ms_download + ri.ms_build + ri.ms_upload;
+                    }
                     if(hpt_scene_tree_cost(run.scene, &after) != HPT_OK) return hpt_failed("hpt_scene_tree_cost");
-                    if(hpt_scene_get_rebuild_info(run.scene, &ri) != HPT_OK) return hpt_failed("hpt_scene_get_rebuild_info");
                     char line[160];
-                    snprintf(line, sizeof line, "[Rebuild] frame %d sah %.4f -> %.4f %.3f ms", f, before.sah, after.sah, ri.ms_download + ri.ms_build + ri.ms_upload);
+                    snprintf(line, sizeof line, "[Rebuild] frame %d sah %.4f -> %.4f %.3f ms", f, before.sah, after.sah, ms);
                     std::cout << line << std::endl;
                     sah_base = after.sah;
                 }
+            } else if(device_builds){    // no ratio: a new tree for every frame's geometry
+                double ms = 0.0; bool fell_back = false;
+                if(int e = device_build(ms, fell_back)) return e;
+                hpt_stats st;
+                if(hpt_get_stats(run.scene, &st) != HPT_OK) return hpt_failed("hpt_get_stats");
+                char line[160];
+                snprintf(line, sizeof line, "[Rebuild] frame %d %s nodes %u depth %u %.3f ms", f, fell_back ? "host" : "device", st.bvh_nodes, st.bvh_depth, ms);
+                std::cout << line << std::endl;
             }
         }
         const bool follow = spin && reproject;          // the motion guide every frame

@@ -69,6 +69,11 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // the new sah as the baseline.  The rebuild sits between the update and the motion guides; the previous geometry is untouched,
 // so a history keeps following across it.  The image does not depend on it.
 //
+// With `rebuild_device` (--rebuild-device; needs moving geometry) the rebuilds are hpt_scene_rebuild_device's (include/hpt.h,
+// "device builds"): under `rebuild_above` the same policy with the device build in the host rebuild's place, without it a
+// device build after every frame's update, one "[Rebuild] frame <f> device nodes <n> depth <d> <ms> ms" line each (the sah is
+// not measured then).  A build that fell back to the host builder says "host" for "device".
+//
 // With `morph_at` (--morph-device; needs `morphs_of`, excludes `triangles_at`, combines with `pose_at` or `skin_at`) the geometry
 // is morphed first: before frame 0 morphs_of fills the sparse targets from the moved scene's records and returns their number,
 // which goes to hpt_scene_set_morphs once; before frame f > 0 morph_at fills one weight per target and the loop calls
@@ -88,6 +93,7 @@ struct FrameMotion {
     bool guided = false;
     bool temporal_variance = false;
     double rebuild_above = 0.0;           // 0: never
+    bool rebuild_device = false;          // rebuilds are device builds; with rebuild_above == 0: after every update
 };
 int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                    int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,

@@ -27,6 +27,9 @@
 //   --rebuild-above R with --frames and --spin, --spin-device or --twist-device: measure the tree's cost (hpt_scene_tree_cost) after
 //                     each frame's update and rebuild the tree in place (hpt_scene_rebuild) when its sah exceeds R times the
 //                     cost of the last built tree; one "[Rebuild]" line per rebuild.  R must be above 1.  Same image.
+//   --rebuild-device  with --frames and --spin, --spin-device, --twist-device or --morph-device: the rebuilds of --rebuild-above are
+//                     built on the device (hpt_scene_rebuild_device); without --rebuild-above the tree is rebuilt on the device
+//                     before every frame that follows an update.  Same image.
 //   --morph-device AMP with --frames and --obj: the OBJ morphed through hpt_scene_set_morphs once and hpt_scene_morph per frame: two
 //                     targets on the OBJ's corners, an outward push and a lift that both grow with the corner's height in the mesh,
 //                     under weights that swing with the frame; combines with --spin-device or --twist-device (morph, then the
@@ -78,6 +81,7 @@ int main(int argc, char **argv){
     double morph_amp = 0.0;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     bool rebuild = false; double rebuild_above = 0.0;
+    bool rebuild_device = false;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -110,6 +114,7 @@ int main(int argc, char **argv){
         else if(arg == "--spin-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); spin_device = true; }
         else if(arg == "--twist-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); twist_device = true; }
         else if(arg == "--rebuild-above" && i + 1 < argc){ rebuild_above = std::stod(argv[++i]); rebuild = true; }
+        else if(arg == "--rebuild-device") rebuild_device = true;
         else if(arg == "--morph-device" && i + 1 < argc){ morph_amp = std::stod(argv[++i]); morph_device = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
@@ -154,6 +159,8 @@ int main(int argc, char **argv){
                       << "                    --spin-device\n"
                       << "  --rebuild-above <R>  with --frames and --spin, --spin-device or --twist-device: rebuild the tree in place when its\n"
                       << "                    cost (sah of hpt_scene_tree_cost) exceeds R times the last built tree's; R > 1\n"
+                      << "  --rebuild-device  the rebuilds of --rebuild-above are built on the device (hpt_scene_rebuild_device); without\n"
+                      << "                    --rebuild-above the tree is rebuilt on the device before every frame that follows an update\n"
                       << "  --morph-device <amp>  with --frames and --obj: the OBJ morphed by two targets on the device (hpt_scene_set_morphs once,\n"
                       << "                    hpt_scene_morph per frame): target 0 pushes a corner away from the vertical axis through the centroid,\n"
                       << "                    target 1 lifts it, both by the corner's height in the mesh times a quarter of the OBJ's radius; the\n"
@@ -228,6 +235,9 @@ int main(int argc, char **argv){
 
     const int W = width > 0 ? width : scene.resolution.first;
     const int H = height > 0 ? height : scene.resolution.second;
+    if(rebuild_device && (frames < 1 || !(spin || spin_device || twist_device || morph_device))){
+        std::cerr << "[Error] --rebuild-device needs --frames and one of --spin, --spin-device, --twist-device, --morph-device.\n"; return -1;
+    }
     float F = 50;
     CudaCamera cam = hpt_host::make_cuda_camera(scene.camera, F, W, H);
     std::vector<float3> frame_results((size_t) W * H);
@@ -245,6 +255,7 @@ int main(int argc, char **argv){
         hpt_host::FrameMotion motion;
         motion.reproject = reproject; motion.guide_spp = guide_spp; motion.guided = guided; motion.temporal_variance = temporal_variance;
         motion.rebuild_above = rebuild ? rebuild_above : 0.0;
+        motion.rebuild_device = rebuild_device;
         if(orbit) motion.camera_at = [&](int f, void *camera84){
             // Rodrigues' rotation of eye - look_at about the unit up vector, in double
             const hpt_host::Camera &c = scene.camera;

@@ -324,6 +324,7 @@ void hpt_scene_destroy(hpt_scene *s){
     for(hipEvent_t e : s->pm.marks) hipEventDestroy(e);
     if(s->up.ev_a) hipEventDestroy(s->up.ev_a);
     if(s->up.ev_b) hipEventDestroy(s->up.ev_b);
+    for(hipEvent_t e : s->rb.ev) if(e) hipEventDestroy(e);
     if(s->tm.ev_start) hipEventDestroy(s->tm.ev_start);
     if(s->tm.ev_stop) hipEventDestroy(s->tm.ev_stop);
     for(hipEvent_t e : s->tm.event_pool) hipEventDestroy(e);

@@ -1,5 +1,5 @@
 // Host side of libhpt.so, shared by its translation units (hpt_api.cpp, render_pt.cpp, render_bdpt.cpp, render_ppm.cpp,
-// denoise.cpp, hpt_multi.cpp, scene_update.cpp, scene_rebuild.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
+// denoise.cpp, hpt_multi.cpp, scene_update.cpp, scene_rebuild.cpp, scene_rebuild_device.cpp): the error channel, the owner of device memory, struct hpt_scene and the steps every integrator takes.
 // Internal and host only; compiled as HIP because it includes the launch interfaces.
 #pragma once
 #include "../../include/hpt.h"
@@ -9,6 +9,7 @@
 #include "ppm_kernels.h"
 #include "denoise_kernels.h"
 #include "refit_kernels.h"
+#include "lbvh_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -202,6 +203,8 @@ struct hpt_scene {
     struct Rebuild {
         hpt::DevBuf<unsigned long long> cost;        // kCostResultWords
         hpt_rebuild_info info{};
+        hpt_device_build_info dinfo{};               // the last hpt_scene_rebuild_device (scene_rebuild_device.cpp)
+        hipEvent_t ev[5] = {};                       // ... and the events around its four phases
     } rb;
 
     // timing and statistics of the last render
@@ -286,6 +289,16 @@ inline bool same_bytes(const std::vector<unsigned char> &kept, const void *given
 // that brought vertices on the device only (scene_update.cpp) this downloads `verts` and splices the 36 bytes per record --
 // once, and only here, so a handle whose records nobody reads never pays for it.  Readers of the vertex bytes go through it.
 int host_triangles(hpt_scene *s, const unsigned char **tris);
+
+// scene_update.cpp, shared with the device build (scene_rebuild_device.cpp).  ensure_previous: the device vertices (and the
+// previous geometry) of a scene that was never updated, from the records it keeps.  ensure_scratch: the refit's scratch for
+// the handle's tree.  refit_tree_boxes: the refit's launches up to the quantised binary tree -- leaf records, slot boxes, the
+// live box, node boxes level by level, the grid, qnodes -- on the tree handed over (the handle's own, or one being built),
+// from up.verts through the handle's scratch; `exact` holds 6 floats per node.
+int ensure_previous(hpt_scene *s);
+int ensure_scratch(hpt_scene *s);
+struct RefitTree { float4 *nodes; uint4 *qnodes; float4 *tris; float *exact; uint32_t num_nodes; const std::vector<uint32_t> *level_begin; };
+int refit_tree_boxes(hpt_scene *s, const RefitTree &t, RefitGrid &grid, uint32_t &ndead);
 
 // the arrays and the description hpt_bvh_export_host hands out, of a scene built (or refitted) on the host (hpt_api.cpp)
 int export_host_tree(const HostScene &hs, hpt_bvh_info *info, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);

@@ -183,6 +183,13 @@ const char *check_rounds_update(const void *kept_spheres, int kept_ns, int kept_
 // device's refit (refit_kernels.hip) is held to these bytes.  dead_out: the number of triangles no ray can hit.
 const char *refit_host_scene(HostScene &hs, const void *tris, int nt, uint64_t *dead_out = nullptr);
 
+// The definition of a device build (include/hpt.h, "device builds"): the Morton-order linear BVH over `tris` -- 63-bit keys of
+// the live centroids on the live triangles' box, a stable sort, the binary radix tree with leaves of kMaxLeafTris triangles
+// or fewer, build_host_scene's breadth-first numbering and greedy four-wide collapse -- with every box, the grid and both
+// quantised trees from refit_host_scene on that topology.  hs.bvh_depth may exceed kMaxBvhDepth: the depth of a radix tree
+// is the data's (the device falls back to the host builder then).  The device builder (lbvh_kernels.hip) is held to these bytes.
+const char *lbvh_host_scene(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt, HostScene &out);
+
 // ---- poses (include/hpt.h, "poses"): per-part 3 x 4 transforms applied to a rest pose ----
 
 constexpr int kMaxParts = 1 << 20;

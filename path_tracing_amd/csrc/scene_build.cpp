@@ -538,6 +538,11 @@ void pack_wide_boxes(HostScene &hs){
     });
 }
 
+// (defined behind build_host_scene)
+void triangle_materials(const RefTriangle *tris, int nt, std::map<MatKey, uint32_t> &mat_table, std::vector<DevMaterial> &materials,
+                        pod_vector<uint32_t> &mat_of);
+void collapse_wide(HostScene &hs);
+
 } // namespace
 
 void grid_of_box(const float lo_in[3], const float hi_in[3], float qorigin[3], float qscale[3]){
@@ -1047,7 +1052,48 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
     quantise_tree(hs);
     if(hs.bvh_depth > kMaxBvhDepth) return "internal error: BVH deeper than the traversal stack";
     lap("quantise");
-    {   // four-wide twin: greedy collapse of the binary tree, breadth-first numbering, same quantised child boxes
+    collapse_wide(hs);
+
+    lap("wide");
+    hs.tris.resize(nt);
+    pod_vector<uint32_t> mat_of((size_t) nt);
+    triangle_materials(tris, nt, mat_table, hs.materials, mat_of);
+    parallel_chunks((size_t) nt, [&](int, size_t b0, size_t e0){
+        for(size_t s = b0; s < e0; ++s){
+            const RefTriangle &t = tris[B.prims[s].index];        // leaf order = the order the build left the primitives in
+            DevTriangle &d = hs.tris[s];
+            triangle_geometry(d, t);
+            d.ordinal = (uint32_t) (ns + nl) + B.prims[s].index;
+            d.material = mat_of[B.prims[s].index];
+            d.flags = (t.m.eta <= 0.0f) ? 1u : 0u;
+        }
+    });
+    lap("triangles");
+    auto t1 = std::chrono::steady_clock::now();
+    hs.ms_bvh_build = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    if(hs.materials.empty()) hs.materials.push_back(blank_material());
+    return "";
+}
+
+namespace {
+
+// materials are numbered in order of first appearance in the INPUT (spheres, then triangles as handed over): one sequential
+// pass over the records that mostly hits its one-entry cache; the leaf-order fill looks the numbers up in mat_of
+void triangle_materials(const RefTriangle *tris, int nt, std::map<MatKey, uint32_t> &mat_table, std::vector<DevMaterial> &materials,
+                        pod_vector<uint32_t> &mat_of){
+    RefMat last; memset(&last, 0xFF, sizeof last); uint32_t last_idx = 0; bool have = false;
+    for(int i = 0; i < nt; ++i){
+        const RefMat &m = tris[i].m;
+        if(!have || memcmp(&m, &last, 28) != 0){ last_idx = intern_material(m, mat_table, materials); last = m; have = true; }
+        mat_of[(size_t) i] = last_idx;
+    }
+}
+
+// four-wide twin: greedy collapse of the binary tree hs.nodes (stored float boxes and child codes), breadth-first numbering,
+// same quantised child boxes; fills wnodes, wide_src and wide_depth.  build_host_scene and lbvh_host_scene run these lines.
+void collapse_wide(HostScene &hs){
+    hs.wide_depth = 0;
+    {
         struct Kid { const float *mn, *mx; uint32_t code, src; };      // src: binary node * 2 + side, what a refit reads the box from
         auto half_area = [](const Kid &k){ float dx = k.mx[0] - k.mn[0], dy = k.mx[1] - k.mn[1], dz = k.mx[2] - k.mn[2]; return dx * dy + dy * dz + dz * dx; };
         struct Kids { Kid k[4]; int n; uint32_t code[4]; };
@@ -1115,33 +1161,151 @@ const char *build_host_scene(const void *lights_v, int nl, const void *spheres_v
         });
         pack_wide_boxes(hs);
     }
+}
 
-    lap("wide");
-    hs.tris.resize(nt);
-    // materials are numbered in order of first appearance in the INPUT (spheres, then triangles as handed over): one sequential
-    // pass over the records that mostly hits its one-entry cache; the leaf-order fill below looks the numbers up
-    pod_vector<uint32_t> mat_of((size_t) nt);
-    {   RefMat last; memset(&last, 0xFF, sizeof last); uint32_t last_idx = 0; bool have = false;
-        for(int i = 0; i < nt; ++i){
-            const RefMat &m = tris[i].m;
-            if(!have || memcmp(&m, &last, 28) != 0){ last_idx = intern_material(m, mat_table, hs.materials); last = m; have = true; }
-            mat_of[(size_t) i] = last_idx;
-        }
+// ---- device builds (include/hpt.h, "device builds"): the Morton-order linear BVH the device builds, restated on the host ----
+
+// cell of a centroid on one axis, 21 bits: Builder::bin_of's shape -- the comparisons first, so a NaN goes to cell 0 and
+// nothing out of range is converted
+inline uint32_t lbvh_cell(float cen, float lo, float scale){
+    const float f = (cen - lo) * scale;
+    return f >= 1.0f ? (f < 2097152.0f ? (uint32_t) f : 2097151u) : 0u;
+}
+// bit k of a 21-bit cell to bit 3 * k
+inline uint64_t lbvh_spread(uint32_t v){
+    uint64_t x = v & 0x1FFFFFu;
+    x = (x | x << 32) & 0x001F00000000FFFFull;
+    x = (x | x << 16) & 0x001F0000FF0000FFull;
+    x = (x | x << 8) & 0x100F00F00F00F00Full;
+    x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+// common-prefix length of the sorted pairs at positions i and j (-1 when j lies outside): of the 64-bit keys, and for equal
+// keys 64 plus that of the positions as 32-bit words
+inline int lbvh_delta(const uint64_t *keys, int64_t n, int64_t i, int64_t j){
+    if(j < 0 || j >= n) return -1;
+    const uint64_t x = keys[i] ^ keys[j];
+    if(x) return __builtin_clzll(x);
+    return 64 + __builtin_clz((uint32_t) i ^ (uint32_t) j);
+}
+
+} // namespace
+
+const char *lbvh_host_scene(const void *lights_v, int nl, const void *spheres_v, int ns, const void *tris_v, int nt, HostScene &hs){
+    if(nl < 0 || ns < 0 || nt < 0) return "negative primitive count";
+    if((nl > 0 && !lights_v) || (ns > 0 && !spheres_v) || (nt > 0 && !tris_v)) return "null primitive array";
+    if((uint64_t) nt >= (1ull << 28)) return "too many triangles (limit 2^28)";
+    const RefSphere *spheres = (const RefSphere *) spheres_v;
+    const RefTriangle *tris = (const RefTriangle *) tris_v;
+    auto t0 = std::chrono::steady_clock::now();
+
+    hs = HostScene();
+    hs.num_spheres = ns; hs.num_lights = nl; hs.num_tris = nt;
+    std::map<MatKey, uint32_t> mat_table;
+    {   std::vector<uint32_t> sphere_material((size_t) ns);
+        for(int i = 0; i < ns; ++i) sphere_material[(size_t) i] = intern_material(spheres[i].m, mat_table, hs.materials);
+        const char *e = flatten_rounds_host(lights_v, nl, spheres_v, ns, sphere_material.data(), hs.rounds, hs.lights);
+        if(e && *e) return e;
     }
-    parallel_chunks((size_t) nt, [&](int, size_t b0, size_t e0){
-        for(size_t s = b0; s < e0; ++s){
-            const RefTriangle &t = tris[B.prims[s].index];        // leaf order = the order the build left the primitives in
-            DevTriangle &d = hs.tris[s];
-            triangle_geometry(d, t);
-            d.ordinal = (uint32_t) (ns + nl) + B.prims[s].index;
-            d.material = mat_of[B.prims[s].index];
-            d.flags = (t.m.eta <= 0.0f) ? 1u : 0u;
-        }
-    });
-    lap("triangles");
-    auto t1 = std::chrono::steady_clock::now();
-    hs.ms_bvh_build = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    pod_vector<uint32_t> mat_of((size_t) nt);
+    triangle_materials(tris, nt, mat_table, hs.materials, mat_of);
     if(hs.materials.empty()) hs.materials.push_back(blank_material());
+
+    // keys: liveness and boxes are triangle_boxes'; the cells lie on the live triangles' box
+    const size_t n = (size_t) nt;
+    pod_vector<Box> tb(n);
+    std::vector<unsigned char> live(n, 0);
+    Box scene_box;
+    triangle_boxes(tris, nt, scene_box, [&](size_t i, const Box &b, bool l){ tb[i] = b; live[i] = l ? 1 : 0; });
+    float scale[3];
+    for(int a = 0; a < 3; ++a){ const float ext = scene_box.mx[a] - scene_box.mn[a]; scale[a] = ext > 0.0f ? 2097152.0f / ext : 0.0f; }
+    std::vector<uint64_t> key_of(n);
+    for(size_t i = 0; i < n; ++i){
+        if(!live[i]){ key_of[i] = ~0ull; continue; }
+        uint32_t cell[3];
+        for(int a = 0; a < 3; ++a){ const float c = 0.5f * (tb[i].mn[a] + tb[i].mx[a]); cell[a] = lbvh_cell(c, scene_box.mn[a], scale[a]); }
+        key_of[i] = lbvh_spread(cell[0]) << 2 | lbvh_spread(cell[1]) << 1 | lbvh_spread(cell[2]);
+    }
+    // order: ascending key, ties by input index; the sorted position is the leaf slot
+    std::vector<uint32_t> order(n);
+    for(size_t i = 0; i < n; ++i) order[i] = (uint32_t) i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){ return key_of[a] < key_of[b]; });
+    std::vector<uint64_t> keys(n);
+    hs.tris.resize(n);
+    for(size_t s = 0; s < n; ++s){
+        const uint32_t i = order[s];
+        keys[s] = key_of[i];
+        DevTriangle &d = hs.tris[s];
+        triangle_geometry(d, tris[i]);
+        d.ordinal = (uint32_t) (ns + nl) + i;
+        d.material = mat_of[i];
+        d.flags = (tris[i].m.eta <= 0.0f) ? 1u : 0u;
+    }
+
+    // topology: the binary radix tree over the sorted pairs; child codes in radix numbering (inner node k splits its range
+    // behind position gamma: the left child is inner node gamma, the right one gamma + 1, a range of kMaxLeafTris or fewer a leaf)
+    auto leaf_code = [](int64_t first, int64_t count){ return kLeafFlag | ((uint32_t) first << 3) | (uint32_t) (count - 1); };
+    BvhNode blank; memset(&blank, 0, sizeof blank);
+    if(nt <= kMaxLeafTris){
+        hs.nodes.assign(1, blank);
+        hs.nodes[0].left = nt > 0 ? leaf_code(0, nt) : kEmptyChild;
+        hs.nodes[0].right = kEmptyChild;
+        hs.level_begin = { 0u, 1u };
+        hs.bvh_depth = nt > 0 ? 1 : 0;
+    } else {
+        const int64_t N = (int64_t) nt;
+        std::vector<uint32_t> rl(n - 1), rr(n - 1);
+        for(int64_t i = 0; i < N - 1; ++i){
+            const uint64_t *k = keys.data();
+            const int64_t d = lbvh_delta(k, N, i, i + 1) > lbvh_delta(k, N, i, i - 1) ? 1 : -1;
+            const int dmin = lbvh_delta(k, N, i, i - d);
+            int64_t lmax = 2;
+            while(lbvh_delta(k, N, i, i + lmax * d) > dmin) lmax *= 2;
+            int64_t l = 0;
+            for(int64_t t = lmax / 2; t >= 1; t /= 2) if(lbvh_delta(k, N, i, i + (l + t) * d) > dmin) l += t;
+            const int64_t j = i + l * d;
+            const int dnode = lbvh_delta(k, N, i, j);
+            int64_t s = 0;
+            for(int64_t t = (l + 1) / 2; ; t = (t + 1) / 2){
+                if(lbvh_delta(k, N, i, i + (s + t) * d) > dnode) s += t;
+                if(t <= 1) break;
+            }
+            const int64_t gamma = i + s * d + std::min<int64_t>(d, 0);
+            const int64_t first = std::min(i, j), last = std::max(i, j);
+            const int64_t lc = gamma - first + 1, rc = last - gamma;
+            rl[(size_t) i] = lc <= kMaxLeafTris ? leaf_code(first, lc) : (uint32_t) gamma;
+            rr[(size_t) i] = rc <= kMaxLeafTris ? leaf_code(gamma + 1, rc) : (uint32_t) (gamma + 1);
+        }
+        // numbering: breadth-first, build_host_scene's rule -- level by level, within a level the inner children in order, left
+        // before right; radix nodes no child code names drop out
+        std::vector<uint32_t> from(1, 0u);               // radix number of every node, breadth-first
+        size_t lvl_begin = 0, lvl_end = 1;
+        while(lvl_begin < lvl_end){
+            hs.level_begin.push_back((uint32_t) lvl_begin);
+            for(size_t q = lvl_begin; q < lvl_end; ++q){
+                BvhNode nd = blank;
+                const uint32_t c[2] = { rl[from[q]], rr[from[q]] };
+                uint32_t out[2];
+                for(int side = 0; side < 2; ++side){
+                    if(c[side] & kLeafFlag){ out[side] = c[side]; continue; }
+                    out[side] = (uint32_t) from.size();
+                    from.push_back(c[side]);
+                }
+                nd.left = out[0]; nd.right = out[1];
+                hs.nodes.push_back(nd);
+            }
+            lvl_begin = lvl_end; lvl_end = from.size();
+        }
+        hs.level_begin.push_back((uint32_t) lvl_end);
+        hs.bvh_depth = (int) hs.level_begin.size() - 1;       // the builder's count: the deepest leaf's depth, root = 0
+    }
+    // everything that is a function of the vertex positions: the refit's own lines, then the collapse over the boxes it wrote
+    const char *e = refit_host_scene(hs, tris_v, nt);
+    if(e && *e) return e;
+    collapse_wide(hs);
+    hs.ms_bvh_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return "";
 }
 

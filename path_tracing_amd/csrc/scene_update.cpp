@@ -32,8 +32,10 @@ int check_triangles(const hpt_scene *s, const void *tris, int nt){
     return on_scene_device(s);
 }
 
+} // namespace
+
 // scratch of the refit, and the build's wide-node map on the device: allocated by the first update and kept
-int ensure_scratch(hpt_scene *s){
+int hpt::ensure_scratch(hpt_scene *s){
     hpt_scene::Update &u = s->up;
     const size_t nt = (size_t) s->geo.nt, nn = (size_t) s->geo.sd.num_nodes;
     HIP_TRY(u.verts.reserve(std::max<size_t>(nt * 9, 1)));
@@ -53,6 +55,7 @@ int ensure_scratch(hpt_scene *s){
     return HPT_OK;
 }
 
+namespace {
 // centre | radius of every sphere record
 std::vector<float4> pack_spheres(const std::vector<unsigned char> &h_spheres, int ns){
     std::vector<float4> r((size_t) ns);
@@ -60,9 +63,11 @@ std::vector<float4> pack_spheres(const std::vector<unsigned char> &h_spheres, in
     return r;
 }
 
+} // namespace
+
 // The previous geometry, before the first update changes the current one: G' = G from the records the scene keeps.  `verts`
 // is filled too, so that from here on it holds the current geometry whichever update comes first.
-int ensure_previous(hpt_scene *s){
+int hpt::ensure_previous(hpt_scene *s){
     hpt_scene::Update &u = s->up;
     if(u.prev_ready) return HPT_OK;
     const hpt_scene::Geometry &g = s->geo;
@@ -83,6 +88,51 @@ int ensure_previous(hpt_scene *s){
     u.prev_ready = true;
     return HPT_OK;
 }
+
+int hpt::refit_tree_boxes(hpt_scene *s, const RefitTree &t, RefitGrid &grid, uint32_t &ndead){
+    hpt_scene::Update &u = s->up;
+    hpt_scene::Geometry &g = s->geo;
+    const int nt = g.nt;
+    const uint32_t num_nodes = t.num_nodes;
+    float4 *nodes = t.nodes;
+    const std::vector<uint32_t> &level_begin = *t.level_begin;
+    // leaf records, slot boxes, the live triangles' box and the dead count
+    HIP_TRY(hipMemsetAsync(u.result.get(), 0, 8 * sizeof(float), nullptr));
+    launch_refit_tris(nullptr, u.verts.get(), t.tris, (uint32_t) nt, (uint32_t) g.sd.num_rounds, u.slot_box.get(), u.partial.get(),
+                      (uint32_t *) (u.result.get() + 6));
+    launch_refit_reduce(nullptr, u.partial.get(), nt ? refit_blocks((uint32_t) nt) : 0u, u.result.get());
+    HIP_TRY(hipGetLastError());
+    float res[8];
+    HIP_TRY(hipMemcpy(res, u.result.get(), sizeof res, hipMemcpyDeviceToHost));
+    memcpy(&ndead, &res[6], 4);
+    // the dead point and pad_abs, as the builder has them (scene_build.cpp, triangle_boxes and box_padding)
+    float mn[3] = { res[0], res[1], res[2] }, mx[3] = { res[3], res[4], res[5] }, at[3] = { 0.0f, 0.0f, 0.0f };
+    if(ndead > 0){
+        for(int a = 0; a < 3; ++a){
+            at[a] = ndead < (uint32_t) nt ? mn[a] : 0.0f;
+            mn[a] = std::min(mn[a], at[a]); mx[a] = std::max(mx[a], at[a]);
+        }
+    }
+    const float pad_abs = box_padding_of(mn, mx, nt);
+    // node boxes, deepest level first
+    for(size_t l = level_begin.size() - 1; l-- > 0; )
+        launch_refit_level(nullptr, nodes, num_nodes, level_begin[l], level_begin[l + 1] - level_begin[l], u.slot_box.get(), (uint32_t) nt,
+                           t.exact, pad_abs, at[0], at[1], at[2]);
+    HIP_TRY(hipGetLastError());
+    // the grid is the union of the stored boxes, which is the union of the root's two (padding is monotone)
+    BvhNode root;
+    HIP_TRY(hipMemcpy(&root, nodes, sizeof root, hipMemcpyDeviceToHost));
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for(int a = 0; a < 3; ++a){
+        if(root.left != kEmptyChild){ lo[a] = std::min(lo[a], std::min(root.lmin[a], root.lmax[a])); hi[a] = std::max(hi[a], std::max(root.lmin[a], root.lmax[a])); }
+        if(root.right != kEmptyChild){ lo[a] = std::min(lo[a], std::min(root.rmin[a], root.rmax[a])); hi[a] = std::max(hi[a], std::max(root.rmin[a], root.rmax[a])); }
+    }
+    grid_of_box(lo, hi, grid.qorigin, grid.qscale);
+    launch_refit_quantise(nullptr, nodes, t.qnodes, num_nodes, grid);
+    return HPT_OK;
+}
+
+namespace {
 
 // What an update brings: records from the host (hpt_scene_update_triangles, packed into up.h_verts by the caller), nine floats
 // per triangle on the device, one record per part applied to the rest pose, one record per bone blended over it, or one
@@ -146,41 +196,10 @@ int refit_from(hpt_scene *s, const Feed &f, double ms_pack){
     }
     if(run_parts) launch_pose_verts(nullptr, rest, u.tri_part.get(), u.xforms.get(), (uint32_t) u.num_parts, (uint32_t) nt, u.verts.get());
     if(run_skin) launch_skin_verts(nullptr, rest, u.skin_bone.get(), u.skin_weight.get(), u.xforms.get(), (uint32_t) u.num_bones, (uint32_t) nt, u.verts.get());
-    // leaf records, slot boxes, the live triangles' box and the dead count
-    HIP_TRY(hipMemsetAsync(u.result.get(), 0, 8 * sizeof(float), nullptr));
-    launch_refit_tris(nullptr, u.verts.get(), (float4 *) g.tris.get(), (uint32_t) nt, (uint32_t) g.sd.num_rounds, u.slot_box.get(), u.partial.get(),
-                      (uint32_t *) (u.result.get() + 6));
-    launch_refit_reduce(nullptr, u.partial.get(), nt ? refit_blocks((uint32_t) nt) : 0u, u.result.get());
-    HIP_TRY(hipGetLastError());
-    float res[8];
-    HIP_TRY(hipMemcpy(res, u.result.get(), sizeof res, hipMemcpyDeviceToHost));
-    uint32_t ndead; memcpy(&ndead, &res[6], 4);
-    // the dead point and pad_abs, as the builder has them (scene_build.cpp, triangle_boxes and box_padding)
-    float mn[3] = { res[0], res[1], res[2] }, mx[3] = { res[3], res[4], res[5] }, at[3] = { 0.0f, 0.0f, 0.0f };
-    if(ndead > 0){
-        for(int a = 0; a < 3; ++a){
-            at[a] = ndead < (uint32_t) nt ? mn[a] : 0.0f;
-            mn[a] = std::min(mn[a], at[a]); mx[a] = std::max(mx[a], at[a]);
-        }
-    }
-    const float pad_abs = box_padding_of(mn, mx, nt);
-    // node boxes, deepest level first
-    for(size_t l = u.level_begin.size() - 1; l-- > 0; )
-        launch_refit_level(nullptr, nodes, num_nodes, u.level_begin[l], u.level_begin[l + 1] - u.level_begin[l], u.slot_box.get(), (uint32_t) nt,
-                           u.exact.get(), pad_abs, at[0], at[1], at[2]);
-    HIP_TRY(hipGetLastError());
-    // the grid is the union of the stored boxes, which is the union of the root's two (padding is monotone)
-    BvhNode root;
-    HIP_TRY(hipMemcpy(&root, nodes, sizeof root, hipMemcpyDeviceToHost));
-    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for(int a = 0; a < 3; ++a){
-        if(root.left != kEmptyChild){ lo[a] = std::min(lo[a], std::min(root.lmin[a], root.lmax[a])); hi[a] = std::max(hi[a], std::max(root.lmin[a], root.lmax[a])); }
-        if(root.right != kEmptyChild){ lo[a] = std::min(lo[a], std::min(root.rmin[a], root.rmax[a])); hi[a] = std::max(hi[a], std::max(root.rmin[a], root.rmax[a])); }
-    }
-    RefitGrid grid;
-    grid_of_box(lo, hi, grid.qorigin, grid.qscale);
+    RefitGrid grid; uint32_t ndead = 0;
+    const RefitTree tree{ nodes, (uint4 *) g.qnodes.get(), (float4 *) g.tris.get(), u.exact.get(), num_nodes, &u.level_begin };
+    if(int rc = refit_tree_boxes(s, tree, grid, ndead)) return rc;
     for(int a = 0; a < 3; ++a){ g.sd.qorigin[a] = grid.qorigin[a]; g.sd.qscale[a] = grid.qscale[a]; }
-    launch_refit_quantise(nullptr, nodes, (uint4 *) g.qnodes.get(), num_nodes, grid);
     launch_refit_wide(nullptr, nodes, num_nodes, (uint4 *) g.wnodes.get(), u.d_wide_src.get(), u.num_wide, grid);
     launch_tri_frames(nullptr, (const float4 *) g.tris.get(), nt, g.tri_frames.get());
     HIP_TRY(hipGetLastError());
