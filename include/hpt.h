@@ -1242,7 +1242,8 @@ int hpt_scene_get_rebuild_info(const hpt_scene *scene, hpt_rebuild_info *out);
  *
  * Out of scope: a tree of the host builder's quality (PLOC, treelet optimisation, spatial splits); building at
  * hpt_scene_create; hpt_multi_* and the scene the one-shot wrappers keep; a caller-stream or non-blocking variant;
- * exporting the four-wide tree; any automatic policy inside the library (pt_cli --rebuild-device is a caller's). */
+ * exporting the four-wide tree; any automatic policy inside the library (pt_cli --rebuild-device is a caller's).
+ * "Bounded device builds" below bound the depth of this tree; the tree's quality is unchanged by them. */
 typedef struct hpt_device_build_info {
     uint64_t builds;
     uint32_t fell_back, nodes_before, nodes_after, depth_before, depth_after, wide_depth;
@@ -1253,6 +1254,55 @@ int hpt_scene_get_device_build_info(const hpt_scene *scene, hpt_device_build_inf
 int hpt_bvh_device_build_host(const void *lights, int num_lights, const void *spheres, int num_spheres, const void *triangles,
                               const void *new_triangles, int num_triangles, hpt_bvh_info *info, hpt_device_build_info *binfo,
                               void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap);
+
+/* ---- bounded device builds ---------------------------------------------------------------------------------------
+ * hpt_scene_rebuild_device_bounded is hpt_scene_rebuild_device with a tree of at most max_depth levels, so that the depth
+ * of the data's radix tree never sends the call to the host builder.  hpt_bvh_device_build_bounded_host is its
+ * definition, on the host alone, and the device is held to its bytes.  Keys, order, leaf codes, numbering, boxes, grid,
+ * qnodes and the four-wide twin are those of "device builds"; only the topology differs, and it is made top-down.
+ *
+ * max_depth.  0 means 30.  Otherwise it must lie in [need(num_triangles), 30], where need(count) is the smallest k >= 1
+ * with 2^k >= (count + 1) / 2 (1 up to four triangles): the levels a balanced tree of full leaves takes.
+ * A node at level d (the root is level 0) covers the sorted positions [first, first + count), count > 2.  With D the
+ * effective max_depth, need(count) <= D - d holds at the root and is kept by both splits:
+ *   forced, when need(count) == D - d: the left child gets 2 * ((leaves + 1) / 2) triangles, leaves = (count + 1) / 2,
+ *     the right child the rest -- every leaf below is full but possibly the last (the host builder's rule at its limit);
+ *   radix, otherwise: with last = first + count - 1 and gamma the largest p in [first, last) for which
+ *     delta(first, p) > delta(first, last), the left child gets gamma - first + 1 triangles.  On sorted pairs
+ *     delta(first, p) does not increase with p, so gamma is found by bisection, also in ranges below a forced node,
+ *     which the radix tree never had.
+ * A child of 2 triangles or fewer is a leaf code, any other an inner node at level d + 1.  Two triangles or fewer give
+ * the one-node trees of "device builds".
+ * What follows: bvh_depth <= D always; and while no node is forced every range is one of the radix tree's and every
+ * split the radix tree's, so a build with forced_nodes == 0 equals hpt_bvh_device_build_host byte for byte.
+ *
+ * The device numbers the tree level by level as before (count, scan, scatter; 4 bytes read back per level), each node
+ * carrying its range; the host's loop ends after D levels.  Inner nodes left at that point are impossible by the rule
+ * above: the call then returns HPT_ERR_DEVICE ("internal error") and the handle is as it was.  The guard of "device
+ * builds" runs unchanged.  The one fallback left is a four-wide twin too deep for the resume launch's stack
+ * (wide_depth > 19), handled as there (hpt_scene_rebuild, fell_back = 1).  A wide level spans a binary level at least, so
+ * wide_depth <= bvh_depth: a build with max_depth <= 19 can never fall back, and such a depth is accepted up to 2^20
+ * triangles.
+ *
+ * The call fills hpt_device_build_info as hpt_scene_rebuild_device does (hpt_scene_get_device_build_info describes the
+ * last device build of either kind) and hpt_bounded_build_info: the effective max_depth, the number of forced nodes and
+ * the first level that has one (0xFFFFFFFF when none was forced).  hpt_scene_get_bounded_build_info gives zeros before
+ * the first bounded call.  hpt_bvh_device_build_bounded_host takes hpt_bvh_device_build_host's arguments and
+ * conventions, then max_depth and the record to fill (may be NULL); its binfo->fell_back is 1 exactly when
+ * wide_depth > 19.
+ *
+ * hpt_scene_rebuild_device_bounded returns HPT_ERR_INVALID with a message, before the device is touched, for a null
+ * scene, a max_depth outside the values above, or a current device other than the scene's.
+ *
+ * Out of scope: a forced split chosen by position or area (it is by count, on the Morton order); raising the
+ * traversal's 30 levels; everything "device builds" leaves out. */
+typedef struct hpt_bounded_build_info { uint32_t max_depth, forced_nodes, first_forced_level, reserved; } hpt_bounded_build_info;
+int hpt_scene_rebuild_device_bounded(hpt_scene *scene, int max_depth);
+int hpt_scene_get_bounded_build_info(const hpt_scene *scene, hpt_bounded_build_info *out);
+int hpt_bvh_device_build_bounded_host(const void *lights, int num_lights, const void *spheres, int num_spheres, const void *triangles,
+                                      const void *new_triangles, int num_triangles, hpt_bvh_info *info, hpt_device_build_info *binfo,
+                                      void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap, int max_depth,
+                                      hpt_bounded_build_info *bbinfo);
 
 #ifdef __cplusplus
 }

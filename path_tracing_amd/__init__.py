@@ -142,6 +142,10 @@ class DeviceBuildInfo(C.Structure):
                 ("ms_sort", C.c_double), ("ms_topology", C.c_double), ("ms_refit", C.c_double), ("ms_collapse", C.c_double)]
 
 
+class BoundedBuildInfo(C.Structure):
+    _fields_ = [("max_depth", C.c_uint32), ("forced_nodes", C.c_uint32), ("first_forced_level", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _tree_cost_dict(c: TreeCost) -> dict:
     """The fields of hpt_tree_cost (root_extent as a tuple) and, under "bytes", the struct's 120 bytes."""
     d = {n: getattr(c, n) for n, _ in c._fields_ if n != "root_extent"}
@@ -213,7 +217,8 @@ def load_library() -> C.CDLL:
                      "hpt_pose_host", "hpt_scene_set_skin", "hpt_scene_skin", "hpt_skin_host", "hpt_scene_set_morphs", "hpt_scene_morph",
                      "hpt_morph_host",
                      "hpt_scene_tree_cost", "hpt_bvh_cost_host", "hpt_scene_rebuild", "hpt_scene_get_rebuild_info",
-                     "hpt_scene_rebuild_device", "hpt_scene_get_device_build_info", "hpt_bvh_device_build_host"):
+                     "hpt_scene_rebuild_device", "hpt_scene_get_device_build_info", "hpt_bvh_device_build_host",
+                     "hpt_scene_rebuild_device_bounded", "hpt_scene_get_bounded_build_info", "hpt_bvh_device_build_bounded_host"):
             if hasattr(lib, name):          # (an older build loaded through HPT_LIBRARY for an A/B run lacks the newest entry points)
                 getattr(lib, name).restype = C.c_int
         if hasattr(lib, "hpt_sppm_destroy"):
@@ -540,6 +545,19 @@ class Scene:
         info = DeviceBuildInfo()
         _check(self._lib.hpt_scene_get_device_build_info(self._h, C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_}
+
+    def rebuild_device_bounded(self, max_depth=0):
+        """rebuild_device with a tree of at most max_depth levels (include/hpt.h, "bounded device builds"; 0: the traversal's
+        30): afterwards export_bvh() equals device_build_bounded_bvh_host(lights, spheres, read_triangles(), None, max_depth).
+        The depth of the data's radix tree no longer sends the call to rebuild(); a max_depth of 19 or less never falls back.
+        Fills device_build_info() and bounded_build_info().  Blocking."""
+        _check(self._lib.hpt_scene_rebuild_device_bounded(self._h, C.c_int(int(max_depth))))
+
+    def bounded_build_info(self) -> dict:
+        """The last rebuild_device_bounded: dict(max_depth, forced_nodes, first_forced_level); zeros before the first."""
+        info = BoundedBuildInfo()
+        _check(self._lib.hpt_scene_get_bounded_build_info(self._h, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in info._fields_ if n != "reserved"}
 
     # -- ray probes (tests) ---------------------------------------------------------------
     def trace_closest(self, origins, dirs, brute_force=False):
@@ -1027,6 +1045,26 @@ def device_build_bvh_host(lights, spheres, triangles, new_triangles=None) -> dic
         _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), _vp(new_triangles) if new_triangles is not None else None,
         len(triangles), info, C.byref(binfo), qn, qcap, tr, tcap))
     out["build"] = {n: getattr(binfo, n) for n, _ in binfo._fields_}
+    return out
+
+
+def device_build_bounded_bvh_host(lights, spheres, triangles, new_triangles=None, max_depth=0) -> dict:
+    """hpt_bvh_device_build_bounded_host, the definition of Scene.rebuild_device_bounded on the host (no device needed).
+    The keys of device_build_bvh_host and, under "bounded", dict(max_depth, forced_nodes, first_forced_level)."""
+    lib = load_library()
+    lights = np.ascontiguousarray(lights, LIGHT)
+    spheres = np.ascontiguousarray(spheres, SPHERE)
+    triangles = np.ascontiguousarray(triangles, TRIANGLE)
+    if new_triangles is not None:
+        new_triangles = np.ascontiguousarray(new_triangles, TRIANGLE)
+        if len(new_triangles) != len(triangles):
+            raise HptError("hpt error 1: an update keeps the triangle count: %d triangles, %d were handed over" % (len(triangles), len(new_triangles)))
+    binfo = DeviceBuildInfo(); bb = BoundedBuildInfo()
+    out = _export_bvh(lambda info, qn, qcap, tr, tcap: lib.hpt_bvh_device_build_bounded_host(
+        _vp(lights), len(lights), _vp(spheres), len(spheres), _vp(triangles), _vp(new_triangles) if new_triangles is not None else None,
+        len(triangles), info, C.byref(binfo), qn, qcap, tr, tcap, C.c_int(int(max_depth)), C.byref(bb)))
+    out["build"] = {n: getattr(binfo, n) for n, _ in binfo._fields_}
+    out["bounded"] = {n: getattr(bb, n) for n, _ in bb._fields_ if n != "reserved"}
     return out
 
 

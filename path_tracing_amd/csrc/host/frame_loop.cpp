@@ -74,10 +74,13 @@ int hpt_host::run_frame_loop(const std::string &mode, const void *camera, float 
     if(rebuilds && !spin){ std::cerr << "[Error] --rebuild-above needs --spin, --spin-device, --twist-device or --morph-device" << std::endl; return -1; }
     const bool device_builds = motion && motion->rebuild_device;                       // --rebuild-device
     if(device_builds && !spin){ std::cerr << "[Error] --rebuild-device needs --spin, --spin-device, --twist-device or --morph-device" << std::endl; return -1; }
+    if(motion && motion->rebuild_depth >= 0 && !device_builds){ std::cerr << "[Error] --rebuild-depth needs --rebuild-device" << std::endl; return -1; }
+    if(motion && motion->rebuild_depth > 30){ std::cerr << "[Error] --rebuild-depth needs 0 or a depth of 1 to 30" << std::endl; return -1; }
     // a device build, with the time of its four phases (the host builder's when it fell back)
     auto device_build = [&](double &ms, bool &fell_back) -> int {
         hpt_device_build_info di; hpt_rebuild_info ri;
-        if(hpt_scene_rebuild_device(run.scene) != HPT_OK) return hpt_failed("hpt_scene_rebuild_device");
+        if(motion->rebuild_depth >= 0){ if(hpt_scene_rebuild_device_bounded(run.scene, motion->rebuild_depth) != HPT_OK) return hpt_failed("hpt_scene_rebuild_device_bounded"); }
+        else if(hpt_scene_rebuild_device(run.scene) != HPT_OK) return hpt_failed("hpt_scene_rebuild_device");
         if(hpt_scene_get_device_build_info(run.scene, &di) != HPT_OK) return hpt_failed("hpt_scene_get_device_build_info");
         if(hpt_scene_get_rebuild_info(run.scene, &ri) != HPT_OK) return hpt_failed("hpt_scene_get_rebuild_info");
         fell_back = di.fell_back != 0;

@@ -72,7 +72,9 @@ bool moved_run(const std::string &mode, MovedRun &out);
 // With `rebuild_device` (--rebuild-device; needs moving geometry) the rebuilds are hpt_scene_rebuild_device's (include/hpt.h,
 // "device builds"): under `rebuild_above` the same policy with the device build in the host rebuild's place, without it a
 // device build after every frame's update, one "[Rebuild] frame <f> device nodes <n> depth <d> <ms> ms" line each (the sah is
-// not measured then).  A build that fell back to the host builder says "host" for "device".
+// not measured then).  A build that fell back to the host builder says "host" for "device".  With `rebuild_depth` >= 0
+// (--rebuild-depth; needs `rebuild_device`) those builds are hpt_scene_rebuild_device_bounded's with that max_depth (include/hpt.h,
+// "bounded device builds"; 0: the traversal's limit), which the depth of the data's radix tree never sends to the host builder.
 //
 // With `morph_at` (--morph-device; needs `morphs_of`, excludes `triangles_at`, combines with `pose_at` or `skin_at`) the geometry
 // is morphed first: before frame 0 morphs_of fills the sparse targets from the moved scene's records and returns their number,
@@ -94,6 +96,7 @@ struct FrameMotion {
     bool temporal_variance = false;
     double rebuild_above = 0.0;           // 0: never
     bool rebuild_device = false;          // rebuilds are device builds; with rebuild_above == 0: after every update
+    int rebuild_depth = -1;               // -1: hpt_scene_rebuild_device; 0 .. 30: hpt_scene_rebuild_device_bounded with this max_depth
 };
 int run_frame_loop(const std::string &mode, const void *camera, float *image, std::vector<unsigned char> &rgb8, int light_depth,
                    int eye_depth, int W, int H, int frames, int frame_spp, int spl, float radius, double until_rms,

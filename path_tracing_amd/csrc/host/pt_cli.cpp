@@ -30,6 +30,8 @@
 //   --rebuild-device  with --frames and --spin, --spin-device, --twist-device or --morph-device: the rebuilds of --rebuild-above are
 //                     built on the device (hpt_scene_rebuild_device); without --rebuild-above the tree is rebuilt on the device
 //                     before every frame that follows an update.  Same image.
+//   --rebuild-depth D with --rebuild-device: its builds are bounded ones (hpt_scene_rebuild_device_bounded) of at most D levels;
+//                     D is 0 (the traversal's 30) or 1 .. 30, and 19 or less never falls back to the host builder.  Same image.
 //   --morph-device AMP with --frames and --obj: the OBJ morphed through hpt_scene_set_morphs once and hpt_scene_morph per frame: two
 //                     targets on the OBJ's corners, an outward push and a lift that both grow with the corner's height in the mesh,
 //                     under weights that swing with the frame; combines with --spin-device or --twist-device (morph, then the
@@ -81,7 +83,7 @@ int main(int argc, char **argv){
     double morph_amp = 0.0;
     bool orbit = false, reproject = false, guided = false, temporal_variance = false;
     bool rebuild = false; double rebuild_above = 0.0;
-    bool rebuild_device = false;
+    bool rebuild_device = false; int rebuild_depth = -1;
     for(int i = 1; i < argc; ++i){
         std::string arg = argv[i];
         if(arg == "--spp" && i + 1 < argc) spp = std::stoi(argv[++i]);
@@ -115,6 +117,11 @@ int main(int argc, char **argv){
         else if(arg == "--twist-device" && i + 1 < argc){ spin_deg = std::stod(argv[++i]); twist_device = true; }
         else if(arg == "--rebuild-above" && i + 1 < argc){ rebuild_above = std::stod(argv[++i]); rebuild = true; }
         else if(arg == "--rebuild-device") rebuild_device = true;
+        else if(arg == "--rebuild-depth" && i + 1 < argc){
+            char *end = nullptr; const long d = std::strtol(argv[++i], &end, 10);
+            if(!end || *end || end == argv[i] || d < 0 || d > 30){ std::cerr << "[Error] --rebuild-depth needs 0 or a depth of 1 to 30.\n"; return -1; }
+            rebuild_depth = (int) d;
+        }
         else if(arg == "--morph-device" && i + 1 < argc){ morph_amp = std::stod(argv[++i]); morph_device = true; }
         else if(arg == "--reproject") reproject = true;
         else if(arg == "--guided") guided = true;
@@ -161,6 +168,8 @@ int main(int argc, char **argv){
                       << "                    cost (sah of hpt_scene_tree_cost) exceeds R times the last built tree's; R > 1\n"
                       << "  --rebuild-device  the rebuilds of --rebuild-above are built on the device (hpt_scene_rebuild_device); without\n"
                       << "                    --rebuild-above the tree is rebuilt on the device before every frame that follows an update\n"
+                      << "  --rebuild-depth <D>  with --rebuild-device: its builds are bounded to D levels (hpt_scene_rebuild_device_bounded);\n"
+                      << "                    D is 0 (the traversal's 30) or 1 to 30; 19 or less never falls back to the host builder\n"
                       << "  --morph-device <amp>  with --frames and --obj: the OBJ morphed by two targets on the device (hpt_scene_set_morphs once,\n"
                       << "                    hpt_scene_morph per frame): target 0 pushes a corner away from the vertical axis through the centroid,\n"
                       << "                    target 1 lifts it, both by the corner's height in the mesh times a quarter of the OBJ's radius; the\n"
@@ -238,6 +247,7 @@ int main(int argc, char **argv){
     if(rebuild_device && (frames < 1 || !(spin || spin_device || twist_device || morph_device))){
         std::cerr << "[Error] --rebuild-device needs --frames and one of --spin, --spin-device, --twist-device, --morph-device.\n"; return -1;
     }
+    if(rebuild_depth >= 0 && !rebuild_device){ std::cerr << "[Error] --rebuild-depth needs --rebuild-device.\n"; return -1; }
     float F = 50;
     CudaCamera cam = hpt_host::make_cuda_camera(scene.camera, F, W, H);
     std::vector<float3> frame_results((size_t) W * H);
@@ -256,6 +266,7 @@ int main(int argc, char **argv){
         motion.reproject = reproject; motion.guide_spp = guide_spp; motion.guided = guided; motion.temporal_variance = temporal_variance;
         motion.rebuild_above = rebuild ? rebuild_above : 0.0;
         motion.rebuild_device = rebuild_device;
+        motion.rebuild_depth = rebuild_depth;
         if(orbit) motion.camera_at = [&](int f, void *camera84){
             // Rodrigues' rotation of eye - look_at about the unit up vector, in double
             const hpt_host::Camera &c = scene.camera;

@@ -204,6 +204,7 @@ struct hpt_scene {
         hpt::DevBuf<unsigned long long> cost;        // kCostResultWords
         hpt_rebuild_info info{};
         hpt_device_build_info dinfo{};               // the last hpt_scene_rebuild_device (scene_rebuild_device.cpp)
+        hpt_bounded_build_info binfo{};              // the last hpt_scene_rebuild_device_bounded
         hipEvent_t ev[5] = {};                       // ... and the events around its four phases
     } rb;
 

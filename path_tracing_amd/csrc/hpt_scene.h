@@ -190,6 +190,17 @@ const char *refit_host_scene(HostScene &hs, const void *tris, int nt, uint64_t *
 // is the data's (the device falls back to the host builder then).  The device builder (lbvh_kernels.hip) is held to these bytes.
 const char *lbvh_host_scene(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt, HostScene &out);
 
+// The definition of a bounded device build (include/hpt.h, "bounded device builds"): lbvh_host_scene's keys, order, leaf
+// records, numbering, boxes and collapse, over a topology made top-down.  A node at level d whose range needs every one of
+// the D - d levels left (lbvh_need) is split into balanced halves of full leaves -- Builder::build_node's rule -- and any
+// other node by Karras' split of its range.  hs.bvh_depth <= D; while no node is forced the tree is lbvh_host_scene's.
+// max_depth: 0 for kMaxBvhDepth, else within [lbvh_need(nt), kMaxBvhDepth] (lbvh_check_depth: "" or the refusal in msg).
+struct BoundedInfo { uint32_t max_depth = 0, forced_nodes = 0, first_forced_level = 0xFFFFFFFFu; };
+int lbvh_need(int64_t count);          // the smallest k >= 1 with 2^k >= (count + 1) / 2: the levels a range of count triangles needs
+const char *lbvh_check_depth(int nt, int max_depth, int &effective, char *msg, size_t msg_cap);
+const char *lbvh_bounded_host_scene(const void *lights, int nl, const void *spheres, int ns, const void *tris, int nt, int max_depth,
+                                    HostScene &out, BoundedInfo &info);
+
 // ---- poses (include/hpt.h, "poses"): per-part 3 x 4 transforms applied to a rest pose ----
 
 constexpr int kMaxParts = 1 << 20;

@@ -45,6 +45,19 @@ void launch_lbvh_scan(hipStream_t s, uint32_t *block_sum, uint32_t blocks, uint3
 void launch_lbvh_level_scatter(hipStream_t s, const uint2 *child, uint32_t num_inner, uint32_t *from, uint32_t first, uint32_t count, const uint32_t *cnt,
                                const uint32_t *block_sum, float4 *nodes, uint32_t max_nodes);
 
+// Bounded builds ("bounded device builds"), one level per call, count - launch_lbvh_scan - scatter as above, but a node
+// carries its range of sorted positions at its breadth-first number: range[node] = (first, count), count > kMaxLeafTris.
+// count: per lane the split of its node into split[node] (the left child's triangles; 0 for a range that is none) -- forced
+// when the range needs all of levels_left (balanced halves of full leaves), else Karras' split by a bisection over
+// keys_sorted of at most 32 trips -- and its inner children into cnt, per block their sum into block_sum and the block's
+// forced nodes added to *forced (one atomicAdd per block).  scatter: nodes[node] exactly as launch_lbvh_level_scatter writes
+// it, and range[] of the inner children at their new numbers.  Every range and number read is checked against num_tris and
+// max_nodes; a lane that fails a check writes nothing.  Blocks stride over the level under kLbvhMaxBlocks.
+void launch_lbvh_bounded_count(hipStream_t s, const unsigned long long *keys_sorted, uint32_t num_tris, const uint2 *range, uint32_t first, uint32_t count,
+                               uint32_t max_nodes, int levels_left, uint32_t *split, uint32_t *cnt, uint32_t *block_sum, uint32_t *forced);
+void launch_lbvh_bounded_scatter(hipStream_t s, uint2 *range, const uint32_t *split, uint32_t num_tris, uint32_t first, uint32_t count, const uint32_t *cnt,
+                                 const uint32_t *block_sum, float4 *nodes, uint32_t max_nodes);
+
 // The four-wide collapse, one level per call, the same three steps: todo[first .. first + count) holds the binary node every
 // wide node of the level is collapsed from.  collapse: the greedy opening of build_host_scene over the stored float boxes of
 // `nodes` (the inner child of the largest half area first, strict >, first found), the up to four children as binary child

@@ -190,6 +190,95 @@ __global__ __launch_bounds__(kLbvhBlock) void k_lbvh_level_scatter(const uint2 *
     nodes[(size_t) node * 4 + 3] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
 }
 
+// ---- bounded builds: the topology top-down, one level per launch pair (lbvh_bounded_host_scene, scene_build.cpp) ----
+
+// the levels a range of count triangles needs: the smallest k >= 1 with 2^k >= (count + 1) / 2
+__device__ __forceinline__ int need_of(uint32_t count){
+    const uint32_t leaves = (count + 1u) / 2u;
+    return leaves <= 2u ? 1 : 32 - __clz((int) (leaves - 1u));
+}
+// a range a node may have: more than a leaf, inside the sorted positions
+__device__ __forceinline__ bool range_ok(uint2 r, uint32_t num_tris){ return r.y > kLeafTris && r.x < num_tris && r.y <= num_tris - r.x; }
+
+// One lane per node of the level, a block per 256 of them, blocks striding.  The lane's split: forced (balanced halves of full
+// leaves) when its range needs every level left, else Karras' split by a bisection of at most 32 trips.  The block's scan
+// carries the inner children in its low half and the forced nodes in its high half (at most 512 and 256 per block).
+__global__ __launch_bounds__(kLbvhBlock) void k_lbvh_bounded_count(const unsigned long long *__restrict__ keys, uint32_t num_tris,
+                                                                   const uint2 *__restrict__ range, uint32_t first, uint32_t count, uint32_t max_nodes,
+                                                                   int levels_left, uint32_t *__restrict__ split, uint32_t *__restrict__ cnt,
+                                                                   uint32_t *__restrict__ block_sum, uint32_t *__restrict__ forced){
+    const uint32_t chunks = (count + (uint32_t) kLbvhBlock - 1u) / (uint32_t) kLbvhBlock;
+    for(uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x){
+        const uint32_t j = chunk * (uint32_t) kLbvhBlock + threadIdx.x;
+        uint32_t c = 0, f = 0;
+        if(j < count){
+            const uint32_t node = first + j;
+            if(node < max_nodes){
+                const uint2 r = range[node];
+                uint32_t lc = 0;                               // 0: not a range, the scatter writes nothing for it
+                if(range_ok(r, num_tris)){
+                    if(need_of(r.y) >= levels_left){
+                        const uint32_t leaves = (r.y + 1u) / 2u;
+                        lc = 2u * ((leaves + 1u) / 2u);
+                        f = 1u;
+                    } else {
+                        const long long n = (long long) num_tris, a = (long long) r.x, last = a + (long long) r.y - 1;
+                        const unsigned long long ka = keys[a];
+                        const int dnode = delta(keys, n, a, ka, last);
+                        long long lo = a, hi = last;           // delta(a, lo) > dnode >= delta(a, hi)
+                        for(int it = 0; it < 32; ++it){
+                            if(hi - lo <= 1) break;
+                            const long long mid = lo + (hi - lo) / 2;
+                            if(delta(keys, n, a, ka, mid) > dnode) lo = mid; else hi = mid;
+                        }
+                        lc = (uint32_t) (lo - a) + 1u;
+                    }
+                    c = (lc > kLeafTris ? 1u : 0u) + (r.y - lc > kLeafTris ? 1u : 0u);
+                }
+                split[node] = lc;
+            }
+            cnt[j] = c;
+        }
+        uint32_t total;
+        block_scan(c | f << 16, total);
+        if(threadIdx.x == 0){
+            block_sum[chunk] = total & 0xFFFFu;
+            if(total >> 16) atomicAdd(forced, total >> 16);
+        }
+    }
+}
+
+// The record k_lbvh_level_scatter writes, from the node's range and split; the children's ranges go to their new numbers.
+__global__ __launch_bounds__(kLbvhBlock) void k_lbvh_bounded_scatter(uint2 *__restrict__ range, const uint32_t *__restrict__ split, uint32_t num_tris,
+                                                                     uint32_t first, uint32_t count, const uint32_t *__restrict__ cnt,
+                                                                     const uint32_t *__restrict__ block_sum, float4 *__restrict__ nodes, uint32_t max_nodes){
+    const uint32_t chunks = (count + (uint32_t) kLbvhBlock - 1u) / (uint32_t) kLbvhBlock;
+    for(uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x){
+        const uint32_t j = chunk * (uint32_t) kLbvhBlock + threadIdx.x;
+        const uint32_t c = j < count ? cnt[j] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_scan(c, total);
+        const uint32_t node = first + j;
+        if(j >= count || node >= max_nodes) continue;
+        const uint2 r = range[node];
+        const uint32_t lc = split[node];
+        if(!range_ok(r, num_tris) || lc == 0u || lc >= r.y) continue;
+        uint32_t o = first + count + block_sum[chunk] + ex;
+        const uint32_t cf[2] = { r.x, r.x + lc }, cc[2] = { lc, r.y - lc };
+        uint32_t code[2];
+#pragma unroll
+        for(int side = 0; side < 2; ++side){
+            if(cc[side] <= kLeafTris){ code[side] = leaf_code(cf[side], cc[side]); continue; }
+            if(o < max_nodes){ range[o] = make_uint2(cf[side], cc[side]); code[side] = o; } else code[side] = kEmpty;     // (the host has checked the total: never taken)
+            ++o;
+        }
+        nodes[(size_t) node * 4] = make_float4(INFINITY, INFINITY, INFINITY, __uint_as_float(code[0]));
+        nodes[(size_t) node * 4 + 1] = make_float4(-INFINITY, -INFINITY, -INFINITY, __uint_as_float(code[1]));
+        nodes[(size_t) node * 4 + 2] = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);
+        nodes[(size_t) node * 4 + 3] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+    }
+}
+
 // ---- the four-wide collapse ----
 
 struct Kids { uint32_t code[4], src[4]; float area[4]; int n; };
@@ -330,6 +419,20 @@ void launch_lbvh_level_scatter(hipStream_t s, const uint2 *child, uint32_t num_i
                                const uint32_t *block_sum, float4 *nodes, uint32_t max_nodes){
     if(count == 0) return;
     hipLaunchKernelGGL(k_lbvh_level_scatter, dim3(lbvh_blocks(count)), dim3(kLbvhBlock), 0, s, child, num_inner, from, first, count, cnt, block_sum, nodes,
+                       max_nodes);
+}
+
+void launch_lbvh_bounded_count(hipStream_t s, const unsigned long long *keys_sorted, uint32_t num_tris, const uint2 *range, uint32_t first, uint32_t count,
+                               uint32_t max_nodes, int levels_left, uint32_t *split, uint32_t *cnt, uint32_t *block_sum, uint32_t *forced){
+    if(count == 0) return;
+    hipLaunchKernelGGL(k_lbvh_bounded_count, stride_grid(count), dim3(kLbvhBlock), 0, s, keys_sorted, num_tris, range, first, count, max_nodes, levels_left,
+                       split, cnt, block_sum, forced);
+}
+
+void launch_lbvh_bounded_scatter(hipStream_t s, uint2 *range, const uint32_t *split, uint32_t num_tris, uint32_t first, uint32_t count, const uint32_t *cnt,
+                                 const uint32_t *block_sum, float4 *nodes, uint32_t max_nodes){
+    if(count == 0) return;
+    hipLaunchKernelGGL(k_lbvh_bounded_scatter, stride_grid(count), dim3(kLbvhBlock), 0, s, range, split, num_tris, first, count, cnt, block_sum, nodes,
                        max_nodes);
 }
 

@@ -1191,15 +1191,15 @@ inline int lbvh_delta(const uint64_t *keys, int64_t n, int64_t i, int64_t j){
     return 64 + __builtin_clz((uint32_t) i ^ (uint32_t) j);
 }
 
-} // namespace
-
-const char *lbvh_host_scene(const void *lights_v, int nl, const void *spheres_v, int ns, const void *tris_v, int nt, HostScene &hs){
+// What lbvh_host_scene and lbvh_bounded_host_scene share ahead of the topology: materials, rounds and lights, the keys, the
+// stable order and the leaf records in it.  keys: the sorted keys, one per leaf slot.
+const char *lbvh_sorted_leaves(const void *lights_v, int nl, const void *spheres_v, int ns, const void *tris_v, int nt, HostScene &hs,
+                               std::vector<uint64_t> &keys){
     if(nl < 0 || ns < 0 || nt < 0) return "negative primitive count";
     if((nl > 0 && !lights_v) || (ns > 0 && !spheres_v) || (nt > 0 && !tris_v)) return "null primitive array";
     if((uint64_t) nt >= (1ull << 28)) return "too many triangles (limit 2^28)";
     const RefSphere *spheres = (const RefSphere *) spheres_v;
     const RefTriangle *tris = (const RefTriangle *) tris_v;
-    auto t0 = std::chrono::steady_clock::now();
 
     hs = HostScene();
     hs.num_spheres = ns; hs.num_lights = nl; hs.num_tris = nt;
@@ -1232,7 +1232,7 @@ const char *lbvh_host_scene(const void *lights_v, int nl, const void *spheres_v,
     std::vector<uint32_t> order(n);
     for(size_t i = 0; i < n; ++i) order[i] = (uint32_t) i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){ return key_of[a] < key_of[b]; });
-    std::vector<uint64_t> keys(n);
+    keys.resize(n);
     hs.tris.resize(n);
     for(size_t s = 0; s < n; ++s){
         const uint32_t i = order[s];
@@ -1243,18 +1243,69 @@ const char *lbvh_host_scene(const void *lights_v, int nl, const void *spheres_v,
         d.material = mat_of[i];
         d.flags = (tris[i].m.eta <= 0.0f) ? 1u : 0u;
     }
+    return "";
+}
+
+inline uint32_t lbvh_leaf_code(int64_t first, int64_t count){ return kLeafFlag | ((uint32_t) first << 3) | (uint32_t) (count - 1); }
+
+// the trees of kMaxLeafTris triangles or fewer: one node
+void lbvh_one_node(HostScene &hs, int nt){
+    BvhNode blank; memset(&blank, 0, sizeof blank);
+    hs.nodes.assign(1, blank);
+    hs.nodes[0].left = nt > 0 ? lbvh_leaf_code(0, nt) : kEmptyChild;
+    hs.nodes[0].right = kEmptyChild;
+    hs.level_begin = { 0u, 1u };
+    hs.bvh_depth = nt > 0 ? 1 : 0;
+}
+
+// numbering: breadth-first, build_host_scene's rule -- level by level, within a level the inner children in order, left
+// before right; nodes no child code names drop out.  rl, rr: the child codes of every node in the topology's own numbering
+// (node 0 is the root; an inner child is the number of its node there).
+void lbvh_number(HostScene &hs, const std::vector<uint32_t> &rl, const std::vector<uint32_t> &rr){
+    BvhNode blank; memset(&blank, 0, sizeof blank);
+    std::vector<uint32_t> from(1, 0u);               // the topology's number of every node, breadth-first
+    size_t lvl_begin = 0, lvl_end = 1;
+    while(lvl_begin < lvl_end){
+        hs.level_begin.push_back((uint32_t) lvl_begin);
+        for(size_t q = lvl_begin; q < lvl_end; ++q){
+            BvhNode nd = blank;
+            const uint32_t c[2] = { rl[from[q]], rr[from[q]] };
+            uint32_t out[2];
+            for(int side = 0; side < 2; ++side){
+                if(c[side] & kLeafFlag){ out[side] = c[side]; continue; }
+                out[side] = (uint32_t) from.size();
+                from.push_back(c[side]);
+            }
+            nd.left = out[0]; nd.right = out[1];
+            hs.nodes.push_back(nd);
+        }
+        lvl_begin = lvl_end; lvl_end = from.size();
+    }
+    hs.level_begin.push_back((uint32_t) lvl_end);
+    hs.bvh_depth = (int) hs.level_begin.size() - 1;       // the builder's count: the deepest leaf's depth, root = 0
+}
+
+// everything that is a function of the vertex positions: the refit's own lines, then the collapse over the boxes it wrote
+const char *lbvh_boxes(HostScene &hs, const void *tris_v, int nt, std::chrono::steady_clock::time_point t0){
+    const char *e = refit_host_scene(hs, tris_v, nt);
+    if(e && *e) return e;
+    collapse_wide(hs);
+    hs.ms_bvh_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return "";
+}
+
+} // namespace
+
+const char *lbvh_host_scene(const void *lights_v, int nl, const void *spheres_v, int ns, const void *tris_v, int nt, HostScene &hs){
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> keys;
+    if(const char *e = lbvh_sorted_leaves(lights_v, nl, spheres_v, ns, tris_v, nt, hs, keys); e && *e) return e;
+    const size_t n = (size_t) nt;
 
     // topology: the binary radix tree over the sorted pairs; child codes in radix numbering (inner node k splits its range
     // behind position gamma: the left child is inner node gamma, the right one gamma + 1, a range of kMaxLeafTris or fewer a leaf)
-    auto leaf_code = [](int64_t first, int64_t count){ return kLeafFlag | ((uint32_t) first << 3) | (uint32_t) (count - 1); };
-    BvhNode blank; memset(&blank, 0, sizeof blank);
-    if(nt <= kMaxLeafTris){
-        hs.nodes.assign(1, blank);
-        hs.nodes[0].left = nt > 0 ? leaf_code(0, nt) : kEmptyChild;
-        hs.nodes[0].right = kEmptyChild;
-        hs.level_begin = { 0u, 1u };
-        hs.bvh_depth = nt > 0 ? 1 : 0;
-    } else {
+    if(nt <= kMaxLeafTris) lbvh_one_node(hs, nt);
+    else {
         const int64_t N = (int64_t) nt;
         std::vector<uint32_t> rl(n - 1), rr(n - 1);
         for(int64_t i = 0; i < N - 1; ++i){
@@ -1275,38 +1326,86 @@ const char *lbvh_host_scene(const void *lights_v, int nl, const void *spheres_v,
             const int64_t gamma = i + s * d + std::min<int64_t>(d, 0);
             const int64_t first = std::min(i, j), last = std::max(i, j);
             const int64_t lc = gamma - first + 1, rc = last - gamma;
-            rl[(size_t) i] = lc <= kMaxLeafTris ? leaf_code(first, lc) : (uint32_t) gamma;
-            rr[(size_t) i] = rc <= kMaxLeafTris ? leaf_code(gamma + 1, rc) : (uint32_t) (gamma + 1);
+            rl[(size_t) i] = lc <= kMaxLeafTris ? lbvh_leaf_code(first, lc) : (uint32_t) gamma;
+            rr[(size_t) i] = rc <= kMaxLeafTris ? lbvh_leaf_code(gamma + 1, rc) : (uint32_t) (gamma + 1);
         }
-        // numbering: breadth-first, build_host_scene's rule -- level by level, within a level the inner children in order, left
-        // before right; radix nodes no child code names drop out
-        std::vector<uint32_t> from(1, 0u);               // radix number of every node, breadth-first
-        size_t lvl_begin = 0, lvl_end = 1;
-        while(lvl_begin < lvl_end){
-            hs.level_begin.push_back((uint32_t) lvl_begin);
-            for(size_t q = lvl_begin; q < lvl_end; ++q){
-                BvhNode nd = blank;
-                const uint32_t c[2] = { rl[from[q]], rr[from[q]] };
-                uint32_t out[2];
-                for(int side = 0; side < 2; ++side){
-                    if(c[side] & kLeafFlag){ out[side] = c[side]; continue; }
-                    out[side] = (uint32_t) from.size();
-                    from.push_back(c[side]);
-                }
-                nd.left = out[0]; nd.right = out[1];
-                hs.nodes.push_back(nd);
-            }
-            lvl_begin = lvl_end; lvl_end = from.size();
-        }
-        hs.level_begin.push_back((uint32_t) lvl_end);
-        hs.bvh_depth = (int) hs.level_begin.size() - 1;       // the builder's count: the deepest leaf's depth, root = 0
+        lbvh_number(hs, rl, rr);
     }
-    // everything that is a function of the vertex positions: the refit's own lines, then the collapse over the boxes it wrote
-    const char *e = refit_host_scene(hs, tris_v, nt);
-    if(e && *e) return e;
-    collapse_wide(hs);
-    hs.ms_bvh_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return lbvh_boxes(hs, tris_v, nt, t0);
+}
+
+// ---- bounded device builds (include/hpt.h, "bounded device builds") --------------------------------------------------------
+
+int lbvh_need(int64_t count){
+    const int64_t leaves = (count + 1) / 2;
+    int k = 1;
+    while((1ll << k) < leaves) ++k;
+    return k;
+}
+
+const char *lbvh_check_depth(int nt, int max_depth, int &effective, char *msg, size_t msg_cap){
+    effective = max_depth == 0 ? kMaxBvhDepth : max_depth;
+    const int need = lbvh_need(nt < 0 ? 0 : nt);
+    if(max_depth < 0 || max_depth > kMaxBvhDepth || effective < need){
+        snprintf(msg, msg_cap, "max_depth %d: must be 0 (the limit, %d) or lie in [%d, %d] for %d triangles", max_depth, kMaxBvhDepth, need, kMaxBvhDepth, nt);
+        return msg;
+    }
     return "";
+}
+
+const char *lbvh_bounded_host_scene(const void *lights_v, int nl, const void *spheres_v, int ns, const void *tris_v, int nt, int max_depth,
+                                    HostScene &hs, BoundedInfo &bi){
+    static thread_local char msg[160];
+    auto t0 = std::chrono::steady_clock::now();
+    bi = BoundedInfo();
+    if(nt >= 0 && (uint64_t) nt < (1ull << 28)){          // (the other counts are refused below, in the shared lines)
+        int D = 0;
+        if(const char *e = lbvh_check_depth(nt, max_depth, D, msg, sizeof msg); *e) return e;
+        bi.max_depth = (uint32_t) D;
+    }
+    std::vector<uint64_t> keys;
+    if(const char *e = lbvh_sorted_leaves(lights_v, nl, spheres_v, ns, tris_v, nt, hs, keys); e && *e) return e;
+    const int D = (int) bi.max_depth;
+
+    // topology, top-down: a node is its range of sorted positions and its level; nodes are numbered as they are made
+    if(nt <= kMaxLeafTris) lbvh_one_node(hs, nt);
+    else {
+        struct Range { int64_t first, count; int level; };
+        std::vector<Range> todo(1, Range{ 0, (int64_t) nt, 0 });
+        std::vector<uint32_t> rl, rr;
+        const uint64_t *k = keys.data();
+        const int64_t N = (int64_t) nt;
+        for(size_t q = 0; q < todo.size(); ++q){
+            const Range r = todo[q];
+            const int64_t leaves = (r.count + 1) / 2;
+            int64_t lc;
+            if(lbvh_need(r.count) >= D - r.level){         // forced: full leaves, the left half rounded up
+                lc = 2 * ((leaves + 1) / 2);
+                bi.forced_nodes += 1;
+                if(bi.first_forced_level == 0xFFFFFFFFu) bi.first_forced_level = (uint32_t) r.level;
+            } else {                                       // Karras' split of the range: delta(first, p) does not increase with p
+                const int64_t last = r.first + r.count - 1;
+                const int dnode = lbvh_delta(k, N, r.first, last);
+                int64_t lo = r.first, hi = last;           // delta(first, lo) > dnode >= delta(first, hi)
+                while(hi - lo > 1){
+                    const int64_t mid = lo + (hi - lo) / 2;
+                    if(lbvh_delta(k, N, r.first, mid) > dnode) lo = mid; else hi = mid;
+                }
+                lc = lo - r.first + 1;
+            }
+            const int64_t rc = r.count - lc;
+            uint32_t code[2];
+            const int64_t cf[2] = { r.first, r.first + lc }, cc[2] = { lc, rc };
+            for(int side = 0; side < 2; ++side){
+                if(cc[side] <= kMaxLeafTris){ code[side] = lbvh_leaf_code(cf[side], cc[side]); continue; }
+                code[side] = (uint32_t) todo.size();
+                todo.push_back(Range{ cf[side], cc[side], r.level + 1 });
+            }
+            rl.push_back(code[0]); rr.push_back(code[1]);
+        }
+        lbvh_number(hs, rl, rr);
+    }
+    return lbvh_boxes(hs, tris_v, nt, t0);
 }
 
 // ---- tree cost (include/hpt.h, "tree cost") --------------------------------------------------------------------------------

@@ -3,6 +3,8 @@
 // the sort, the radix tree, the breadth-first numbers, the four-wide collapse -- and the refit launches (scene_update.cpp,
 // refit_tree_boxes) everything that is a function of the vertex positions.  The host's share is the level loops (4 bytes read
 // back per level, capped by a constant, never by a device condition), the limits, the guard and the swap.
+// A bounded build (hpt_scene_rebuild_device_bounded, to the bytes of lbvh_bounded_host_scene) runs the same stages around another
+// topology step: no radix tree, but a level loop whose lanes split their node's range (forced or Karras' split), capped by max_depth.
 // Compiled with hipcc (host code only).
 #include "hpt_host.h"
 
@@ -11,6 +13,7 @@
 using namespace hpt;
 
 static_assert(sizeof(hpt_device_build_info) == 64, "ABI record: keep path_tracing_amd/__init__.py in step");
+static_assert(sizeof(hpt_bounded_build_info) == 16, "ABI record: keep path_tracing_amd/__init__.py in step");
 static_assert(kMaxLeafTris == 2, "lbvh_kernels.hip builds leaves of two triangles (kLeafTris)");
 
 namespace {
@@ -29,13 +32,10 @@ int fall_back(hpt_scene *s){
     return HPT_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int hpt_scene_rebuild_device(hpt_scene *s){
-    if(!s) return fail(HPT_ERR_INVALID, "null scene");
-    if(int rc = on_scene_device(s)) return rc;
+// Both device builds.  max_depth == 0: hpt_scene_rebuild_device, the radix tree, which falls back beyond kMaxBvhDepth levels;
+// else a bounded build of at most max_depth levels (checked by the caller).
+int build_on_device(hpt_scene *s, int max_depth){
+    const bool bounded = max_depth > 0;
     hpt_scene::Geometry &g = s->geo;
     hpt_scene::Update &u = s->up;
     hpt_scene::Rebuild &rb = s->rb;
@@ -51,7 +51,7 @@ int hpt_scene_rebuild_device(hpt_scene *s){
     // fresh buffers and the builder's scratch; the handle is touched only when all of them are filled
     DevBuf<BvhNode> nodes; DevBuf<QBvhNode> qnodes; DevBuf<WideNode> wnodes; DevBuf<DevTriangle> dtris; DevBuf<float4> frames; DevBuf<uint4> wide_src;
     DevBuf<unsigned long long> keys, keys_sorted; DevBuf<uint32_t> idx, idx_sorted, rank, from, cnt, block_sum, total; DevBuf<uint2> child;
-    DevBuf<uint4> kid_code; DevBuf<float> exact; DevBuf<unsigned char> sort_tmp;
+    DevBuf<uint4> kid_code; DevBuf<float> exact; DevBuf<unsigned char> sort_tmp; DevBuf<uint32_t> forced;
     const size_t sort_bytes = std::max<size_t>(lbvh_sort_tmp_bytes(n), 1);
     hipError_t e = reserve_all(max_nodes, nodes, qnodes, wnodes, wide_src, kid_code, cnt, child);
     if(e == hipSuccess) e = reserve_all(max_nodes, dtris, keys, keys_sorted, idx, idx_sorted, rank);
@@ -60,6 +60,7 @@ int hpt_scene_rebuild_device(hpt_scene *s){
     if(e == hipSuccess) e = exact.reserve((size_t) max_nodes * 6);
     if(e == hipSuccess) e = block_sum.reserve(lbvh_blocks(max_nodes) + 1u);
     if(e == hipSuccess) e = total.reserve(1);
+    if(e == hipSuccess && bounded) e = forced.reserve((size_t) kMaxBvhDepth);
     if(e == hipSuccess) e = sort_tmp.reserve(sort_bytes);
     if(e == hipSuccess) e = rb.cost.reserve(kCostResultWords);
     if(e != hipSuccess) return fail_hip("device build: buffers", e);
@@ -91,6 +92,7 @@ int hpt_scene_rebuild_device(hpt_scene *s){
     launch_lbvh_permute(nullptr, (const float4 *) g.tris.get(), rank.get(), n, num_rounds, d_tris);
     std::vector<uint32_t> level_begin;
     uint32_t num_nodes = 1;
+    hpt_bounded_build_info bb{ (uint32_t) max_depth, 0u, 0xFFFFFFFFu, 0u };
     if(nt <= kMaxLeafTris){
         BvhNode root; memset(&root, 0, sizeof root);
         for(int a = 0; a < 3; ++a){ root.lmin[a] = root.rmin[a] = INFINITY; root.lmax[a] = root.rmax[a] = -INFINITY; }
@@ -98,6 +100,38 @@ int hpt_scene_rebuild_device(hpt_scene *s){
         root.right = kEmptyChild;
         HIP_TRY(hipMemcpy(nodes.get(), &root, sizeof root, hipMemcpyHostToDevice));
         level_begin = { 0u, 1u };
+    } else if(bounded){
+        // a node is its range of sorted positions, at its breadth-first number: `child` holds the ranges, `rank` (free again
+        // after the permutation) the splits; the forced nodes are counted per level
+        uint2 *range = child.get();
+        const uint2 whole = make_uint2(0u, n);
+        HIP_TRY(hipMemcpyAsync(range, &whole, sizeof whole, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(forced.get(), 0, (size_t) kMaxBvhDepth * sizeof(uint32_t), nullptr));
+        uint32_t first = 0, count = 1;
+        bool done = false;
+        for(int level = 0; level < max_depth && !done; ++level){
+            level_begin.push_back(first);
+            uint32_t next = 0;
+            launch_lbvh_bounded_count(nullptr, keys_sorted.get(), n, range, first, count, max_nodes, max_depth - level, rank.get(), cnt.get(),
+                                      block_sum.get(), forced.get() + level);
+            launch_lbvh_scan(nullptr, block_sum.get(), lbvh_blocks(count), total.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(&next, total.get(), sizeof next, hipMemcpyDeviceToHost));
+            if((uint64_t) first + count + next > max_nodes) return fail(HPT_ERR_DEVICE, "device build: internal error: more nodes than triangles");
+            launch_lbvh_bounded_scatter(nullptr, range, rank.get(), n, first, count, cnt.get(), block_sum.get(), d_nodes, max_nodes);
+            first += count; count = next;
+            done = count == 0;
+        }
+        HIP_TRY(hipGetLastError());
+        if(!done){ HIP_TRY(hipDeviceSynchronize()); return fail(HPT_ERR_DEVICE, "device build: internal error: inner nodes below max_depth; the handle is as it was"); }
+        level_begin.push_back(first);
+        num_nodes = first;
+        uint32_t per_level[kMaxBvhDepth];
+        HIP_TRY(hipMemcpy(per_level, forced.get(), sizeof per_level, hipMemcpyDeviceToHost));
+        for(int level = 0; level < kMaxBvhDepth; ++level){
+            if(per_level[level] && bb.first_forced_level == 0xFFFFFFFFu) bb.first_forced_level = (uint32_t) level;
+            bb.forced_nodes += per_level[level];
+        }
     } else {
         const uint32_t num_inner = n - 1u;
         launch_lbvh_radix(nullptr, keys_sorted.get(), n, child.get());
@@ -154,7 +188,11 @@ int hpt_scene_rebuild_device(hpt_scene *s){
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(rb.ev[4], nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    if(!wide_fits(wide_depth)) return fall_back(s);
+    if(!wide_fits(wide_depth)){
+        if(int rc = fall_back(s)) return rc;
+        if(bounded) rb.binfo = bb;
+        return HPT_OK;
+    }
 
     // ---- the guard: the new tree measured where it lies; a malformed one never reaches a trace kernel
     HIP_TRY(hipMemsetAsync(rb.cost.get(), 0, kCostResultWords * sizeof(unsigned long long), nullptr));
@@ -187,6 +225,31 @@ int hpt_scene_rebuild_device(hpt_scene *s){
     di.builds += 1; di.fell_back = 0;
     di.nodes_after = num_nodes; di.depth_after = (uint32_t) bvh_depth; di.wide_depth = (uint32_t) wide_depth;
     di.ms_sort = ms[0]; di.ms_topology = ms[1]; di.ms_refit = ms[2]; di.ms_collapse = ms[3];
+    if(bounded) rb.binfo = bb;
+    return HPT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int hpt_scene_rebuild_device(hpt_scene *s){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    if(int rc = on_scene_device(s)) return rc;
+    return build_on_device(s, 0);
+}
+
+int hpt_scene_rebuild_device_bounded(hpt_scene *s, int max_depth){
+    if(!s) return fail(HPT_ERR_INVALID, "null scene");
+    char msg[160]; int D = 0;
+    if(const char *e = lbvh_check_depth(s->geo.nt, max_depth, D, msg, sizeof msg); *e) return fail(HPT_ERR_INVALID, e);
+    if(int rc = on_scene_device(s)) return rc;
+    return build_on_device(s, D);
+}
+
+int hpt_scene_get_bounded_build_info(const hpt_scene *s, hpt_bounded_build_info *out){
+    if(!s || !out) return fail(HPT_ERR_INVALID, "null argument");
+    *out = s->rb.binfo;
     return HPT_OK;
 }
 
@@ -215,6 +278,30 @@ int hpt_bvh_device_build_host(const void *lights, int nl, const void *spheres, i
         binfo->fell_back = (hs.bvh_depth > kMaxBvhDepth || !wide_fits(hs.wide_depth)) ? 1u : 0u;
         binfo->nodes_after = (uint32_t) hs.nodes.size(); binfo->depth_after = (uint32_t) hs.bvh_depth; binfo->wide_depth = (uint32_t) hs.wide_depth;
     }
+    return export_host_tree(hs, info, qnodes_out, qnodes_cap, tris_out, tris_cap);
+}
+
+int hpt_bvh_device_build_bounded_host(const void *lights, int nl, const void *spheres, int ns, const void *tris, const void *new_tris, int nt,
+                                      hpt_bvh_info *info, hpt_device_build_info *binfo, void *qnodes_out, size_t qnodes_cap, void *tris_out, size_t tris_cap,
+                                      int max_depth, hpt_bounded_build_info *bbinfo){
+    if(!info) return fail(HPT_ERR_INVALID, "null info");
+    HostScene hs; BoundedInfo bi;
+    const char *err = lbvh_bounded_host_scene(lights, nl, spheres, ns, tris, nt, max_depth, hs, bi);
+    if(err && *err) return fail(HPT_ERR_INVALID, err);
+    if(new_tris){
+        char msg[200];
+        err = check_triangle_update(tris, nt, new_tris, nt, msg, sizeof msg);
+        if(err && *err) return fail(HPT_ERR_INVALID, err);
+        err = refit_host_scene(hs, new_tris, nt);
+        if(err && *err) return fail(HPT_ERR_INVALID, err);
+    }
+    if(binfo){
+        memset(binfo, 0, sizeof *binfo);
+        binfo->builds = 1;
+        binfo->fell_back = wide_fits(hs.wide_depth) ? 0u : 1u;
+        binfo->nodes_after = (uint32_t) hs.nodes.size(); binfo->depth_after = (uint32_t) hs.bvh_depth; binfo->wide_depth = (uint32_t) hs.wide_depth;
+    }
+    if(bbinfo) *bbinfo = hpt_bounded_build_info{ bi.max_depth, bi.forced_nodes, bi.first_forced_level, 0u };
     return export_host_tree(hs, info, qnodes_out, qnodes_cap, tris_out, tris_cap);
 }
 
